@@ -12,23 +12,29 @@ is reset to the initial point on the device (no host round trip), so every
 timed step is a full Newton step.  The timed steps run the production path:
 HIP-graph replay for steps whose factor does not fork (C4's batches), eager
 launches with at most one step in flight for the look-ahead factor (C3, C2,
-C5) -- each line's config.timing says which; a second, instrumented pass with
-per-phase HIP events gives the phase split and the roofline numbers.
+C5) -- each line's config.timing says which.
+
+A plain run does only what the headline figure needs: set up, warm up, time
+the steps, write the outputs (--dump-outputs DIR), print the result line.
+--full adds everything else, each part with its own --no-* switch: the CPU
+baselines, a second, instrumented pass with per-phase HIP events (the phase
+split and the roofline numbers), and the sub-objects below.
 
 Multi-GPU (torchrun, one process per GPU):
   * headline (C3): each rank solves its own independent QP -- the path does
     not shard a single QP (replicas, weak scaling);
-  * "batched" sub-object (C4, BASELINE.json configs[3]): the 1024-QP batch
+  * "batched" sub-object (--full; C4, BASELINE.json configs[3]): the 1024-QP batch
     (n=256, m=64) sharded over the ranks, strong scaling, with ONE all-reduce
     (MAX) of the device-computed convergence summary per step -- the only
     collective (SURVEY.md §8e);
-  * "batched_shard" sub-object (one GPU only): C4 at 128 QPs, the shard one
+  * "batched_shard" sub-object (--full, one GPU only): C4 at 128 QPs, the shard one
     rank holds in the 8-GPU job, measured alone;
-  * "configs" sub-object (default c3 run): C2 (normal equations, n=2048) and
+  * "configs" sub-object (--full c3 run): C2 (normal equations, n=2048) and
     C5 (n=16384, fp32 factor + fp64 refinement), replicas like the headline,
     each with its own roofline and CPU baseline (--no-configs skips them).
 
     python bench.py [--gpus N] [--steps K] [--warmup W] [--workload c3|c2|c4|c5|...]
+                    [--dump-outputs DIR] [--full]
 """
 import argparse
 import json
@@ -118,6 +124,44 @@ def load_json(rel):
     return out
 
 
+DUMP_BUDGET_BYTES = 64 << 20  # --dump-outputs writes at most this much in all
+
+
+def dump_outputs(dirname, arrays):
+    """DIR/<name>.npy (float64) for each array a caller of the timed path
+    receives after its last step."""
+    import numpy as np
+    os.makedirs(dirname, exist_ok=True)
+    total = 0
+    for name, a in arrays.items():
+        a = np.ascontiguousarray(a, dtype=np.float64)
+        total += a.nbytes
+        assert total <= DUMP_BUDGET_BYTES, f"--dump-outputs: {name} takes the dump past {DUMP_BUDGET_BYTES} bytes"
+        np.save(os.path.join(dirname, name + ".npy"), a)
+
+
+def single_outputs(qp):
+    """What the last step left in an Optimizer: the new iterate, the affine
+    and the combined Newton directions, the residuals, the scalar block."""
+    import numpy as np
+    return {"vars": qp.vars(), "daff": qp.daff(), "dir": qp.dir(), "residuals": qp.residuals(),
+            "scalars": np.array(list(qp.scalars().values()))}  # in ipmz_amd.SC's order
+
+
+def batch_outputs(qp, summary):
+    """The same for a Batch, one row per QP (iterate and combined direction;
+    a fixed, evenly spaced subset of the QPs when all of them would not fit
+    the budget), every QP's scalar block and the reduced summary."""
+    import numpy as np
+    per_qp = 2 * qp.state_len * 8
+    keep = max(1, min(qp.batch, (DUMP_BUDGET_BYTES - qp.batch * 8 * 16 - 4096) // per_qp))
+    idx = np.unique(np.linspace(0, qp.batch - 1, keep).astype(np.int64))
+    return {"qp_index": idx.astype(np.float64),
+            "vars": np.stack([qp.state(int(i), 0) for i in idx]),
+            "dir": np.stack([qp.state(int(i), 2) for i in idx]),
+            "scalars": qp.batch_scalars(), "summary": summary}
+
+
 def timed(world, dist, torch, steps, fn):
     """Barrier + sync on both sides of exactly `steps` calls; max over ranks."""
     if world > 1:
@@ -137,7 +181,7 @@ def timed(world, dist, torch, steps, fn):
     return elapsed
 
 
-def run_batched(I, ctx, args, world, rank, dist, torch, wl, nbatch):
+def run_batched(I, ctx, args, world, rank, dist, torch, wl, nbatch, dump=None):
     """C4: this rank's contiguous shard of the batch as one Batch; per step
     one device summary kernel + ONE all-reduce (MAX) on the solver's stream."""
     from ipmz_amd.dist import reduce_summary, shard
@@ -157,6 +201,8 @@ def run_batched(I, ctx, args, world, rank, dist, torch, wl, nbatch):
         one_step()
     elapsed = timed(world, dist, torch, args.steps, one_step)
     graph = qp.last_step_graph()
+    if dump and rank == 0:
+        dump_outputs(dump, batch_outputs(qp, buf.cpu().numpy()))
     # instrumented pass (per-phase HIP events, eager launches)
     N = wl["n"] + wl["m"] + wl["p"]
     ph, fac = None, None
@@ -176,7 +222,8 @@ def run_batched(I, ctx, args, world, rank, dist, torch, wl, nbatch):
                    "qps_on_rank0": B, "parallelism": f"batch sharded over {world} rank(s); one all-reduce (MAX) "
                                                      "of {max res, max mu, unconverged} per step",
                    "timing": ("HIP-graph replay" if graph else "eager launches") + " of the whole step + the "
-                             "summary kernel + the all-reduce; phases from a second, instrumented pass"},
+                             "summary kernel + the all-reduce" +
+                             ("" if args.no_instrumented else "; phases from a second, instrumented pass")},
         "phase_ms_per_step": ({k: ph[k] / args.steps for k in ("step", "assemble", "factor", "solve", "eval")}
                               if ph else None),
         "roofline": {"bound": "mfma", "kernel": "batched factor phase (whole left-looking LDL^T of each QP in "
@@ -206,9 +253,9 @@ def shard_line(I, ctx, args, dist, torch):
     return sub
 
 
-def run_single(I, ctx, args, world, dist, torch, workload):
-    """One QP per rank (replicas): the timed HIP-graph pass, then the
-    instrumented pass for the phase split and the roofline."""
+def run_single(I, ctx, args, world, dist, torch, workload, dump=None):
+    """One QP per rank (replicas): the timed production-path pass, then
+    (--full) the instrumented pass for the phase split and the roofline."""
     wl = WORKLOADS[workload]
     n, m, p = wl["n"], wl["m"], wl["p"]
     Nk = n + m + p
@@ -226,6 +273,8 @@ def run_single(I, ctx, args, world, dist, torch, workload):
         qp.step(flags)
     elapsed = timed(world, dist, torch, args.steps, lambda: qp.step(flags))
     graph = qp.last_step_graph()
+    if dump and rank == 0:
+        dump_outputs(dump, single_outputs(qp))
     ph = None
     if not args.no_instrumented:
         qp.set_timing(True)  # resets the phase accumulators; eager launches with HIP events
@@ -258,7 +307,8 @@ def run_single(I, ctx, args, world, dist, torch, workload):
                    "timing": ("HIP-graph replay of the whole step" if graph else
                               "eager launches of the whole step (its factor forks onto the look-ahead streams), "
                               "at most one step in flight") +
-                             " (production path); phases from a second, instrumented pass",
+                             " (production path)" +
+                             ("" if args.no_instrumented else "; phases from a second, instrumented pass"),
                    "description": wl["desc"]},
         "restarts": s["restarts"],
     }
@@ -329,7 +379,16 @@ def main():
     ap.add_argument("--ir-tol", type=float, default=1e-12, help="c5: refinement tolerance")
     ap.add_argument("--batch", type=int, default=0, help="c4: override the global batch (e.g. 128 = one rank's "
                                                           "shard at 8 GPUs, measured on one GPU)")
+    ap.add_argument("--dump-outputs", metavar="DIR", default=None,
+                    help="after the timed steps, write what the headline's last timed step computed as "
+                         "DIR/<name>.npy (float64; rank 0)")
+    ap.add_argument("--full", action="store_true",
+                    help="also the CPU baselines, the instrumented (per-phase, roofline) pass, the C4 'batched' / "
+                         "'batched_shard' and the C2 / C5 'configs' sub-objects (each has its --no-* switch); "
+                         "a plain run times the headline only")
     args = ap.parse_args()
+    if not args.full:
+        args.no_cpu_baseline = args.no_batched = args.no_configs = args.no_instrumented = True
 
     # the CPU baselines first (rank 0, one GPU): a child process on the host
     # cores while the GPU is idle, so the GPU legs below run back to back
@@ -377,7 +436,7 @@ def main():
         nbatch = args.batch
 
     if nbatch:  # C4 as the headline
-        head = run_batched(I, ctx, args, world, rank, dist, torch, wl, nbatch)
+        head = run_batched(I, ctx, args, world, rank, dist, torch, wl, nbatch, dump=args.dump_outputs)
         out = dict(head)
         if world == 1 and nbatch != 128 and not args.no_batched:
             out["batched_shard"] = shard_line(I, ctx, args, dist, torch)
@@ -386,7 +445,7 @@ def main():
         out["config"]["description"] = wl["desc"]
         out["config"]["formulation"] = "SlackedSlacks ineq, augmented LDL^T"
     else:
-        out = run_single(I, ctx, args, world, dist, torch, args.workload)
+        out = run_single(I, ctx, args, world, dist, torch, args.workload, dump=args.dump_outputs)
         if not args.no_batched:
             out["batched"] = run_batched(I, ctx, args, world, rank, dist, torch, WORKLOADS["c4"], 1024)
             if world == 1:

@@ -5,7 +5,7 @@ for i in 1 2 3; do
   for w in old new; do
     d=.; [ $w = old ] && d=_old
     for b in 1024 128; do
-      (cd $d && timeout -k 10 120 python bench.py --workload c4 --batch $b --no-cpu-baseline --steps 20) > $O/${w}_b${b}_$i.json 2>$O/${w}_b${b}_$i.err || exit 1
+      (cd $d && timeout -k 10 120 python bench.py --full --workload c4 --batch $b --no-cpu-baseline --steps 20) > $O/${w}_b${b}_$i.json 2>$O/${w}_b${b}_$i.err || exit 1
     done
   done
 done

@@ -20,14 +20,14 @@ for s in ${STEPS:-smoke tests bench prof}; do
   case $s in
     smoke) step smoke 300 python -c "import __graft_entry__ as g; g.smoke()" ;;
     tests) step tests 1000 python -u -m pytest tests -m gpu -v --timeout=400 --timeout-method thread -p no:cacheprovider ;;
-    bench) step bench 600 python bench.py ${BENCH_ARGS:-} ;;
-    bench_c2) step bench_c2 300 python bench.py --workload c2 ;;
-    bench_c4) step bench_c4 300 python bench.py --workload c4 ;;
-    bench_c5) step bench_c5 300 python bench.py --workload c5 ;;
-    prof)  step prof 600 rocprofv3 --kernel-trace --stats -d "$OUT/prof" -o run --output-format csv -- python bench.py --steps 5 --warmup 1 --no-cpu-baseline ;;
+    bench) step bench 600 python bench.py --full ${BENCH_ARGS:-} ;;
+    bench_c2) step bench_c2 300 python bench.py --full --workload c2 ;;
+    bench_c4) step bench_c4 300 python bench.py --full --workload c4 ;;
+    bench_c5) step bench_c5 300 python bench.py --full --workload c5 ;;
+    prof)  step prof 600 rocprofv3 --kernel-trace --stats -d "$OUT/prof" -o run --output-format csv -- python bench.py --full --steps 5 --warmup 1 --no-cpu-baseline ;;
     # HBM traffic: one counter group per pass (MI355X_MICROARCH.md, rocprofv3 PMC slots)
-    pmc_fetch) step pmc_fetch 240 rocprofv3 --pmc FETCH_SIZE -d "$OUT/pmc_fetch" -o run --output-format csv -- python bench.py --steps 1 --warmup 0 --no-cpu-baseline ;;
-    pmc_write) step pmc_write 240 rocprofv3 --pmc WRITE_SIZE -d "$OUT/pmc_write" -o run --output-format csv -- python bench.py --steps 1 --warmup 0 --no-cpu-baseline ;;
+    pmc_fetch) step pmc_fetch 240 rocprofv3 --pmc FETCH_SIZE -d "$OUT/pmc_fetch" -o run --output-format csv -- python bench.py --full --steps 1 --warmup 0 --no-cpu-baseline ;;
+    pmc_write) step pmc_write 240 rocprofv3 --pmc WRITE_SIZE -d "$OUT/pmc_write" -o run --output-format csv -- python bench.py --full --steps 1 --warmup 0 --no-cpu-baseline ;;
     # factor-phase counters of ONE bench step (tools/pmc_factor.py), one counter group per pass
     pmcf_fetch) step ${PMCW:-c3}_pmcf_fetch 240 rocprofv3 --pmc FETCH_SIZE -d "$OUT/${PMCW:-c3}_pmcf_fetch" -o run --output-format csv -- python bench.py --workload ${PMCW:-c3} --steps 1 --warmup 0 --no-cpu-baseline --no-instrumented --no-batched --no-configs ;;
     pmcf_write) step ${PMCW:-c3}_pmcf_write 240 rocprofv3 --pmc WRITE_SIZE -d "$OUT/${PMCW:-c3}_pmcf_write" -o run --output-format csv -- python bench.py --workload ${PMCW:-c3} --steps 1 --warmup 0 --no-cpu-baseline --no-instrumented --no-batched --no-configs ;;
@@ -49,7 +49,7 @@ for s in ${STEPS:-smoke tests bench prof}; do
     mixedtests) step mixedtests 400 python -u -m pytest tests/test_gpu_mixed.py tests/test_gpu_step_paths.py tests/test_gpu_graph.py -v --timeout 240 --timeout-method thread -p no:cacheprovider ;;
     newtests) step newtests 600 python -u -m pytest tests/test_gpu_headline.py tests/test_gpu_c4_batch.py -v --timeout 400 --timeout-method thread -p no:cacheprovider ;;
     kfactor) step kfactor 300 ipm-zoo_amd/build/kbench 11264 factor 384 256 512 ;;
-    trace) step trace 300 rocprofv3 --kernel-trace -d "$OUT/trace" -o run --output-format csv -- python bench.py --steps 3 --warmup 1 --no-cpu-baseline --no-batched --no-instrumented ;;
+    trace) step trace 300 rocprofv3 --kernel-trace -d "$OUT/trace" -o run --output-format csv -- python bench.py --full --steps 3 --warmup 1 --no-cpu-baseline --no-batched --no-instrumented ;;
     c2trace) step c2trace 300 rocprofv3 --kernel-trace -d "$OUT/c2trace" -o run --output-format csv -- python bench.py --workload c2 --steps 3 --warmup 1 --no-cpu-baseline --no-batched --no-instrumented --no-configs ;;
     c2hip) step c2hip 300 rocprofv3 --hip-trace --kernel-trace -d "$OUT/c2hip" -o run --output-format csv -- python bench.py --workload c2 --steps 3 --warmup 1 --no-cpu-baseline --no-batched --no-instrumented --no-configs ;;
     counters) step counters 120 rocprofv3 -L ;;

@@ -1,6 +1,6 @@
 #!/usr/bin/env python3
 """HBM traffic per launch of the trailing-update GEMM from two rocprofv3
---pmc passes (FETCH_SIZE, WRITE_SIZE) of `bench.py --steps 1 --warmup 0`.
+--pmc passes (FETCH_SIZE, WRITE_SIZE) of `bench.py --full --steps 1 --warmup 0`.
 
 Corrections (MI355X_MICROARCH.md, HBM): FETCH_SIZE/WRITE_SIZE are KiB;
 on gfx950 FETCH_SIZE reports half the bytes of a 16-B/lane streaming read,
