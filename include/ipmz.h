@@ -12,6 +12,11 @@
  *   ipmz_overwriting_solve_ldlt <- LinearSolvers::overwriting_solve_ldlt
  *                                  (LinearSolvers.h:16-17, LinearSolvers.cpp:44-74)
  *   ipmz_ldlt_factor / _solve   <- the same pair on device-resident K (no copies)
+ *   ipmz_ldlt_solve_multi, ipmz_overwriting_solve_ldlt_multi, ipmz_qp_kkt_solve
+ *                               <- no reference counterpart (the reference solves one
+ *                                  vector at a time): overwriting_solve_ldlt for a block
+ *                                  of right-hand sides, one per row, as a blocked
+ *                                  triangular solve that reads L once per sweep
  *   ipmz_qp_create + ipmz_qp_load_host
  *                               <- NumericalOptimization::build_environment
  *                                  (EnvironmentBuilder.h:19-20, EnvironmentBuilder.cpp:7-76)
@@ -138,6 +143,20 @@ int ipmz_ldlt_factor(ipmz_ctx* ctx, int N, double* K, int64_t ld, double* D, voi
 int ipmz_ldlt_solve(ipmz_ctx* ctx, int N, const double* K, int64_t ld, const double* D, const void* ws, double* b);
 /* Rebuild the solve workspace from an explicit unit-lower L (device). */
 int ipmz_ldlt_prepare_solve(ipmz_ctx* ctx, int N, const double* L, int64_t ld, void* ws, int64_t ws_bytes);
+/* B (device): nrhs rows of length N, row r = right-hand side r, stride ldb >= N (even).
+ * Every row <- K^{-1} row with the factor left by ipmz_ldlt_factor /
+ * ipmz_ldlt_prepare_solve; asynchronous, in place, no allocation.  K's ld must
+ * be even too, K (N rows of ld elements) and B 16-byte aligned; B[r][N .. ldb)
+ * is never written.
+ * nrhs == 1 is ipmz_ldlt_solve (bitwise); from a crossover nrhs on the rows
+ * are solved together, blocked over column panels of IPMZ_SOLVE_MULTI_PANEL
+ * columns on fp64 MFMA (L read once per sweep; stream-ordered launches, no
+ * cross-workgroup waiting, deterministic), below it one after the other.
+ * ws as for ipmz_ldlt_solve.  Out of scope: multi-right-hand-side forms of
+ * ipmz_mixed_solve, ipmz_normal_solve and ipmz_bk_solve. */
+#define IPMZ_SOLVE_MULTI_PANEL 256
+int ipmz_ldlt_solve_multi(ipmz_ctx* ctx, int N, const double* K, int64_t ld, const double* D, const void* ws,
+                          double* B, int64_t ldb, int nrhs);
 
 /* ---- mixed precision (config C5): fp32 factor + fp64 refinement -----------
  * No reference counterpart (the reference is fp64 throughout,
@@ -204,6 +223,9 @@ int ipmz_ldlt_decomposition(ipmz_ctx* ctx, int N, const double* A, double* L, do
 /* L: host N x N unit lower; D: host N; b: host N, overwritten with the
  * solution.  N == 0 is a no-op (LinearSolvers.cpp:46-48). */
 int ipmz_overwriting_solve_ldlt(ipmz_ctx* ctx, int N, const double* L, const double* D, double* b);
+/* The same for nrhs right-hand sides: B host, nrhs x N row-major, every row
+ * overwritten with its solution.  N == 0 or nrhs == 0 is a no-op. */
+int ipmz_overwriting_solve_ldlt_multi(ipmz_ctx* ctx, int N, const double* L, const double* D, double* B, int nrhs);
 
 /* ---- the Newton-step solver --------------------------------------------- */
 /* Settings::EqualityHandling (SymbolicOptimization.h:28-64) */
@@ -312,6 +334,17 @@ int ipmz_qp_set_state(ipmz_qp* qp, const double* host_vars);
  * (lower triangle written, upper zero).  For parity tests. */
 int ipmz_qp_get_kkt(ipmz_qp* qp, double* host_K);
 int ipmz_qp_kkt_dim(ipmz_qp* qp);
+/* Solve with the KKT matrix of the QP's current iterate: assembles it (the
+ * matrix ipmz_qp_get_kkt returns, order ipmz_qp_kkt_dim), factors it and
+ * solves the nrhs rows of B (device, Newton order, stride ldb >= N, even) as
+ * ipmz_ldlt_solve_multi does.  Returns the factor's info like
+ * ipmz_ldlt_factor (synchronizes).  Leaves the iterate and all later steps
+ * unchanged.  For single QPs whose step factors the augmented system with
+ * fp64 LDL^T: IPMZ_ERR_INVALID for batches, IPMZ_EQ_NONE (Bunch-Kaufman), an
+ * enabled normal-equations reduction or mixed-precision mode.  The Newton
+ * step itself is untouched: its two solves depend on each other and stay
+ * single-vector. */
+int ipmz_qp_kkt_solve(ipmz_qp* qp, int nrhs, double* B, int64_t ldb);
 /* Newton directions through the mixed-precision solve (fp32 factor of the
  * scaled KKT matrix + fp64 refinement to tol, at most max_refine corrections
  * per solve); enable = 0 returns to the fp64 factor.  Single QPs only.  The

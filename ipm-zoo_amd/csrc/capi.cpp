@@ -441,6 +441,44 @@ int ipmz_ldlt_prepare_solve(ipmz_ctx* ctx, int N, const double* L, int64_t ld, v
   return IPMZ_OK;
 }
 
+// Multi-right-hand-side solve (trsm.hip).  Panel width of the blocked path
+// (IPMZ_SOLVE_MULTI_PANEL) and the number of right-hand sides from which it
+// runs; below it the rows go through the single-vector solve one by one.
+// Both from tools/solve_multi_bench.py (profiles/solve_multi/bench.json,
+// DESIGN.md "Multi-right-hand-side solve"): 256 columns beat 128 and 512 at
+// every measured point; the blocked path breaks even with the loop at 6.6
+// rows (N = 11264) and 8.5 rows (N = 2560).
+static constexpr int SOLVE_MULTI_PANEL = IPMZ_SOLVE_MULTI_PANEL;
+static constexpr int SOLVE_MULTI_CROSSOVER = 10;
+static_assert(SOLVE_MULTI_PANEL % 128 == 0 && SOLVE_MULTI_PANEL <= IPMZ_TRSM_PANEL_MAX, "panel width");
+
+int ipmz_ldlt_solve_multi(ipmz_ctx* ctx, int N, const double* K, int64_t ld, const double* D, const void* ws,
+                          double* B, int64_t ldb, int nrhs) {
+  if (!ctx || N < 0 || nrhs < 0 || ld < N || ldb < N || (ld & 1) || (ldb & 1))
+    return fail(IPMZ_ERR_INVALID, "ipmz_ldlt_solve_multi: bad arguments (nrhs >= 0, ld >= N, ldb >= N, both even)");
+  if (N == 0 || nrhs == 0) return IPMZ_OK;
+  if (!K || !D || !ws || !B) return fail(IPMZ_ERR_INVALID, "ipmz_ldlt_solve_multi: null pointer");
+  if (nrhs == 1) return ipmz_ldlt_solve(ctx, N, K, ld, D, ws, B);
+  if (((uintptr_t)K & 15) || ((uintptr_t)B & 15))
+    return fail(IPMZ_ERR_INVALID, "ipmz_ldlt_solve_multi: K and B must be 16-byte aligned");
+  HIP_OK(hipSetDevice(ctx->device));
+  const int nbo = nbo_for(ctx, N);
+  const WsLayout l = ws_layout(N, nbo, ctx->nbi);
+  const int dbg = debug_inject_mask();
+  if (nrhs < SOLVE_MULTI_CROSSOVER && !(dbg & IPMZ_DEBUG_MULTI_BLOCKED)) {
+    for (int r = 0; r < nrhs; ++r)
+      HIP_OK(solve_ws(K, ld, N, D, static_cast<const char*>(ws), nbo, ctx->nbi, B + (int64_t)r * ldb, ctx->stream));
+  } else {
+    const int w = (dbg & IPMZ_DEBUG_MULTI_W512) ? 512 : (dbg & IPMZ_DEBUG_MULTI_W128) ? 128 : SOLVE_MULTI_PANEL;
+    HIP_OK(ldlt_solve_multi(K, ld, N, D, reinterpret_cast<const double*>(static_cast<const char*>(ws) + l.linv_off),
+                            ctx->nbi, B, ldb, nrhs, w, ctx->stream));
+  }
+  // as ipmz_ldlt_solve: the workspace's error words are checked by ipmz_ctx_sync
+  ctx->check_pe = panel_err_word(static_cast<const char*>(ws), l);
+  ctx->check_se = solve_err_word(static_cast<const char*>(ws), l);
+  return IPMZ_OK;
+}
+
 // Mixed precision (config C5) -------------------------------------------------
 }  // extern "C"
 
@@ -753,6 +791,40 @@ int ipmz_overwriting_solve_ldlt(ipmz_ctx* ctx, int N, const double* L, const dou
   hipFree(dL);
   hipFree(dD);
   hipFree(db);
+  hipFree(ws);
+  return rc;
+}
+
+int ipmz_overwriting_solve_ldlt_multi(ipmz_ctx* ctx, int N, const double* L, const double* D, double* B, int nrhs) {
+  if (!ctx || N < 0 || nrhs < 0) return fail(IPMZ_ERR_INVALID, "ipmz_overwriting_solve_ldlt_multi: bad arguments");
+  if (N == 0 || nrhs == 0) return IPMZ_OK;
+  if (!L || !D || !B) return fail(IPMZ_ERR_INVALID, "null pointer");
+  HIP_OK(hipSetDevice(ctx->device));
+  const int64_t ld = round_up(N, 64), ldb = round_up(N, 2);
+  const int64_t wsb = ws_layout(N, nbo_for(ctx, N), ctx->nbi).total;
+  double *dL = nullptr, *dD = nullptr, *dB = nullptr;
+  char* ws = nullptr;
+  bool ok = hipMalloc(&dL, (size_t)(ld * N * 8)) == hipSuccess && hipMalloc(&dD, (size_t)N * 8) == hipSuccess &&
+            hipMalloc(&dB, (size_t)(ldb * nrhs * 8)) == hipSuccess && hipMalloc(&ws, (size_t)wsb) == hipSuccess;
+  int rc = ok ? IPMZ_OK : fail(IPMZ_ERR_NOMEM, "device allocation failed");
+  if (!rc && (hipMemcpy2DAsync(dL, ld * 8, L, (size_t)N * 8, (size_t)N * 8, N, hipMemcpyHostToDevice, ctx->stream) !=
+                  hipSuccess ||
+              hipMemcpyAsync(dD, D, (size_t)N * 8, hipMemcpyHostToDevice, ctx->stream) != hipSuccess ||
+              hipMemcpy2DAsync(dB, ldb * 8, B, (size_t)N * 8, (size_t)N * 8, nrhs, hipMemcpyHostToDevice,
+                               ctx->stream) != hipSuccess))
+    rc = fail(IPMZ_ERR_HIP, "copy-in failed");
+  if (!rc) rc = ipmz_ldlt_prepare_solve(ctx, N, dL, ld, ws, wsb);
+  if (!rc) rc = ipmz_ldlt_solve_multi(ctx, N, dL, ld, dD, ws, dB, ldb, nrhs);
+  // ws is freed below: check the solve's error words now, not at a later sync
+  ctx->check_pe = ctx->check_se = nullptr;
+  if (!rc) rc = ws_status(ctx->stream, ws, N, nbo_for(ctx, N), ctx->nbi, "ipmz_overwriting_solve_ldlt_multi");
+  if (!rc && (hipMemcpy2DAsync(B, (size_t)N * 8, dB, ldb * 8, (size_t)N * 8, nrhs, hipMemcpyDeviceToHost,
+                               ctx->stream) != hipSuccess ||
+              hipStreamSynchronize(ctx->stream) != hipSuccess))
+    rc = fail(IPMZ_ERR_HIP, "copy-out failed");
+  hipFree(dL);
+  hipFree(dD);
+  hipFree(dB);
   hipFree(ws);
   return rc;
 }
@@ -1679,6 +1751,30 @@ int ipmz_qp_get_kkt(ipmz_qp* s, double* out) {
   for (int i = 0; i < s->N; ++i)
     for (int j = i + 1; j < s->N; ++j) out[(int64_t)i * s->N + j] = 0.0;
   return IPMZ_OK;
+}
+
+int ipmz_qp_kkt_solve(ipmz_qp* s, int nrhs, double* B, int64_t ldb) {
+  if (!s) return fail(IPMZ_ERR_INVALID, "null qp");
+  if (s->B != 1) return fail(IPMZ_ERR_INVALID, "ipmz_qp_kkt_solve: single QPs only, this is a batch");
+  if (s->eqnone)
+    return fail(IPMZ_ERR_INVALID, "ipmz_qp_kkt_solve: EqualityHandling::None factors with Bunch-Kaufman, which has "
+                                  "no multi-right-hand-side solve");
+  if (s->normal)
+    return fail(IPMZ_ERR_INVALID, "ipmz_qp_kkt_solve: the normal-equations reduction is enabled (augmented LDL^T only)");
+  if (s->mixed)
+    return fail(IPMZ_ERR_INVALID, "ipmz_qp_kkt_solve: mixed precision is enabled (fp64 LDL^T only)");
+  if (!s->loaded) return fail(IPMZ_ERR_STATE, "load or generate the QP first");
+  if (nrhs < 0 || ldb < s->N || (ldb & 1) || (nrhs > 0 && !B))
+    return fail(IPMZ_ERR_INVALID, "ipmz_qp_kkt_solve: bad arguments (nrhs >= 0, ldb >= N and even)");
+  HIP_OK(hipSetDevice(s->ctx->device));
+  // the step's own assembly and factor, on the storage the next step
+  // overwrites anyway (it assembles and factors again): the iterate is only read
+  HIP_OK(qp_assemble(s->qb, s->ctx->stream));
+  int rc = factor_impl(s->ctx, s->N, s->K, s->ldk, s->D, s->ws, nullptr);
+  if (!rc) rc = ipmz_ldlt_solve_multi(s->ctx, s->N, s->K, s->ldk, s->D, s->ws, B, ldb, nrhs);
+  s->ctx->check_pe = s->ctx->check_se = nullptr;  // s->ws is the solver's: checked here, not at a later sync
+  if (rc) return rc;
+  return read_info(s->ctx, s->ws, s->N);  // synchronizes; checks the error words of s->ws itself
 }
 
 int ipmz_qp_set_mixed_precision(ipmz_qp* s, int enable, double tol, int max_refine) {

@@ -37,12 +37,17 @@ namespace ipmz {
 // 4096 = the chain launch draws no ticket: the rows launch runs every chain role in its 4-wave form
 //        (what a serialized dispatch order can produce; the forms must factor bitwise alike),
 // 8192 = batches assemble the whole KKT into K every step (not the kept K0) (A/B),
-// 16384 = batches run the two solves and the phases between them as separate launches (A/B)
+// 16384 = batches run the two solves and the phases between them as separate launches (A/B),
+// 65536 = ipmz_ldlt_solve_multi runs its blocked path from 2 right-hand sides on (no looped single-vector
+//         solves below the crossover) (A/B, tools/solve_multi_bench.py),
+// 131072 / 262144 = ... with 512- / 128-column panels instead of IPMZ_SOLVE_MULTI_PANEL (A/B)
 enum { IPMZ_INJECT_SOLVE = 1, IPMZ_INJECT_PANEL = 2, IPMZ_INJECT_GRAPH_FORKS = 4, IPMZ_DEBUG_CONVERT_ONLY = 16,
        IPMZ_DEBUG_ONE_STREAM = 32, IPMZ_DEBUG_TRACE = 64, IPMZ_DEBUG_F32_ENGINE = 128,
        IPMZ_DEBUG_NO_FOURTH = 256, IPMZ_DEBUG_IR_FULL = 512,
        IPMZ_DEBUG_F64_ENGINE = 1024, IPMZ_DEBUG_GIVEBACK = 2048, IPMZ_DEBUG_ROWS_CHAIN = 4096,
-       IPMZ_DEBUG_NO_K0 = 8192, IPMZ_DEBUG_NO_FUSED_SOLVES = 16384, IPMZ_DEBUG_READY_LATE = 32768 };
+       IPMZ_DEBUG_NO_K0 = 8192, IPMZ_DEBUG_NO_FUSED_SOLVES = 16384, IPMZ_DEBUG_READY_LATE = 32768,
+       IPMZ_DEBUG_MULTI_BLOCKED = 65536, IPMZ_DEBUG_MULTI_W512 = 131072,
+       IPMZ_DEBUG_MULTI_W128 = 262144 };
 #define IPMZ_TRACE(...)                                                  \
   do {                                                                   \
     if (::ipmz::debug_inject_mask() & ::ipmz::IPMZ_DEBUG_TRACE) {        \
@@ -159,6 +164,15 @@ hipError_t gemm_nt_sub(int M, int N, int Kd, const double* A, int64_t lda, const
 // In-place b <- L^{-T} D^{-1} L^{-1} b; side: 2*nbi doubles of scratch.
 hipError_t ldlt_solve(const double* K, int64_t ld, int N, const double* D, const double* Linv, int nbi, double* b,
                       double* side, hipStream_t st);
+
+// trsm.hip: the same solve for nrhs right-hand sides at once.  B: nrhs rows of
+// length N (row r = right-hand side r, stride ldb >= N), solved in place;
+// blocked over column panels of width w (a multiple of 128, <=
+// IPMZ_TRSM_PANEL_MAX) on fp64 MFMA.  ld and ldb even, K and B 16-byte
+// aligned.  Stream-ordered launches only: no cross-workgroup waiting.
+#define IPMZ_TRSM_PANEL_MAX 512
+hipError_t ldlt_solve_multi(const double* K, int64_t ld, int N, const double* D, const double* Linv, int nbi,
+                            double* B, int64_t ldb, int nrhs, int w, hipStream_t st);
 
 // one workgroup per QP of a batch (small N); b: batch of rhs, stride sb
 hipError_t ldlt_solve_batched(const double* K, int64_t ld, int N, const double* D, const double* Linv, int nbi,

@@ -3,6 +3,7 @@
 //
 //   LinearSolvers::ldlt_decomposition      include/NumericalOptimization/LinearSolvers.h:11
 //   LinearSolvers::overwriting_solve_ldlt  LinearSolvers.h:16-17
+//   LinearSolvers::overwriting_solve_ldlt_multi  (the same, one right-hand side per row of a Matrix)
 //   Data, build_environment                EnvironmentBuilder.h:7-20
 //   Optimizer(...).solve()                 Optimizer.h:15-20
 //
@@ -82,6 +83,29 @@ inline void overwriting_solve_ldlt(const Matrix& L, const Vector& D, Vector& b, 
     for (size_t j = 0; j < n; ++j) flat[i * n + j] = L[i][j];
   }
   check(ipmz_overwriting_solve_ldlt(ctx.get(), (int)n, flat.data(), D.data(), b.data()), "ipmz_overwriting_solve_ldlt");
+}
+
+// The same for a block of right-hand sides: every row of B is one right-hand
+// side, overwritten with its solution (no reference counterpart: the
+// reference solves one vector at a time).  Empty B is a no-op.
+inline void overwriting_solve_ldlt_multi(const Matrix& L, const Vector& D, Matrix& B,
+                                         Context& ctx = Context::instance()) {
+  if (B.empty() || B[0].empty()) return;
+  const size_t nrhs = B.size(), n = B[0].size();
+  if (D.size() != n || L.size() != n) throw AssertionError("overwriting_solve_ldlt_multi: size mismatch");
+  std::vector<double> flat(n * n), rhs(nrhs * n);
+  for (size_t i = 0; i < n; ++i) {
+    if (L[i].size() != n) throw AssertionError("overwriting_solve_ldlt_multi: L is not square");
+    for (size_t j = 0; j < n; ++j) flat[i * n + j] = L[i][j];
+  }
+  for (size_t r = 0; r < nrhs; ++r) {
+    if (B[r].size() != n) throw AssertionError("overwriting_solve_ldlt_multi: rows of B differ in length");
+    for (size_t j = 0; j < n; ++j) rhs[r * n + j] = B[r][j];
+  }
+  check(ipmz_overwriting_solve_ldlt_multi(ctx.get(), (int)n, flat.data(), D.data(), rhs.data(), (int)nrhs),
+        "ipmz_overwriting_solve_ldlt_multi");
+  for (size_t r = 0; r < nrhs; ++r)
+    for (size_t j = 0; j < n; ++j) B[r][j] = rhs[r * n + j];
 }
 
 }  // namespace LinearSolvers

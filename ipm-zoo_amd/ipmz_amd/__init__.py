@@ -46,8 +46,9 @@ EXPORTS = [
     "ipmz_batch_copy_scalars", "ipmz_normal_workspace_bytes", "ipmz_normal_factor", "ipmz_normal_solve",
     "ipmz_qp_set_reduction", "ipmz_bk_factor", "ipmz_bk_factor_ex", "ipmz_bk_solve", "ipmz_symmetric_indefinite_factorization",
     "ipmz_overwriting_solve_bunch_kaufman", "ipmz_debug_inject", "ipmz_batch_summary", "ipmz_batch_set_factor_kernel",
-    "ipmz_qp_last_step_graph",
+    "ipmz_qp_last_step_graph", "ipmz_ldlt_solve_multi", "ipmz_overwriting_solve_ldlt_multi", "ipmz_qp_kkt_solve",
 ]
+SOLVE_MULTI_PANEL = 256  # include/ipmz.h IPMZ_SOLVE_MULTI_PANEL: column panel of the blocked multi-rhs solve
 REDUCTION_AUGMENTED, REDUCTION_NORMAL = 0, 1
 
 _P = ctypes.POINTER(ctypes.c_double)
@@ -151,6 +152,9 @@ def _load():
         "ipmz_batch_summary": ([_VP, _VP], _I),
         "ipmz_batch_set_factor_kernel": ([_VP, _I], _I),
         "ipmz_qp_last_step_graph": ([_VP], _I),
+        "ipmz_ldlt_solve_multi": ([_VP, _I, _VP, _I64, _VP, _VP, _VP, _I64, _I], _I),
+        "ipmz_overwriting_solve_ldlt_multi": ([_VP, _I, _P, _P, _P, _I], _I),
+        "ipmz_qp_kkt_solve": ([_VP, _I, _VP, _I64], _I),
     }
     for name, (args, res) in sig.items():
         fn = getattr(lib, name)
@@ -238,6 +242,11 @@ class Context:
         return _check(lib.ipmz_ldlt_solve(self.h, N, _VP(K_ptr), ld, _VP(D_ptr), _VP(ws_ptr), _VP(b_ptr)),
                       "ipmz_ldlt_solve")
 
+    def ldlt_solve_multi(self, N, K_ptr, ld, D_ptr, ws_ptr, B_ptr, ldb, nrhs):
+        """Every row of B (nrhs rows of length N, stride ldb, device) <- K^{-1} row, in place."""
+        return _check(lib.ipmz_ldlt_solve_multi(self.h, N, _VP(K_ptr), ld, _VP(D_ptr), _VP(ws_ptr), _VP(B_ptr), ldb,
+                                                nrhs), "ipmz_ldlt_solve_multi")
+
     # -- mixed precision (C5): fp32 factor of S K S + fp64 refinement --
     def mixed_workspace_bytes(self, N):
         return lib.ipmz_mixed_workspace_bytes(self.h, N)
@@ -323,6 +332,22 @@ class LinearSolvers:
         _check(lib.ipmz_overwriting_solve_ldlt((ctx or default_context()).h, N, _dp(L), _dp(D), _dp(b)),
                "ipmz_overwriting_solve_ldlt")
         return b
+
+    @staticmethod
+    def overwriting_solve_ldlt_multi(L, D, B, ctx=None):
+        """overwriting_solve_ldlt for a block of right-hand sides: B is a
+        C-contiguous float64 (nrhs, N) array, one right-hand side per row,
+        overwritten with the solutions and returned."""
+        L = np.ascontiguousarray(L, dtype=np.float64)
+        D = np.ascontiguousarray(D, dtype=np.float64)
+        if not (isinstance(B, np.ndarray) and B.dtype == np.float64 and B.ndim == 2 and B.flags.c_contiguous):
+            raise IpmzError("overwriting_solve_ldlt_multi: B must be a C-contiguous float64 (nrhs, N) array")
+        nrhs, N = B.shape
+        if D.shape != (N,) or L.shape != (N, N):
+            raise IpmzError("overwriting_solve_ldlt_multi: size mismatch")  # LinearSolvers.cpp:50-53
+        _check(lib.ipmz_overwriting_solve_ldlt_multi((ctx or default_context()).h, N, _dp(L), _dp(D), _dp(B), nrhs),
+               "ipmz_overwriting_solve_ldlt_multi")
+        return B
 
 
 def _ip(a):
@@ -477,6 +502,12 @@ class Optimizer:
         K = np.zeros((self.N, self.N))
         _check(lib.ipmz_qp_get_kkt(self.h, _dp(K)), "ipmz_qp_get_kkt")
         return K
+
+    def kkt_solve(self, B_ptr, nrhs, ldb):
+        """Every row of B (device, nrhs rows in Newton order, stride ldb) <-
+        K^{-1} row with the KKT matrix of the current iterate (kkt()); returns
+        the factor's info.  Single QPs on the fp64 augmented LDL^T only."""
+        return _check(lib.ipmz_qp_kkt_solve(self.h, nrhs, _VP(B_ptr), ldb), "ipmz_qp_kkt_solve")
 
     def set_timing(self, on=True):
         _check(lib.ipmz_qp_set_timing(self.h, 1 if on else 0), "ipmz_qp_set_timing")
