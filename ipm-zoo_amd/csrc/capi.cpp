@@ -222,7 +222,7 @@ int ipmz_ctx_get_blocking(ipmz_ctx* ctx, int N, int* nbo, int* nbi) {
 
 // ---------------------------------------------------------------------------
 // Workspace: [info int (256 B)] [panel ctrl words] [side 2*nbi] [Linv nblk*nbi^2] [W 3*N*nbo]
-//            [ybuf N] [zbuf N] [solve ctrl words] [solve prep (nbi 64): X, X^T, M, Q per 128-row block]
+//            [ybuf, zbuf: solve_vec_elems(N) each] [solve ctrl words] [solve prep (nbi 64): X, X^T, M, Q per 128-row block]
 namespace {
 struct WsLayout {
   int64_t info_off, pctrl_off, side_off, linv_off, w_off, y_off, z_off, ctrl_off, prep_off, total;
@@ -236,8 +236,8 @@ WsLayout ws_layout(int N, int nbo, int nbi) {
   l.linv_off = l.side_off + round_up(2 * nbi * 8, 256);
   l.w_off = l.linv_off + round_up(nblk * nbi * nbi * 8, 256);
   l.y_off = l.w_off + round_up(3 * (int64_t)N * nbo * 8, 256);  // W triple-buffered (look-ahead)
-  l.z_off = l.y_off + round_up((int64_t)N * 8, 256);
-  l.ctrl_off = l.z_off + round_up((int64_t)N * 8, 256);
+  l.z_off = l.y_off + round_up(solve_vec_elems(N) * 8, 256);
+  l.ctrl_off = l.z_off + round_up(solve_vec_elems(N) * 8, 256);
   l.prep_off = l.ctrl_off + 256;
   l.total = l.prep_off + (nbi == 64 ? round_up(solve_prep_elems(N) * 8, 256) : 0);
   return l;
@@ -304,8 +304,8 @@ BkWs bk_ws(char* base, int N) {
   };
   w.Linv = reinterpret_cast<double*>(take((int64_t)((N + 63) / 64) * 64 * 64 * 8));
   w.P = reinterpret_cast<double*>(take(solve_prep_elems(N) * 8));
-  w.y = reinterpret_cast<double*>(take((int64_t)N * 8));
-  w.x = reinterpret_cast<double*>(take((int64_t)N * 8));
+  w.y = reinterpret_cast<double*>(take(solve_vec_elems(N) * 8));
+  w.x = reinterpret_cast<double*>(take(solve_vec_elems(N) * 8));
   w.ctrl = reinterpret_cast<unsigned*>(take(256));
   w.meta = take((int64_t)bk_fast_meta_bytes(N));
   w.total = off;

@@ -40,14 +40,17 @@ namespace ipmz {
 // 16384 = batches run the two solves and the phases between them as separate launches (A/B),
 // 65536 = ipmz_ldlt_solve_multi runs its blocked path from 2 right-hand sides on (no looped single-vector
 //         solves below the crossover) (A/B, tools/solve_multi_bench.py),
-// 131072 / 262144 = ... with 512- / 128-column panels instead of IPMZ_SOLVE_MULTI_PANEL (A/B)
+// 131072 / 262144 = ... with 512- / 128-column panels instead of IPMZ_SOLVE_MULTI_PANEL (A/B),
+// 524288 / 1048576 = the persistent solve splits every 128-row block over 2 / 4 workgroups, whatever
+//         its table says; both bits = the unsplit solve (all three bitwise alike,
+//         tests/test_gpu_solve_split.py)
 enum { IPMZ_INJECT_SOLVE = 1, IPMZ_INJECT_PANEL = 2, IPMZ_INJECT_GRAPH_FORKS = 4, IPMZ_DEBUG_CONVERT_ONLY = 16,
        IPMZ_DEBUG_ONE_STREAM = 32, IPMZ_DEBUG_TRACE = 64, IPMZ_DEBUG_F32_ENGINE = 128,
        IPMZ_DEBUG_NO_FOURTH = 256, IPMZ_DEBUG_IR_FULL = 512,
        IPMZ_DEBUG_F64_ENGINE = 1024, IPMZ_DEBUG_GIVEBACK = 2048, IPMZ_DEBUG_ROWS_CHAIN = 4096,
        IPMZ_DEBUG_NO_K0 = 8192, IPMZ_DEBUG_NO_FUSED_SOLVES = 16384, IPMZ_DEBUG_READY_LATE = 32768,
        IPMZ_DEBUG_MULTI_BLOCKED = 65536, IPMZ_DEBUG_MULTI_W512 = 131072,
-       IPMZ_DEBUG_MULTI_W128 = 262144 };
+       IPMZ_DEBUG_MULTI_W128 = 262144, IPMZ_DEBUG_SOLVE_H2 = 524288, IPMZ_DEBUG_SOLVE_H4 = 1048576 };
 #define IPMZ_TRACE(...)                                                  \
   do {                                                                   \
     if (::ipmz::debug_inject_mask() & ::ipmz::IPMZ_DEBUG_TRACE) {        \
@@ -181,11 +184,14 @@ hipError_t ldlt_solve_batched(const double* K, int64_t ld, int N, const double* 
 // trsv_persist.hip: the same solve as ONE persistent launch on 128-row
 // blocks (nbi == 64 factors).  P: solve_prep_elems(N) elements written by
 // solve_prep from the factor's 64 x 64 inverses (once per factorization);
-// ybuf, xbuf: N elements; ctrl: IPMZ_SOLVE_CTRL_WORDS unsigned, all set up
-// by solve_reset once per factorization (ctrl[SOLVE_ERR_WORD] is sticky).
+// ybuf, xbuf: solve_vec_elems(N) elements each (the block vectors, then the
+// slices the parts of a split block exchange); ctrl: IPMZ_SOLVE_CTRL_WORDS
+// unsigned, all set up by solve_reset once per factorization
+// (ctrl[SOLVE_ERR_WORD] is sticky).
 int64_t solve_prep_elems(int N);
+int64_t solve_vec_elems(int N);
 // the persistent solve's state after a factorization: control words zero,
-// y / x buffers (N elements of size elem) all-ones sentinels; the solve
+// y / x buffers (solve_vec_elems(N) elements of size elem) all-ones sentinels; the solve
 // launches keep it so for the next solve.  Optionally in the same launch:
 // info / info2 words set to 0x7f7f7f7f ("no failed pivot") and nwords words
 // zeroed (a factor's panel ctrl words)

@@ -233,8 +233,8 @@ int64_t mixed_ws_carve(char* base, int N, int nbo, MixedWs& w) {
   w.D32 = reinterpret_cast<float*>(take((int64_t)N * 4));
   w.Linv32 = reinterpret_cast<float*>(take(nblk * 64 * 64 * 4));
   w.W32 = reinterpret_cast<float*>(take(3 * (int64_t)N * nbo * 4));
-  w.y32 = reinterpret_cast<float*>(take((int64_t)N * 4));
-  w.z32 = reinterpret_cast<float*>(take((int64_t)N * 4));
+  w.y32 = reinterpret_cast<float*>(take(solve_vec_elems(N) * 4));
+  w.z32 = reinterpret_cast<float*>(take(solve_vec_elems(N) * 4));
   w.r32 = reinterpret_cast<float*>(take((int64_t)N * 4));
   w.ctrl = reinterpret_cast<unsigned*>(take(IPMZ_SOLVE_CTRL_WORDS * 4));
   w.P32 = reinterpret_cast<float*>(take(solve_prep_elems(N) * 4));

@@ -20,6 +20,29 @@
 // sweep (nb-1..0) are two launches whose workgroups dequeue tickets from a
 // device counter; a ticket only waits on lower tickets, which belong to
 // running workgroups, so a grid cannot deadlock.
+//
+// Split blocks.  A block's work may be spread over H = 2 or 4 workgroups
+// ("parts", RW = 128 / H rows each), so that a hop moves 1/H of a tile
+// through each CU.  Forward part h streams rows h RW .. of the tiles L_JK, of
+// X_J and of M_J; X_J v needs the v slices of the parts below it (X_J is
+// lower triangular), which the parts publish in a sentinel-initialised
+// exchange buffer kept like the block vectors (sc1 stores, one aligned store
+// per element, one round of loads stages and proves).  Backward part h owns
+// columns h RW .. of block column J and rows h RW .. of X_J^T and Q_J, and
+// needs the u slices of the parts above it.  Tickets: forward ticket t is
+// (block t / H, part t % H), backward ticket t is (block nb-1 - t / H, part
+// H-1 - t % H) -- the part nobody in its block waits for comes last.  A ticket
+// then waits only for block vectors of earlier blocks and for slices of
+// earlier parts of its own block: all lower tickets, drawn by workgroups that
+// are running, whatever the dispatch order and however few workgroups are
+// resident.  A part of a ragged last block that owns no rows publishes
+// nothing and nobody waits for it.  The slices are polled in the same loop
+// as the previous block's vector (they arrive together), so the split adds
+// no round trip to the chain.  Every element is computed by the operations
+// of the unsplit kernel in the same order -- results are bitwise those of
+// H = 1.  The exchange buffers follow the discipline of the block vectors:
+// the forward launch resets the u slices, the backward launch the v slices.
+//
 // The bulk L_JK y_K products stream the off-diagonal tiles in order, in
 // pairs (512 threads x 2 x 32 elements = two 128 x 128 tiles in flight), a
 // pair consumed as soon as its two block vectors are complete.  Readiness
@@ -45,7 +68,8 @@ __device__ unsigned long long g_sstamp[2][256][6];
 namespace {
 constexpr int SB = IPMZ_SOLVE_BLOCK;  // rows per solve block
 constexpr int SNT = 512;              // threads per solve workgroup (8 waves, <= 256 VGPRs)
-// Register-blocked 128 x 128 tiles, 32 elements per thread:
+// Register-blocked 128 x 128 tiles, 32 elements per thread (unsplit, H = 1;
+// a part of a split block holds 4 / H rows resp. 4 / H columns of these):
 //   row phases (L_JK y_K, X_J v, M_J y): thread (rg = t / 16, cg = t % 16)
 //     holds rows 4 rg + k (k < 4), columns 2 cg + 32 j + e (j < 4, e < 2):
 //     the 16 lanes of a row group read 256 contiguous bytes per load;
@@ -241,7 +265,12 @@ __global__ __launch_bounds__(256) void solve_prep_kernel(const T* __restrict__ K
 }
 
 // ---------------------------------------------------------------------------
-template <typename T, bool BWD>
+// One sweep.  H = workgroups ("parts") per 128-row block, each owning RW =
+// 128 / H rows (forward) or columns (backward) of the block's tiles; H = 1 is
+// the unsplit form.  Every element goes through the same operations in the
+// same order for every H: a row's 16 lanes hold the same columns, a column's
+// 16 row groups the same 8 rows; only the rows (columns) per thread change.
+template <typename T, bool BWD, int H>
 __global__ __launch_bounds__(SNT) void trsv128_kernel(const T* __restrict__ K, int64_t ld, int N,
                                                       const T* __restrict__ D, const T* __restrict__ X,
                                                       const T* __restrict__ XT, const T* __restrict__ M,
@@ -249,37 +278,49 @@ __global__ __launch_bounds__(SNT) void trsv128_kernel(const T* __restrict__ K, i
                                                       unsigned* ctrl, int nb, const unsigned* __restrict__ skip,
                                                       int inject) {
   typedef typename Mfma<T>::vec2_t V2;
-  typedef T Tile[RP_ROWS * 8];  // 32 elements: [k][j][e] (row phases) / [k][j][e] (column phase, k < 8, j < 2)
-  if (skip && *skip) return;    // mixed-precision refinement already converged
-  __shared__ T vs[2][SB];       // staged block vectors (bulk), then the critical vector
-  __shared__ T red[SB / CP_ROWS][SB];
-  __shared__ T vec[SB], bj[SB];
-  // X_J (forward) / X_J^T (backward), staged at the start of the ticket so
-  // the row phase after the bulk reads LDS, not HBM (stride padded: the 4 row
-  // groups of a wave hit different banks)
-  __shared__ __attribute__((aligned(16))) T xs[SB * XS_LD];
+  constexpr int RW = SB / H;        // rows / columns a part owns
+  constexpr int RPR = RP_ROWS / H;  // row phases: rows per thread
+  constexpr int CPT = 4 / H;        // column phase: columns per thread
+  constexpr int TE = 8 * RPR;       // elements of a register tile (= CP_ROWS * CPT)
+  static_assert(H == 1 || H == 2 || H == 4, "parts per block");
+  typedef T Tile[TE];  // [k][j][e] (row phases, k < RPR) / [k][i] (column phase, k < 8, i < CPT)
+  if (skip && *skip) return;  // mixed-precision refinement already converged
+  __shared__ T vs[2][SB];     // staged block vectors (bulk), then the critical vector
+  __shared__ T red[SB / CP_ROWS][RW];
+  __shared__ T vec[SB], bj[RW];
+  // the part's rows of X_J (forward) / X_J^T (backward), staged at the start
+  // of the ticket so the row phase after the bulk reads LDS, not HBM (stride
+  // padded: the row groups of a wave hit different banks)
+  __shared__ __attribute__((aligned(16))) T xs[RW * XS_LD];
   __shared__ unsigned sh_ticket, sh_stop, sh_nr[2];
   unsigned* err = ctrl + SOLVE_ERR_WORD;
+  // the parts' exchange vectors (v slices forward, u slices backward) follow
+  // the block vectors in the same ranges
+  T* const vbuf = ybuf + (int64_t)nb * SB;
+  T* const ubuf = xbuf + (int64_t)nb * SB;
   const int tid = threadIdx.x;
   const int rg = tid / RP_LANES, cg = tid % RP_LANES;  // row phases
   if (tid == 0) sh_nr[0] = sh_nr[1] = 0u;
 
-  // uniform: stage block vectors kb0, kb0 + dir (nk <= 2 of them, cnt(kb)
-  // valid entries each) into vs, polled until all are complete (no sentinel
-  // left); false: gave up -- after SPIN_TICKS, or when another workgroup
-  // raised err (read every 32nd round, so a poll round is one load latency)
+  // uniform: stage up to two vectors (c0 entries at p0 into d0 by threads
+  // 0..127, c1 at p1 into d1 by threads 128..255; p1 may be null), polled
+  // until all are complete (no sentinel left); entries c .. f-1 of a
+  // destination are zeroed.  false: gave up -- after SPIN_TICKS, or when
+  // another workgroup raised err (read every 32nd round, so a poll round is
+  // one load latency)
   const unsigned long long t_start = __builtin_amdgcn_s_memrealtime();
-  auto stage = [&](const T* buf, int kb0, int nk, int dir) -> bool {
+  auto stage2 = [&](const T* p0, int c0, int f0, T* d0, const T* p1, int c1, int f1, T* d1) -> bool {
     for (unsigned it = 1;; ++it) {
-      lds_sync();  // earlier reads of vs / sh_nr / sh_stop are done
+      lds_sync();  // earlier reads of vs / vec / sh_nr / sh_stop are done
       const int bsel = tid / SB, e = tid % SB;
       if (tid == 0) sh_nr[(it + 1) & 1] = 0u;  // the next round's flag
-      if (bsel < nk) {
-        const int kb = kb0 + dir * bsel;
-        const int cnt = N - kb * SB < SB ? N - kb * SB : SB;
-        const T v = e < cnt ? ld_sc1(&buf[(int64_t)kb * SB + e]) : T(0);
+      const T* const p = bsel ? p1 : p0;
+      if (bsel < 2 && p) {
+        const int cnt = bsel ? c1 : c0, nfill = bsel ? f1 : f0;
+        T* const d = bsel ? d1 : d0;
+        const T v = e < cnt ? ld_sc1(&p[e]) : T(0);
         if (e < cnt && is_sentinel(v)) sh_nr[it & 1] = 1u;
-        vs[bsel][e] = v;
+        if (e < cnt || e < nfill) d[e] = v;
       }
       if (tid == 0)
         sh_stop = __builtin_amdgcn_s_memrealtime() - t_start > SPIN_TICKS || ((it & 31u) == 0u && ld_sc1(err) != 0u);
@@ -292,12 +333,19 @@ __global__ __launch_bounds__(SNT) void trsv128_kernel(const T* __restrict__ K, i
       __builtin_amdgcn_s_sleep(1);
     }
   };
-  // row phases: a 128 x 128 row-major tile (row stride SB) at p into t
-  // (one base address per thread, immediate offsets)
+  // block vectors kb0, kb0 + dir (nk <= 2 of them) of buf into vs
+  auto stage = [&](const T* buf, int kb0, int nk, int dir) -> bool {
+    const int kb1 = kb0 + dir;
+    const int n0 = N - kb0 * SB < SB ? N - kb0 * SB : SB;
+    const int n1 = N - kb1 * SB < SB ? N - kb1 * SB : SB;
+    return stage2(buf + (int64_t)kb0 * SB, n0, SB, vs[0], nk > 1 ? buf + (int64_t)kb1 * SB : nullptr, n1, SB, vs[1]);
+  };
+  // row phases: RW rows of a 128-column row-major tile (row stride SB) at p
+  // into t (one base address per thread, immediate offsets)
   auto load_rows = [&](Tile& t, const T* p) {
-    const T* q = p + RP_ROWS * rg * SB + 2 * cg;
+    const T* q = p + RPR * rg * SB + 2 * cg;
 #pragma unroll
-    for (int k = 0; k < RP_ROWS; ++k)
+    for (int k = 0; k < RPR; ++k)
 #pragma unroll
       for (int j = 0; j < 4; ++j) {
         const V2 v2 = *reinterpret_cast<const V2*>(q + k * SB + 32 * j);
@@ -307,13 +355,13 @@ __global__ __launch_bounds__(SNT) void trsv128_kernel(const T* __restrict__ K, i
   };
   auto put_xs = [&](const Tile& t) {
 #pragma unroll
-    for (int k = 0; k < RP_ROWS; ++k)
+    for (int k = 0; k < RPR; ++k)
 #pragma unroll
       for (int j = 0; j < 4; ++j)
-        *reinterpret_cast<V2*>(&xs[(RP_ROWS * rg + k) * XS_LD + 2 * cg + 32 * j]) = V2{t[8 * k + 2 * j], t[8 * k + 2 * j + 1]};
+        *reinterpret_cast<V2*>(&xs[(RPR * rg + k) * XS_LD + 2 * cg + 32 * j]) = V2{t[8 * k + 2 * j], t[8 * k + 2 * j + 1]};
   };
   // acc[k] += xs[row k, :] . v[columns of this thread]
-  auto dot_xs = [&](T (&acc)[RP_ROWS], const T* v) {
+  auto dot_xs = [&](T (&acc)[RPR], const T* v) {
     T vv[8];
 #pragma unroll
     for (int j = 0; j < 4; ++j) {
@@ -322,16 +370,16 @@ __global__ __launch_bounds__(SNT) void trsv128_kernel(const T* __restrict__ K, i
       vv[2 * j + 1] = v2.y;
     }
 #pragma unroll
-    for (int k = 0; k < RP_ROWS; ++k)
+    for (int k = 0; k < RPR; ++k)
 #pragma unroll
       for (int j = 0; j < 4; ++j) {
-        const V2 x2 = *reinterpret_cast<const V2*>(&xs[(RP_ROWS * rg + k) * XS_LD + 2 * cg + 32 * j]);
+        const V2 x2 = *reinterpret_cast<const V2*>(&xs[(RPR * rg + k) * XS_LD + 2 * cg + 32 * j]);
         acc[k] = fma(x2.x, vv[2 * j], acc[k]);
         acc[k] = fma(x2.y, vv[2 * j + 1], acc[k]);
       }
   };
   // acc[k] += t[k, :] . v[columns of this thread]
-  auto dot_rows = [&](T (&acc)[RP_ROWS], const Tile& t, const T* v) {
+  auto dot_rows = [&](T (&acc)[RPR], const Tile& t, const T* v) {
     T vv[8];
 #pragma unroll
     for (int j = 0; j < 4; ++j) {
@@ -340,7 +388,7 @@ __global__ __launch_bounds__(SNT) void trsv128_kernel(const T* __restrict__ K, i
       vv[2 * j + 1] = v2.y;
     }
 #pragma unroll
-    for (int k = 0; k < RP_ROWS; ++k)
+    for (int k = 0; k < RPR; ++k)
 #pragma unroll
       for (int i = 0; i < 8; ++i) acc[k] = fma(t[8 * k + i], vv[i], acc[k]);
   };
@@ -350,33 +398,47 @@ __global__ __launch_bounds__(SNT) void trsv128_kernel(const T* __restrict__ K, i
     if (tid == 0) sh_ticket = atomicAdd(&ctrl[BWD ? SC_TICKET_B : SC_TICKET], 1u);
     lds_sync();
     const int ticket = (int)sh_ticket;
-    if (ticket >= nb) return;
+    if (ticket >= nb * H) return;
     // the other sweep's ticket counter, for the next launch of that sweep
     // (the previous one has completed: stream order)
     if (ticket == 0 && tid == 0) st_sc1(&ctrl[BWD ? SC_TICKET : SC_TICKET_B], 0u);
 
     if constexpr (!BWD) {
       // ============================================================ forward
-      const int J = ticket, J0 = J * SB;
+      const int J = ticket / H, h = ticket % H, J0 = J * SB, r0 = h * RW;
       const int R = N - J0 < SB ? N - J0 : SB;
-      SSTAMP(J, 0);
-      if (tid < R) st_sc1(&xbuf[J0 + tid], sentinel<T>());  // for this solve's backward launch
-      // rows past N read row J0 (finite data): their sums are never used
-      const T* Lrow = K + (int64_t)J0 * ld;
+      const int Rh = R - r0 < RW ? R - r0 : RW;  // rows of this part
+      if (Rh <= 0) continue;                     // ragged last block: nothing to own, nobody waits for it
+#ifdef IPMZ_SOLVE_STAMPS
+      const bool stamp = h == H - 1 || Rh < RW || R == r0 + RW;  // the block's last part
+#define SSTAMPH(J, i) \
+  if (stamp) SSTAMP(J, i)
+#else
+#define SSTAMPH(J, i)
+#endif
+      SSTAMPH(J, 0);
+      if (tid < Rh) {  // for this solve's backward launch
+        st_sc1(&xbuf[J0 + r0 + tid], sentinel<T>());
+        if (H > 1) st_sc1(&ubuf[J0 + r0 + tid], sentinel<T>());
+      }
+      // rows past N read the part's first row (finite data): their sums are never used
+      const T* Lrow = K + (int64_t)(J0 + r0) * ld;
       const int64_t ldr = ld;
-      auto row_ok = [&](int k) { return RP_ROWS * rg + k < R; };
-      T acc[RP_ROWS] = {T(0), T(0), T(0), T(0)};
+      auto row_ok = [&](int k) { return RPR * rg + k < Rh; };
+      T acc[RPR];
+#pragma unroll
+      for (int k = 0; k < RPR; ++k) acc[k] = T(0);
       Tile ta, tb;  // the next two tiles in flight
-      // X_J and b_J -> LDS up front
-      load_rows(ta, X + (int64_t)J * SB * SB);
-      if (tid < SB) bj[tid] = tid < R ? b[J0 + tid] : T(0);
+      // the part's rows of X_J and b_J -> LDS up front
+      load_rows(ta, X + (int64_t)J * SB * SB + r0 * SB);
+      if (tid < RW) bj[tid] = tid < Rh ? b[J0 + r0 + tid] : T(0);
       put_xs(ta);
       auto load_tile = [&](Tile& t, int Kb) {
-#pragma unroll
-        for (int k = 0; k < RP_ROWS; ++k)
+    #pragma unroll
+        for (int k = 0; k < RPR; ++k)
 #pragma unroll
           for (int j = 0; j < 4; ++j) {
-            const int64_t row = row_ok(k) ? RP_ROWS * rg + k : 0;
+            const int64_t row = row_ok(k) ? RPR * rg + k : 0;
             const V2 v2 = *reinterpret_cast<const V2*>(Lrow + row * ldr + (int64_t)Kb * SB + 2 * cg + 32 * j);
             t[8 * k + 2 * j] = v2.x;
             t[8 * k + 2 * j + 1] = v2.y;
@@ -388,7 +450,7 @@ __global__ __launch_bounds__(SNT) void trsv128_kernel(const T* __restrict__ K, i
       // consumed -- two hops before the hand-off needs it (loaded after the
       // bulk, its reload sat on the chain: DESIGN.md §4, the solve)
       const int Kp = J - 2;  // pairs region [0, Kp)
-      const T* Mj = M + (int64_t)J * SB * SB;
+      const T* Mj = M + (int64_t)J * SB * SB + r0 * SB;
       if (Kp > 0) {
         load_tile(ta, 0);
         if (Kp > 1) load_tile(tb, 1);
@@ -412,71 +474,111 @@ __global__ __launch_bounds__(SNT) void trsv128_kernel(const T* __restrict__ K, i
         if (!stage(ybuf, J - 2, 1, 1)) return;
         dot_rows(acc, ta, vs[0]);
       }
-      SSTAMP(J, 1);
+      SSTAMPH(J, 1);
 #pragma unroll
-      for (int k = 0; k < RP_ROWS; ++k) acc[k] = lanes16_sum(acc[k]);
+      for (int k = 0; k < RPR; ++k) acc[k] = lanes16_sum(acc[k]);
       lds_sync();  // vec / vs reuse; xs, bj staged
+      // v = b_J - sum_{K<J-1} L_JK y_K: this part's slice, published for the
+      // parts above it (X_J is lower triangular: they need it, it needs
+      // theirs not); the slices above count as zero
       if (cg == 0) {
 #pragma unroll
-        for (int k = 0; k < RP_ROWS; ++k) {
-          const int rr = RP_ROWS * rg + k;
-          vec[rr] = bj[rr] - acc[k];  // v = b_J - sum_{K<J-1} L_JK y_K
+        for (int k = 0; k < RPR; ++k) {
+          const int rr = RPR * rg + k;
+          const T v = bj[rr] - acc[k];
+          vec[r0 + rr] = v;
+          if (H > 1 && h < H - 1 && rr < Rh) st_sc1(&vbuf[J0 + r0 + rr], v);
         }
       }
-      lds_sync();
-      T y[RP_ROWS] = {T(0), T(0), T(0), T(0)};
+      if (H > 1 && tid < SB && tid >= r0 + RW) vec[tid] = T(0);
+      // the slices below (complete parts: this one has rows) are polled
+      // together with y_{J-1}: the two arrive about together (block J-1
+      // publishes 0.2 us after it sees y_{J-2}, the siblings their slices
+      // after the same y_{J-2}), and one poll loop for both is one global
+      // round trip less on the chain than one after the other
+      const bool both = H > 1 && h > 0 && J > 0;
+      if (H > 1 && h > 0) {
+        SSTAMPH(J, 2);
+        if (!stage2(vbuf + J0, r0, 0, vec, both ? ybuf + (int64_t)(J - 1) * SB : nullptr, SB, SB, vs[0])) return;
+        SSTAMPH(J, 5);
+      } else {
+        lds_sync();
+      }
+      T y[RPR];
+#pragma unroll
+      for (int k = 0; k < RPR; ++k) y[k] = T(0);
       dot_xs(y, vec);  // X_J v
       if (J > 0) {     // the hand-off: y_J = X_J v - M_J y_{J-1}
-        SSTAMP(J, 2);
-        if (!stage(ybuf, J - 1, 1, 1)) return;
-        SSTAMP(J, 4);
-        T d[RP_ROWS] = {T(0), T(0), T(0), T(0)};
+        if (!both) {
+          SSTAMPH(J, 2);
+          if (!stage(ybuf, J - 1, 1, 1)) return;
+        }
+        SSTAMPH(J, 4);
+        T d[RPR];
+#pragma unroll
+        for (int k = 0; k < RPR; ++k) d[k] = T(0);
         dot_rows(d, tb, vs[0]);
 #pragma unroll
-        for (int k = 0; k < RP_ROWS; ++k) y[k] -= d[k];
+        for (int k = 0; k < RPR; ++k) y[k] -= d[k];
       }
-      // inject (tests only): block 0 never publishes -> every consumer times out
+      // inject (tests only): no part of block 0 publishes -> every consumer times out
 #pragma unroll
-      for (int k = 0; k < RP_ROWS; ++k) {
+      for (int k = 0; k < RPR; ++k) {
         const T yk = lanes16_sum(y[k]);
-        const int rr = RP_ROWS * rg + k;
-        if (cg == 0 && rr < R && !(inject && J == 0)) st_sc1(&ybuf[J0 + rr], yk);
+        const int rr = RPR * rg + k;
+        if (cg == 0 && rr < Rh && !(inject && J == 0)) st_sc1(&ybuf[J0 + r0 + rr], yk);
       }
-      SSTAMP(J, 3);
+      SSTAMPH(J, 3);
+#undef SSTAMPH
     } else {
       // =========================================================== backward
-      const int J = nb - 1 - ticket, J0 = J * SB;
+      // the part with the highest columns draws the lowest ticket: X_J^T is
+      // upper triangular, so a part needs the u slices of the parts above it
+      const int J = nb - 1 - ticket / H, h = H - 1 - ticket % H, J0 = J * SB, c0 = h * RW;
       const int R = N - J0 < SB ? N - J0 : SB;
+      const int Rh = R - c0 < RW ? R - c0 : RW;  // columns (= rows of x_J) of this part
+      if (Rh <= 0) continue;                     // ragged last block: nothing to own, nobody waits for it
       const bool last = J + 1 >= nb;
       // bulk: column phase; columns past the block's R give sums that are
       // never used; rows past N (ragged last block) are not read and meet
       // zero vector entries
       const int crg = tid / CP_LANES, ccg = tid % CP_LANES;
+      auto col = [&](int i) { return CPT == 4 ? 2 * ccg + 64 * (i >> 1) + (i & 1) : CPT == 2 ? 2 * ccg + i : ccg; };
       const bool ragged = N % SB != 0;
-      T acc[4] = {T(0), T(0), T(0), T(0)};  // columns 2 ccg + 64 j + e
+      T acc[CPT];  // columns col(i) of the part
+#pragma unroll
+      for (int i = 0; i < CPT; ++i) acc[i] = T(0);
       Tile ta, tb;
-      // X_J^T and z_J = y_J / D_J -> LDS up front (y_J from the forward
-      // launch: complete)
-      load_rows(ta, XT + (int64_t)J * SB * SB);
-      if (tid < SB) bj[tid] = tid < R ? ybuf[J0 + tid] / D[J0 + tid] : T(0);
-      if (tid < R) st_sc1(&ybuf[J0 + tid], sentinel<T>());  // only this block reads y_J: reset for the next solve
+      // the part's rows of X_J^T and of z_J = y_J / D_J -> LDS up front (y_J
+      // from the forward launch: complete)
+      load_rows(ta, XT + (int64_t)J * SB * SB + c0 * SB);
+      if (tid < RW) bj[tid] = tid < Rh ? ybuf[J0 + c0 + tid] / D[J0 + c0 + tid] : T(0);
+      if (tid < Rh) {  // only this part reads its y_J rows: reset for the next solve
+        st_sc1(&ybuf[J0 + c0 + tid], sentinel<T>());
+        if (H > 1) st_sc1(&vbuf[J0 + c0 + tid], sentinel<T>());
+      }
       put_xs(ta);
       auto load_tile = [&](Tile& t, int Kb) {
-        const int R0 = Kb * SB + CP_ROWS * crg;
-        const T* p = K + (int64_t)R0 * ld + J0 + 2 * ccg;
+            const int R0 = Kb * SB + CP_ROWS * crg;
+        const T* p = K + (int64_t)R0 * ld + J0 + c0 + (CPT > 1 ? 2 * ccg : ccg);
         const bool rag = ragged && Kb == nb - 1;
 #pragma unroll
-        for (int k = 0; k < CP_ROWS; ++k)
+        for (int k = 0; k < CP_ROWS; ++k) {
+          const bool in = !rag || R0 + k < N;
+          if constexpr (CPT > 1) {
 #pragma unroll
-          for (int j = 0; j < 2; ++j) {
-            const bool in = !rag || R0 + k < N;
-            const V2 v2 = in ? *reinterpret_cast<const V2*>(p + (int64_t)k * ld + 64 * j) : V2{T(0), T(0)};
-            t[4 * k + 2 * j] = v2.x;
-            t[4 * k + 2 * j + 1] = v2.y;
+            for (int j = 0; j < CPT / 2; ++j) {
+              const V2 v2 = in ? *reinterpret_cast<const V2*>(p + (int64_t)k * ld + 64 * j) : V2{T(0), T(0)};
+              t[CPT * k + 2 * j] = v2.x;
+              t[CPT * k + 2 * j + 1] = v2.y;
+            }
+          } else {
+            t[k] = in ? p[(int64_t)k * ld] : T(0);
           }
+        }
       };
       auto dot_cols = [&](const Tile& t, const T* v) {
-        T xv[CP_ROWS];
+            T xv[CP_ROWS];
 #pragma unroll
         for (int k = 0; k < CP_ROWS; k += 2) {
           const V2 v2 = *reinterpret_cast<const V2*>(v + CP_ROWS * crg + k);
@@ -486,14 +588,14 @@ __global__ __launch_bounds__(SNT) void trsv128_kernel(const T* __restrict__ K, i
 #pragma unroll
         for (int k = 0; k < CP_ROWS; ++k)
 #pragma unroll
-          for (int i = 0; i < 4; ++i) acc[i] = fma(t[4 * k + i], xv[k], acc[i]);
+          for (int i = 0; i < CPT; ++i) acc[i] = fma(t[CPT * k + i], xv[k], acc[i]);
       };
       // bulk: K > J+1 from the bottom.  Tiles K > J+2 in pairs as their
       // vectors complete; the last one, block J+2, alone, so that Q_J is
       // loaded into the other register tile as soon as x_{J+3} has been
       // consumed (the forward sweep's M_J schedule, mirrored)
       const int Klo = J + 3;  // pairs region [Klo, nb)
-      const T* Qj = Q + (int64_t)J * SB * SB;
+      const T* Qj = Q + (int64_t)J * SB * SB + c0 * SB;
       if (nb - 1 >= Klo) {
         load_tile(ta, nb - 1);
         if (nb - 2 >= Klo) load_tile(tb, nb - 2);
@@ -519,34 +621,51 @@ __global__ __launch_bounds__(SNT) void trsv128_kernel(const T* __restrict__ K, i
       }
       lds_sync();
 #pragma unroll
-      for (int j = 0; j < 2; ++j) {
-        red[crg][2 * ccg + 64 * j] = acc[2 * j];
-        red[crg][2 * ccg + 64 * j + 1] = acc[2 * j + 1];
-      }
+      for (int i = 0; i < CPT; ++i) red[crg][col(i)] = acc[i];
       lds_sync();
-      if (tid < SB) {
+      // u = z_J - sum L_KJ^T x_K (zero past R): this part's slice, published
+      // for the parts below it; the slices below count as zero
+      if (tid < RW) {
         T t = T(0);
 #pragma unroll
         for (int k = 0; k < SB / CP_ROWS; ++k) t += red[k][tid];
-        vec[tid] = bj[tid] - t;  // u = z_J - sum L_KJ^T x_K (zero past R)
+        const T u = bj[tid] - t;
+        vec[c0 + tid] = u;
+        if (H > 1 && h > 0 && tid < Rh) st_sc1(&ubuf[J0 + c0 + tid], u);
       }
-      lds_sync();
-      T x[RP_ROWS] = {T(0), T(0), T(0), T(0)};
+      if (H > 1 && tid < c0) vec[tid] = T(0);
+      // the slices above, as far as the block has rows, polled together
+      // with x_{J+1} (the forward sweep's joint poll, mirrored)
+      const bool both = H > 1 && h < H - 1 && !last;
+      if (H > 1 && h < H - 1) {
+        const int up = c0 + RW;
+        const int n1 = N - (J + 1) * SB < SB ? N - (J + 1) * SB : SB;
+        if (!stage2(ubuf + J0 + up, R - up, SB - up, vec + up, both ? xbuf + (int64_t)(J + 1) * SB : nullptr, n1, SB,
+                    vs[0]))
+          return;
+      } else {
+        lds_sync();
+      }
+      T x[RPR];
+#pragma unroll
+      for (int k = 0; k < RPR; ++k) x[k] = T(0);
       dot_xs(x, vec);  // X_J^T u
       if (!last) {     // the hand-off: x_J = X_J^T u - Q_J x_{J+1}
-        if (!stage(xbuf, J + 1, 1, 1)) return;
-        T d[RP_ROWS] = {T(0), T(0), T(0), T(0)};
+        if (!both && !stage(xbuf, J + 1, 1, 1)) return;
+        T d[RPR];
+#pragma unroll
+        for (int k = 0; k < RPR; ++k) d[k] = T(0);
         dot_rows(d, tb, vs[0]);
 #pragma unroll
-        for (int k = 0; k < RP_ROWS; ++k) x[k] -= d[k];
+        for (int k = 0; k < RPR; ++k) x[k] -= d[k];
       }
 #pragma unroll
-      for (int k = 0; k < RP_ROWS; ++k) {
+      for (int k = 0; k < RPR; ++k) {
         const T xk = lanes16_sum(x[k]);
-        const int rr = RP_ROWS * rg + k;
-        if (cg == 0 && rr < R) {
-          st_sc1(&xbuf[J0 + rr], xk);
-          b[J0 + rr] = xk;
+        const int rr = RPR * rg + k;
+        if (cg == 0 && rr < Rh) {
+          st_sc1(&xbuf[J0 + c0 + rr], xk);
+          b[J0 + c0 + rr] = xk;
         }
       }
     }
@@ -578,27 +697,71 @@ hipError_t solve_prep(const float* K, int64_t ld, int N, const float* Linv, floa
   return solve_prep_t<float>(K, ld, N, Linv, P, st);
 }
 
+int64_t solve_vec_elems(int N) {
+  const int64_t nb = (N + SB - 1) / SB;
+  return 2 * nb * SB;
+}
+
+// Parts per block (H).  Debug bits force 2 or 4 (both: 1); otherwise from the measured
+// solves of profiles/solve_split/solve_hops.txt (the solve),
+// which rank the same in fp64 and fp32: one block has nothing to split; H = 4
+// is fastest at N = 640 .. 11264 (0.377 against 0.520 ms per fp64 solve at
+// N = 11264), H = 2 at N = 16384 (0.626 against 0.655 for H = 4 and 0.783
+// unsplit), where four parts per block no longer find a CU each
+template <typename T>
+static int solve_parts(int N) {
+  const int dbg = debug_inject_mask();
+  if ((dbg & IPMZ_DEBUG_SOLVE_H2) && (dbg & IPMZ_DEBUG_SOLVE_H4)) return 1;
+  if (dbg & IPMZ_DEBUG_SOLVE_H4) return 4;
+  if (dbg & IPMZ_DEBUG_SOLVE_H2) return 2;
+  if (N <= SB) return 1;
+  return N <= 12288 ? 4 : 2;
+}
+
+// one sweep's launch.  No workgroup waits for one that has not started (the
+// tickets), so the grid is only capped by what could be resident: 256 CUs, a
+// part's LDS (mostly its RW rows of X_J) and its threads of the CU's 2048
+template <typename T, bool BWD, int H>
+static hipError_t launch_sweep(const T* K, int64_t ld, int N, const T* D, const T* P, T* b, T* ybuf, T* xbuf,
+                               unsigned* ctrl, hipStream_t st, const unsigned* skip) {
+  const int nb = (N + SB - 1) / SB;
+  const int64_t q = (int64_t)nb * SB * SB;
+  constexpr int RW = SB / H;
+  constexpr int64_t lds = (int64_t)sizeof(T) * (RW * XS_LD + (SB / CP_ROWS) * RW + 3 * SB + RW) + 64;
+  constexpr int by_threads = 2048 / SNT;
+  constexpr int per_cu = 160 * 1024 / lds < by_threads ? (int)(160 * 1024 / lds) : by_threads;
+  static_assert(per_cu >= 1, "a part's LDS fits a CU");
+  const int tickets = nb * H, cap = 256 * per_cu;
+  const int grid = tickets < cap ? tickets : cap;
+  const int inject = debug_inject_mask() & IPMZ_INJECT_SOLVE;
+  hipLaunchKernelGGL((trsv128_kernel<T, BWD, H>), dim3(grid), dim3(SNT), 0, st, K, ld, N, D, P, P + q, P + 2 * q,
+                     P + 3 * q, b, ybuf, xbuf, ctrl, nb, skip, inject);
+  return hipGetLastError();
+}
+template <typename T, bool BWD>
+static hipError_t sweep_t(const T* K, int64_t ld, int N, const T* D, const T* P, T* b, T* ybuf, T* xbuf,
+                          unsigned* ctrl, hipStream_t st, const unsigned* skip) {
+  if (N <= 0) return hipSuccess;
+  if (ld % 2) return hipErrorInvalidValue;  // 2-element vector loads of the tiles
+  switch (solve_parts<T>(N)) {
+    case 4: return launch_sweep<T, BWD, 4>(K, ld, N, D, P, b, ybuf, xbuf, ctrl, st, skip);
+    case 2: return launch_sweep<T, BWD, 2>(K, ld, N, D, P, b, ybuf, xbuf, ctrl, st, skip);
+    default: return launch_sweep<T, BWD, 1>(K, ld, N, D, P, b, ybuf, xbuf, ctrl, st, skip);
+  }
+}
+
+// no per-solve memsets: each launch leaves the state the next one needs (the
+// forward resets x, the u slices and the backward ticket, the backward resets
+// y, the v slices and the forward ticket); solve_reset establishes it after a
+// factorization.  The two sweeps are two launches (each its own register
+// allocation) of the same H.  An unsplit solve neither writes nor resets the
+// slices, so solves of different H may follow each other on one factor.
 template <typename T>
 static hipError_t solve_persistent_t(const T* K, int64_t ld, int N, const T* D, const T* P, T* b, T* ybuf, T* xbuf,
                                      unsigned* ctrl, hipStream_t st, const unsigned* skip) {
-  if (N <= 0) return hipSuccess;
-  if (ld % 2) return hipErrorInvalidValue;  // 2-element vector loads of the tiles
-  const int nb = (N + SB - 1) / SB;
-  const int64_t q = (int64_t)nb * SB * SB;
-  // no per-solve memsets: each launch leaves the state the next one needs
-  // (the forward resets x and the backward ticket, the backward resets y and
-  // the forward ticket); solve_reset establishes it after a factorization
-  hipError_t e = hipSuccess;
-  // the two sweeps as two launches (each its own register allocation);
-  // resident grids: one workgroup per CU
-  const int grid = nb < 256 ? nb : 256;
-  const int inject = debug_inject_mask() & IPMZ_INJECT_SOLVE;
-  hipLaunchKernelGGL((trsv128_kernel<T, false>), dim3(grid), dim3(SNT), 0, st, K, ld, N, D, P, P + q, P + 2 * q,
-                     P + 3 * q, b, ybuf, xbuf, ctrl, nb, skip, inject);
-  if ((e = hipGetLastError()) != hipSuccess) return e;
-  hipLaunchKernelGGL((trsv128_kernel<T, true>), dim3(grid), dim3(SNT), 0, st, K, ld, N, D, P, P + q, P + 2 * q,
-                     P + 3 * q, b, ybuf, xbuf, ctrl, nb, skip, inject);
-  return hipGetLastError();
+  const hipError_t e = sweep_t<T, false>(K, ld, N, D, P, b, ybuf, xbuf, ctrl, st, skip);
+  if (e != hipSuccess) return e;
+  return sweep_t<T, true>(K, ld, N, D, P, b, ybuf, xbuf, ctrl, st, skip);
 }
 
 // one sweep of the persistent solve (forward: y = L^{-1} b into ybuf;
@@ -607,19 +770,8 @@ static hipError_t solve_persistent_t(const T* K, int64_t ld, int N, const T* D, 
 hipError_t ldlt_solve_persistent_sweep(const double* K, int64_t ld, int N, const double* D, const double* P,
                                        double* b, double* ybuf, double* xbuf, unsigned* ctrl, bool backward,
                                        hipStream_t st, const unsigned* skip) {
-  if (N <= 0) return hipSuccess;
-  if (ld % 2) return hipErrorInvalidValue;
-  const int nb = (N + SB - 1) / SB;
-  const int64_t q = (int64_t)nb * SB * SB;
-  const int grid = nb < 256 ? nb : 256;
-  const int inject = debug_inject_mask() & IPMZ_INJECT_SOLVE;
-  if (backward)
-    hipLaunchKernelGGL((trsv128_kernel<double, true>), dim3(grid), dim3(SNT), 0, st, K, ld, N, D, P, P + q, P + 2 * q,
-                       P + 3 * q, b, ybuf, xbuf, ctrl, nb, skip, inject);
-  else
-    hipLaunchKernelGGL((trsv128_kernel<double, false>), dim3(grid), dim3(SNT), 0, st, K, ld, N, D, P, P + q,
-                       P + 2 * q, P + 3 * q, b, ybuf, xbuf, ctrl, nb, skip, inject);
-  return hipGetLastError();
+  return backward ? sweep_t<double, true>(K, ld, N, D, P, b, ybuf, xbuf, ctrl, st, skip)
+                  : sweep_t<double, false>(K, ld, N, D, P, b, ybuf, xbuf, ctrl, st, skip);
 }
 
 namespace {
@@ -651,8 +803,8 @@ hipError_t solve_reset(void* ybuf, void* xbuf, size_t elem, int N, unsigned* ctr
     most = n > most ? n : most;
   };
   add(ctrl, IPMZ_SOLVE_CTRL_WORDS, 0u);  // tickets + sticky error
-  add(ybuf, (int64_t)N * (int64_t)elem / 4, ~0u);
-  add(xbuf, (int64_t)N * (int64_t)elem / 4, ~0u);
+  add(ybuf, solve_vec_elems(N) * (int64_t)elem / 4, ~0u);  // block vectors + the parts' slices
+  add(xbuf, solve_vec_elems(N) * (int64_t)elem / 4, ~0u);
   add(info, 1, 0x7f7f7f7fu);  // "no pivot failed" (the byte pattern of hipMemset 0x7f)
   add(info2, 1, 0x7f7f7f7fu);
   add(words, nwords, 0u);

@@ -75,8 +75,8 @@ int main(int argc, char** argv) {
   CK(hipMalloc(&info, 64));
   double *yb, *xb;
   unsigned *ctrl, *pctrl;
-  CK(hipMalloc(&yb, N * 8));
-  CK(hipMalloc(&xb, N * 8));
+  CK(hipMalloc(&yb, ipmz::solve_vec_elems(N) * 8));
+  CK(hipMalloc(&xb, ipmz::solve_vec_elems(N) * 8));
   CK(hipMalloc(&ctrl, 256));
   CK(hipMemset(ctrl, 0, 256));
   CK(hipMalloc(&pctrl, ipmz::panel_ctrl_words(N, 64) * 4));
@@ -110,13 +110,16 @@ int main(int argc, char** argv) {
                   tag, N, ms, 4, nb - 1, hop / cnt / 100.0, det / cnt / 100.0, post / cnt / 100.0, wait / cnt / 100.0,
                   late);
       // block J's clocks relative to the store of y_{J-1}
-      double rel[5] = {0, 0, 0, 0, 0};
+      // (a split block: the clocks of its last part; slot 5 = the sibling parts' slices seen, 0 when unsplit)
+      double rel[6] = {0, 0, 0, 0, 0, 0};
       for (int j = 4; j < nb && j < 256; ++j)
-        for (int i = 0; i < 5; ++i) rel[i] += ((double)stp[0][j][i] - (double)stp[0][j - 1][3]) / 100.0;
-      std::printf("   block J vs y_{J-1} stored (us): start %.2f, bulk done %.2f, at hand-off %.2f, "
-                  "y_{J-1} seen %.2f, y_J stored %.2f; previous stores: y_{J-2} %.2f, y_{J-3} %.2f\n",
-                  rel[0] / cnt, rel[1] / cnt, rel[2] / cnt, rel[4] / cnt, rel[3] / cnt, -hop / cnt / 100.0,
-                  -2 * hop / cnt / 100.0);
+        for (int i = 0; i < 6; ++i)
+          rel[i] += stp[0][j][i] ? ((double)stp[0][j][i] - (double)stp[0][j - 1][3]) / 100.0 : 0.0;
+      std::printf("   block J vs y_{J-1} stored (us): start %.2f, bulk done %.2f, sibling slices seen %.2f, "
+                  "at hand-off %.2f, y_{J-1} seen %.2f, y_J stored %.2f; previous stores: y_{J-2} %.2f, "
+                  "y_{J-3} %.2f\n",
+                  rel[0] / cnt, rel[1] / cnt, rel[5] / cnt, rel[2] / cnt, rel[4] / cnt, rel[3] / cnt,
+                  -hop / cnt / 100.0, -2 * hop / cnt / 100.0);
     };
     double* P;
     CK(hipMalloc(&P, ipmz::solve_prep_elems(N) * 8));
@@ -135,8 +138,8 @@ int main(int argc, char** argv) {
     CK(hipMalloc(&L32, nl * 4));
     CK(hipMalloc(&P32, ipmz::solve_prep_elems(N) * 4));
     CK(hipMalloc(&b32, N * 4));
-    CK(hipMalloc(&y32, N * 4));
-    CK(hipMalloc(&x32, N * 4));
+    CK(hipMalloc(&y32, ipmz::solve_vec_elems(N) * 4));
+    CK(hipMalloc(&x32, ipmz::solve_vec_elems(N) * 4));
     hipLaunchKernelGGL(kb_to_f32, dim3(2048), dim3(256), 0, st, K, K32, ld * N);
     hipLaunchKernelGGL(kb_to_f32, dim3(64), dim3(256), 0, st, D, D32, (int64_t)N);
     hipLaunchKernelGGL(kb_to_f32, dim3(512), dim3(256), 0, st, Linv, L32, nl);
