@@ -17,6 +17,11 @@
  *                                  vector at a time): overwriting_solve_ldlt for a block
  *                                  of right-hand sides, one per row, as a blocked
  *                                  triangular solve that reads L once per sweep
+ *   ipmz_mixed_solve_multi, ipmz_qp_kkt_solve_mixed, ipmz_sym_residual_multi
+ *                               <- no reference counterpart either: the same block of
+ *                                  right-hand sides through the fp32 factor (blocked fp32
+ *                                  solve) with fp64 refinement and a per-row stop test;
+ *                                  the refinement's residual R = B - X K on its own
  *   ipmz_qp_create + ipmz_qp_load_host
  *                               <- NumericalOptimization::build_environment
  *                                  (EnvironmentBuilder.h:19-20, EnvironmentBuilder.cpp:7-76)
@@ -152,8 +157,9 @@ int ipmz_ldlt_prepare_solve(ipmz_ctx* ctx, int N, const double* L, int64_t ld, v
  * are solved together, blocked over column panels of IPMZ_SOLVE_MULTI_PANEL
  * columns on fp64 MFMA (L read once per sweep; stream-ordered launches, no
  * cross-workgroup waiting, deterministic), below it one after the other.
- * ws as for ipmz_ldlt_solve.  Out of scope: multi-right-hand-side forms of
- * ipmz_mixed_solve, ipmz_normal_solve and ipmz_bk_solve. */
+ * ws as for ipmz_ldlt_solve.  The multi-right-hand-side form of
+ * ipmz_mixed_solve is ipmz_mixed_solve_multi (below).  Out of scope:
+ * multi-right-hand-side forms of ipmz_normal_solve and ipmz_bk_solve. */
 #define IPMZ_SOLVE_MULTI_PANEL 256
 int ipmz_ldlt_solve_multi(ipmz_ctx* ctx, int N, const double* K, int64_t ld, const double* D, const void* ws,
                           double* B, int64_t ldb, int nrhs);
@@ -171,6 +177,33 @@ int ipmz_mixed_factor(ipmz_ctx* ctx, int N, const double* K, int64_t ld, void* w
  * corrections applied}. */
 int ipmz_mixed_solve(ipmz_ctx* ctx, int N, const double* K, int64_t ld, void* ws, double* b, double tol,
                      int max_refine, double* stat);
+/* The same solve for nrhs right-hand sides, the rows of B (device, stride ldb
+ * >= N, even; K's ld even too, K and B 16-byte aligned; B[r][N .. ldb) is
+ * never written, K is left intact).  Per pass: one blocked fp32 solve of all
+ * rows (fp32 MFMA, column panels as ipmz_ldlt_solve_multi), x += correction,
+ * the fp64 residual of all rows (ipmz_sym_residual_multi's kernel) and the
+ * stop test of ipmz_mixed_solve PER ROW.  A row that met tol is frozen: its
+ * solution and its stat {ratio reached, corrections applied} are those of the
+ * pass where it stopped, so a row's result does not depend on which other rows
+ * are in the call.  Passes run until every row stopped or max_refine
+ * corrections are applied.  Deterministic (stream-ordered launches, no
+ * atomics).  The host reads the stop word after every pass: the call BLOCKS,
+ * and returns IPMZ_ERR_STATE while the context's stream is capturing a
+ * hipGraph.  nrhs == 1 is ipmz_mixed_solve (bitwise, stat included; mws
+ * unused); below a crossover nrhs the rows go through it one by one.
+ * ws: the workspace ipmz_mixed_factor filled; mws: extra device workspace of
+ * ipmz_mixed_multi_workspace_bytes(N, nrhs) bytes (x, the fp32 right-hand
+ * sides, per-row state), required for nrhs >= 2: too small is
+ * IPMZ_ERR_INVALID.  stat (host, may be NULL): nrhs x 2 doubles. */
+int64_t ipmz_mixed_multi_workspace_bytes(ipmz_ctx* ctx, int N, int nrhs);
+int ipmz_mixed_solve_multi(ipmz_ctx* ctx, int N, const double* K, int64_t ld, void* ws, double* B, int64_t ldb,
+                           int nrhs, double tol, int max_refine, void* mws, int64_t mws_bytes, double* stat);
+/* R = B - X K for nrhs rows (device, asynchronous), K symmetric with only its
+ * lower triangle read, on fp64 MFMA; every element is summed in a fixed order
+ * (deterministic).  ld, ldx, ldb, ldr >= N and even, all four matrices 16-byte
+ * aligned; R may alias B. */
+int ipmz_sym_residual_multi(ipmz_ctx* ctx, int N, const double* K, int64_t ld, const double* X, int64_t ldx,
+                            const double* B, int64_t ldb, double* R, int64_t ldr, int nrhs);
 
 /* ---- normal-equations reduction (config C2) ------------------------------
  * The reference derives it symbolically (get_normal_equations,
@@ -343,8 +376,20 @@ int ipmz_qp_kkt_dim(ipmz_qp* qp);
  * fp64 LDL^T: IPMZ_ERR_INVALID for batches, IPMZ_EQ_NONE (Bunch-Kaufman), an
  * enabled normal-equations reduction or mixed-precision mode.  The Newton
  * step itself is untouched: its two solves depend on each other and stay
- * single-vector. */
+ * single-vector.  The mixed-precision form is ipmz_qp_kkt_solve_mixed. */
 int ipmz_qp_kkt_solve(ipmz_qp* qp, int nrhs, double* B, int64_t ldb);
+/* ipmz_qp_kkt_solve through the fp32 factor + fp64 refinement
+ * (ipmz_mixed_factor + ipmz_mixed_solve_multi on the assembled KKT matrix),
+ * whether or not the QP's steps use mixed precision.  B 16-byte aligned; tol,
+ * max_refine, stat (host, nrhs x 2, may be NULL) as ipmz_mixed_solve_multi.
+ * Under the restrictions of ipmz_qp_set_mixed_precision: IPMZ_ERR_INVALID for
+ * batches, IPMZ_EQ_NONE, penalty-function equalities or an enabled
+ * normal-equations reduction.  Allocates the QP's mixed-precision workspace on
+ * first use (the one ipmz_qp_set_mixed_precision uses, never reallocated) and
+ * a multi workspace for the largest nrhs seen.  Returns the fp32 factor's
+ * info; synchronizes; IPMZ_ERR_STATE during a graph capture.  Leaves the
+ * iterate and all later steps bitwise unchanged in both step modes. */
+int ipmz_qp_kkt_solve_mixed(ipmz_qp* qp, int nrhs, double* B, int64_t ldb, double tol, int max_refine, double* stat);
 /* Newton directions through the mixed-precision solve (fp32 factor of the
  * scaled KKT matrix + fp64 refinement to tol, at most max_refine corrections
  * per solve); enable = 0 returns to the fp64 factor.  Single QPs only.  The

@@ -5,6 +5,7 @@
 // entry point fails with IPMZ_ERR_NO_DEVICE.
 #include <hip/hip_runtime.h>
 
+#include <algorithm>
 #include <climits>
 #include <cmath>
 #include <cstdio>
@@ -540,6 +541,101 @@ int ipmz_mixed_solve(ipmz_ctx* ctx, int N, const double* K, int64_t ld, void* ws
   return IPMZ_OK;
 }
 
+}  // extern "C"
+
+// Mixed-precision multi-right-hand-side solve (mixed_multi.hip, trsm32.hip).
+// MIXED_MULTI_PANEL: column panel of the blocked fp32 solve;
+// MIXED_MULTI_CROSSOVER: the number of right-hand sides from which the blocked
+// refinement runs -- below it the rows go through mixed_solve one by one.
+// Both from tools/mixed_multi_bench.py (profiles/mixed_multi/bench.json and
+// crossover_scan.json, DESIGN.md "Mixed-precision multi-right-hand-side
+// solve"): 256 columns beat 128 and 512 at every measured point.  At tol =
+// 1e-12, max_refine = 20 the blocked path breaks even with the loop at 5.0
+// rows (N = 2560) and 5.6 rows (N = 16384) and leads by 1.41x / 1.25x at 7.
+// That loop pays ~18 skipped passes per vector (it enqueues all max_refine + 1,
+// ~30 us each once the stop test holds: 0.5 of its 2.4 ms at N = 16384);
+// with a small max_refine it does not, which moves the break-even at N = 16384
+// to ~7.1 rows.  8 is the first count with a clear margin either way
+// (measured 1.60x / 1.43x).
+static constexpr int MIXED_MULTI_PANEL = 256;
+static constexpr int MIXED_MULTI_CROSSOVER = 8;
+static_assert(MIXED_MULTI_PANEL % 128 == 0 && MIXED_MULTI_PANEL <= IPMZ_TRSM_PANEL_MAX, "panel width");
+
+// nrhs >= 2 rows through the factor in w (w.hst == nullptr: the looped solves
+// enqueue all their passes); stats left in m.stat, copied to stat (host, may be
+// null); synchronizes
+static int mixed_multi_impl(ipmz_ctx* ctx, const double* K, int64_t ld, MixedWs& w, const MixedMultiWs& m, double* B,
+                            int64_t ldb, int nrhs, double tol, int max_refine, double* stat) {
+  const int dbg = debug_inject_mask();
+  hipStream_t st = ctx->stream;
+  if (nrhs < MIXED_MULTI_CROSSOVER && !(dbg & IPMZ_DEBUG_MULTI_BLOCKED)) {
+    for (int r = 0; r < nrhs; ++r) {
+      HIP_OK(mixed_solve(K, ld, w, B + (int64_t)r * ldb, tol, max_refine, st));
+      HIP_OK(hipMemcpyAsync(m.stat + 2 * r, w.stat, 2 * sizeof(double), hipMemcpyDeviceToDevice, st));
+    }
+  } else {
+    const int pw = (dbg & IPMZ_DEBUG_MULTI_W512) ? 512 : (dbg & IPMZ_DEBUG_MULTI_W128) ? 128 : MIXED_MULTI_PANEL;
+    HIP_OK(mixed_solve_multi(K, ld, w, m, B, ldb, nrhs, tol, max_refine, pw, st));
+  }
+  if (stat) HIP_OK(hipMemcpyAsync(stat, m.stat, (size_t)nrhs * 2 * sizeof(double), hipMemcpyDeviceToHost, st));
+  HIP_OK(hipStreamSynchronize(st));
+  return IPMZ_OK;
+}
+
+static int not_capturing(ipmz_ctx* ctx, const char* who) {
+  hipStreamCaptureStatus cs = hipStreamCaptureStatusNone;
+  HIP_OK(hipStreamIsCapturing(ctx->stream, &cs));
+  if (cs != hipStreamCaptureStatusNone)
+    return fail(IPMZ_ERR_STATE, std::string(who) + ": the context's stream is capturing a hipGraph; this call waits "
+                                                   "for its stop test on the host and cannot be captured");
+  return IPMZ_OK;
+}
+
+extern "C" {
+
+int64_t ipmz_mixed_multi_workspace_bytes(ipmz_ctx* ctx, int N, int nrhs) {
+  if (!ctx || N < 0 || nrhs < 0) return 0;
+  MixedMultiWs m;
+  return mixed_multi_ws_carve(nullptr, N, nrhs, m);
+}
+
+int ipmz_mixed_solve_multi(ipmz_ctx* ctx, int N, const double* K, int64_t ld, void* ws, double* B, int64_t ldb,
+                           int nrhs, double tol, int max_refine, void* mws, int64_t mws_bytes, double* stat) {
+  if (!ctx || N < 0 || nrhs < 0 || max_refine < 0 || ld < N || ldb < N || (ld & 1) || (ldb & 1))
+    return fail(IPMZ_ERR_INVALID, "ipmz_mixed_solve_multi: bad arguments (nrhs >= 0, max_refine >= 0, ld >= N, "
+                                  "ldb >= N, both even)");
+  if (N == 0 || nrhs == 0) return IPMZ_OK;
+  if (!K || !ws || !B) return fail(IPMZ_ERR_INVALID, "ipmz_mixed_solve_multi: null pointer");
+  HIP_OK(hipSetDevice(ctx->device));
+  int rc = not_capturing(ctx, "ipmz_mixed_solve_multi");
+  if (rc) return rc;
+  if (nrhs == 1) return ipmz_mixed_solve(ctx, N, K, ld, ws, B, tol, max_refine, stat);
+  if (((uintptr_t)K & 15) || ((uintptr_t)B & 15))
+    return fail(IPMZ_ERR_INVALID, "ipmz_mixed_solve_multi: K and B must be 16-byte aligned");
+  MixedMultiWs m;
+  if (!mws || mws_bytes < mixed_multi_ws_carve(nullptr, N, nrhs, m))
+    return fail(IPMZ_ERR_INVALID, "ipmz_mixed_solve_multi: multi workspace too small "
+                                  "(ipmz_mixed_multi_workspace_bytes(N, nrhs))");
+  mixed_multi_ws_carve(static_cast<char*>(mws), N, nrhs, m);
+  MixedWs w;
+  mixed_ws_carve(static_cast<char*>(ws), N, nbo_for(ctx, N), w);
+  return mixed_multi_impl(ctx, K, ld, w, m, B, ldb, nrhs, tol, max_refine, stat);
+}
+
+int ipmz_sym_residual_multi(ipmz_ctx* ctx, int N, const double* K, int64_t ld, const double* X, int64_t ldx,
+                            const double* B, int64_t ldb, double* R, int64_t ldr, int nrhs) {
+  if (!ctx || N < 0 || nrhs < 0 || ld < N || ldx < N || ldb < N || ldr < N || (ld & 1) || (ldx & 1) || (ldb & 1) ||
+      (ldr & 1))
+    return fail(IPMZ_ERR_INVALID, "ipmz_sym_residual_multi: bad arguments (nrhs >= 0; ld, ldx, ldb, ldr >= N and even)");
+  if (N == 0 || nrhs == 0) return IPMZ_OK;
+  if (!K || !X || !B || !R) return fail(IPMZ_ERR_INVALID, "ipmz_sym_residual_multi: null pointer");
+  if (((uintptr_t)K & 15) || ((uintptr_t)X & 15) || ((uintptr_t)B & 15) || ((uintptr_t)R & 15))
+    return fail(IPMZ_ERR_INVALID, "ipmz_sym_residual_multi: K, X, B and R must be 16-byte aligned");
+  HIP_OK(hipSetDevice(ctx->device));
+  HIP_OK(sym_residual_multi(K, ld, N, X, ldx, B, ldb, R, ldr, nrhs, ctx->stream));
+  return IPMZ_OK;
+}
+
 // Normal equations (config C2) ---------------------------------------------
 }  // extern "C"
 
@@ -864,6 +960,9 @@ struct ipmz_qp {
   int ir_max = 10;
   MixedWs mw;
   char* mws = nullptr;
+  // ipmz_qp_kkt_solve_mixed: the multi-right-hand-side workspace, for the largest nrhs seen
+  char* mmws = nullptr;
+  int mmws_nrhs = 0;
   // normal-equations reduction (C2)
   bool normal = false;
   // EqualityHandling::None: Bunch-Kaufman factor (pivots per QP)
@@ -1627,6 +1726,7 @@ int ipmz_qp_destroy(ipmz_qp* s) {
     delete[] s->tr_pairs;
   }
   for (void* p : s->allocs) hipFree(p);
+  if (s->mmws) hipFree(s->mmws);
   if (s->mw.hev) hipEventDestroy(s->mw.hev);
   if (s->mw.hst) hipHostFree(s->mw.hst);
   ipmz_ctx* ctx = s->ctx;
@@ -1777,29 +1877,106 @@ int ipmz_qp_kkt_solve(ipmz_qp* s, int nrhs, double* B, int64_t ldb) {
   return read_info(s->ctx, s->ws, s->N);  // synchronizes; checks the error words of s->ws itself
 }
 
+// the QP's mixed-precision workspace, allocated once (a captured step keeps its addresses)
+static int ensure_mixed_ws(ipmz_qp* s) {
+  if (s->mws) return IPMZ_OK;
+  const int64_t bytes = mixed_ws_bytes(s->N, nbo_for(s->ctx, s->N));
+  void* w = nullptr;
+  if (hipMalloc(&w, (size_t)bytes) != hipSuccess) return fail(IPMZ_ERR_NOMEM, "device allocation failed");
+  s->allocs.push_back(w);
+  HIP_OK(hipMemset(w, 0, (size_t)bytes));  // sticky error words start clear
+  s->mws = static_cast<char*>(w);
+  mixed_ws_carve(s->mws, s->N, nbo_for(s->ctx, s->N), s->mw);
+  void* h = nullptr;  // the stop test's host-mapped word (eager solves wait on it)
+  if (hipHostMalloc(&h, 64, hipHostMallocMapped | hipHostMallocCoherent) != hipSuccess)
+    return fail(IPMZ_ERR_NOMEM, "host allocation failed");
+  s->mw.hst = static_cast<unsigned*>(h);
+  s->mw.hst[0] = s->mw.hst[1] = 0u;
+  void* hd = nullptr;
+  HIP_OK(hipHostGetDevicePointer(&hd, h, 0));
+  s->mw.hst_dev = static_cast<unsigned*>(hd);
+  HIP_OK(hipEventCreateWithFlags(&s->mw.hev, hipEventDisableTiming));
+  return IPMZ_OK;
+}
+
+int ipmz_qp_kkt_solve_mixed(ipmz_qp* s, int nrhs, double* B, int64_t ldb, double tol, int max_refine, double* stat) {
+  if (!s) return fail(IPMZ_ERR_INVALID, "null qp");
+  if (s->B != 1) return fail(IPMZ_ERR_INVALID, "ipmz_qp_kkt_solve_mixed: single QPs only, this is a batch");
+  if (s->eqnone)
+    return fail(IPMZ_ERR_INVALID, "ipmz_qp_kkt_solve_mixed: EqualityHandling::None factors with Bunch-Kaufman, which "
+                                  "has no mixed-precision form");
+  if (s->eqpen)
+    return fail(IPMZ_ERR_INVALID, "ipmz_qp_kkt_solve_mixed: EqualityHandling::PenaltyFunction has no mixed-precision "
+                                  "form");
+  if (s->normal)
+    return fail(IPMZ_ERR_INVALID, "ipmz_qp_kkt_solve_mixed: the normal-equations reduction is enabled (augmented "
+                                  "system only)");
+  if (!s->loaded) return fail(IPMZ_ERR_STATE, "load or generate the QP first");
+  if (nrhs < 0 || max_refine < 0 || ldb < s->N || (ldb & 1) || (nrhs > 0 && !B))
+    return fail(IPMZ_ERR_INVALID, "ipmz_qp_kkt_solve_mixed: bad arguments (nrhs >= 0, max_refine >= 0, ldb >= N and "
+                                  "even)");
+  if (nrhs > 0 && ((uintptr_t)B & 15)) return fail(IPMZ_ERR_INVALID, "ipmz_qp_kkt_solve_mixed: B must be 16-byte aligned");
+  ipmz_ctx* ctx = s->ctx;
+  HIP_OK(hipSetDevice(ctx->device));
+  int rc = not_capturing(ctx, "ipmz_qp_kkt_solve_mixed");
+  if (rc) return rc;
+  if (s->step_pending) {  // a forked step still in flight uses the event pool the factor below takes
+    HIP_OK(hipEventSynchronize(s->step_done));
+    s->step_pending = false;
+  }
+  if ((rc = ensure_mixed_ws(s))) return rc;
+  const int cap = std::max(nrhs, 1);
+  if (cap > s->mmws_nrhs) {
+    HIP_OK(hipStreamSynchronize(ctx->stream));
+    if (s->mmws) hipFree(s->mmws);
+    s->mmws = nullptr;
+    s->mmws_nrhs = 0;
+    MixedMultiWs m;
+    void* p = nullptr;
+    if (hipMalloc(&p, (size_t)mixed_multi_ws_carve(nullptr, s->N, cap, m)) != hipSuccess)
+      return fail(IPMZ_ERR_NOMEM, "device allocation failed");
+    s->mmws = static_cast<char*>(p);
+    s->mmws_nrhs = cap;
+  }
+  // the step's own assembly, and the fp32 factor in the workspace a mixed step
+  // factors into again before it solves: the iterate is only read
+  hipStream_t st = ctx->stream;
+  HIP_OK(qp_assemble(s->qb, st));
+  MixedWs w = s->mw;
+  w.hst = nullptr;  // looped solves enqueue all passes: the steps' learned pass count stays theirs
+  w.hst_dev = nullptr;
+  w.hev = nullptr;
+  if ((rc = mixed_factor_impl(ctx, s->K, s->ldk, w, nullptr))) return rc;
+  MixedMultiWs m;
+  mixed_multi_ws_carve(s->mmws, s->N, cap, m);
+  if (nrhs == 1) {
+    HIP_OK(mixed_solve(s->K, s->ldk, w, B, tol, max_refine, st));
+    HIP_OK(hipMemcpyAsync(m.stat, w.stat, 2 * sizeof(double), hipMemcpyDeviceToDevice, st));
+    if (stat) HIP_OK(hipMemcpyAsync(stat, m.stat, 2 * sizeof(double), hipMemcpyDeviceToHost, st));
+  } else if (nrhs > 1) {
+    if ((rc = mixed_multi_impl(ctx, s->K, s->ldk, w, m, B, ldb, nrhs, tol, max_refine, stat))) return rc;
+  }
+  int info = 0;
+  unsigned e[2] = {0, 0};
+  HIP_OK(hipMemcpyAsync(&info, w.info, sizeof(int), hipMemcpyDeviceToHost, st));
+  HIP_OK(hipMemcpyAsync(&e[0], w.pctrl + PANEL_ERR_WORD, 4, hipMemcpyDeviceToHost, st));
+  HIP_OK(hipMemcpyAsync(&e[1], w.ctrl + SOLVE_ERR_WORD, 4, hipMemcpyDeviceToHost, st));
+  HIP_OK(hipStreamSynchronize(st));
+  if (e[0] || e[1])
+    return fail(IPMZ_ERR_HIP, "ipmz_qp_kkt_solve_mixed: a hand-off inside a persistent kernel of the mixed-precision "
+                              "factor / solve timed out; the result is invalid");
+  return info == 0x7f7f7f7f ? IPMZ_OK : info;
+}
+
 int ipmz_qp_set_mixed_precision(ipmz_qp* s, int enable, double tol, int max_refine) {
   if (!s) return fail(IPMZ_ERR_INVALID, "null qp");
   if (enable && (s->B != 1 || !(tol > 0.0) || max_refine < 0 || s->normal || s->eqnone || s->eqpen))
     return fail(IPMZ_ERR_INVALID, "mixed precision: single QPs, tol > 0, max_refine >= 0, augmented reduction, "
                                   "Regularization equalities");
   HIP_OK(hipSetDevice(s->ctx->device));
-  if (enable && !s->mws) {
-    const int64_t bytes = mixed_ws_bytes(s->N, nbo_for(s->ctx, s->N));
-    void* w = nullptr;
-    if (hipMalloc(&w, (size_t)bytes) != hipSuccess) return fail(IPMZ_ERR_NOMEM, "device allocation failed");
-    s->allocs.push_back(w);
-    HIP_OK(hipMemset(w, 0, (size_t)bytes));  // sticky error words start clear
-    s->mws = static_cast<char*>(w);
-    mixed_ws_carve(s->mws, s->N, nbo_for(s->ctx, s->N), s->mw);
-    void* h = nullptr;  // the stop test's host-mapped word (eager solves wait on it)
-    if (hipHostMalloc(&h, 64, hipHostMallocMapped | hipHostMallocCoherent) != hipSuccess)
-      return fail(IPMZ_ERR_NOMEM, "host allocation failed");
-    s->mw.hst = static_cast<unsigned*>(h);
-    s->mw.hst[0] = s->mw.hst[1] = 0u;
-    void* hd = nullptr;
-    HIP_OK(hipHostGetDevicePointer(&hd, h, 0));
-    s->mw.hst_dev = static_cast<unsigned*>(hd);
-    HIP_OK(hipEventCreateWithFlags(&s->mw.hev, hipEventDisableTiming));
+  if (enable) {
+    const int rc = ensure_mixed_ws(s);
+    if (rc) return rc;
   }
   s->mixed = enable != 0;
   s->ir_tol = tol;

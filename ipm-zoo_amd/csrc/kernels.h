@@ -39,7 +39,8 @@ namespace ipmz {
 // 8192 = batches assemble the whole KKT into K every step (not the kept K0) (A/B),
 // 16384 = batches run the two solves and the phases between them as separate launches (A/B),
 // 65536 = ipmz_ldlt_solve_multi runs its blocked path from 2 right-hand sides on (no looped single-vector
-//         solves below the crossover) (A/B, tools/solve_multi_bench.py),
+//         solves below the crossover) (A/B, tools/solve_multi_bench.py); ipmz_mixed_solve_multi and
+//         ipmz_qp_kkt_solve_mixed likewise (tools/mixed_multi_bench.py),
 // 131072 / 262144 = ... with 512- / 128-column panels instead of IPMZ_SOLVE_MULTI_PANEL (A/B),
 // 524288 / 1048576 = the persistent solve splits every 128-row block over 2 / 4 workgroups, whatever
 //         its table says; both bits = the unsplit solve (all three bitwise alike,
@@ -237,6 +238,34 @@ hipError_t mixed_factor(const double* K, int64_t ld, MixedWs& w, hipStream_t st,
 // b <- K^{-1} b by iterative refinement (device-side stop test)
 hipError_t mixed_solve(const double* K, int64_t ld, MixedWs& w, double* b, double tol, int max_refine,
                        hipStream_t st);
+
+// trsm32.hip: ldlt_solve_multi for the fp32 factor (nbi = 64).  B: nrhs rows
+// of fp32, solved in place; ld a multiple of 64, ldb of 4, K / Linv / B 16-byte
+// aligned, w a multiple of 128 (<= IPMZ_TRSM_PANEL_MAX)
+hipError_t ldlt_solve_multi(const float* K, int64_t ld, int N, const float* D, const float* Linv, float* B,
+                            int64_t ldb, int nrhs, int w, hipStream_t st);
+
+// mixed_multi.hip: the refinement of mixed_solve for nrhs right-hand sides
+// (rows of B) around the blocked fp32 solve, per-row stop test, frozen rows
+struct MixedMultiWs {
+  int64_t ldx = 0, ld32 = 0;
+  int ntiles = 0;
+  double* x = nullptr;       // nrhs x ldx: the solutions
+  float* r32 = nullptr;      // nrhs x ld32: the fp32 right-hand sides / corrections
+  double* part = nullptr;    // nrhs x ntiles x {max|r|, max|b|}
+  double* stat = nullptr;    // nrhs x {ratio reached, corrections applied}
+  unsigned* done = nullptr;  // nrhs: the row is frozen
+  unsigned* word = nullptr;  // every row is frozen
+};
+int64_t mixed_multi_ws_carve(char* base, int N, int nrhs, MixedMultiWs& m);  // base == nullptr: size only
+// rows of B <- K^{-1} row; blocks the host (reads the all-stopped word after
+// every pass); pw: panel width of the fp32 solve.  ld even, K 16-byte aligned.
+hipError_t mixed_solve_multi(const double* K, int64_t ld, const MixedWs& w, const MixedMultiWs& m, double* B,
+                             int64_t ldb, int nrhs, double tol, int max_refine, int pw, hipStream_t st);
+// R = B - X K, K symmetric from its lower triangle (fp64 MFMA); R may alias B.
+// ld, ldx even, K and X 16-byte aligned.
+hipError_t sym_residual_multi(const double* K, int64_t ld, int N, const double* X, int64_t ldx, const double* B,
+                              int64_t ldb, double* R, int64_t ldr, int nrhs, hipStream_t st);
 
 // normal.hip: normal-equations reduction (config C2) -------------------------
 hipError_t ne_check_sign(const double* D, int N, int offset, double sign, int* info, hipStream_t st);

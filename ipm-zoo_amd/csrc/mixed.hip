@@ -21,6 +21,9 @@
 // previous solve needed, waits for the stop test (host-mapped word) and only
 // then enqueues more -- the same kernels in the same order up to the pass
 // that converged, hence the same bits as the full loop.
+//
+// The form for many right-hand sides (blocked fp32 solve, one fp64 residual
+// pass for all rows, per-row stop test) is mixed_multi.hip.
 #include <algorithm>
 
 #include "common.h"

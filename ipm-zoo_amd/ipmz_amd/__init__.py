@@ -47,6 +47,7 @@ EXPORTS = [
     "ipmz_qp_set_reduction", "ipmz_bk_factor", "ipmz_bk_factor_ex", "ipmz_bk_solve", "ipmz_symmetric_indefinite_factorization",
     "ipmz_overwriting_solve_bunch_kaufman", "ipmz_debug_inject", "ipmz_batch_summary", "ipmz_batch_set_factor_kernel",
     "ipmz_qp_last_step_graph", "ipmz_ldlt_solve_multi", "ipmz_overwriting_solve_ldlt_multi", "ipmz_qp_kkt_solve",
+    "ipmz_mixed_multi_workspace_bytes", "ipmz_mixed_solve_multi", "ipmz_sym_residual_multi", "ipmz_qp_kkt_solve_mixed",
 ]
 SOLVE_MULTI_PANEL = 256  # include/ipmz.h IPMZ_SOLVE_MULTI_PANEL: column panel of the blocked multi-rhs solve
 REDUCTION_AUGMENTED, REDUCTION_NORMAL = 0, 1
@@ -155,6 +156,10 @@ def _load():
         "ipmz_ldlt_solve_multi": ([_VP, _I, _VP, _I64, _VP, _VP, _VP, _I64, _I], _I),
         "ipmz_overwriting_solve_ldlt_multi": ([_VP, _I, _P, _P, _P, _I], _I),
         "ipmz_qp_kkt_solve": ([_VP, _I, _VP, _I64], _I),
+        "ipmz_mixed_multi_workspace_bytes": ([_VP, _I, _I], _I64),
+        "ipmz_mixed_solve_multi": ([_VP, _I, _VP, _I64, _VP, _VP, _I64, _I, ctypes.c_double, _I, _VP, _I64, _P], _I),
+        "ipmz_sym_residual_multi": ([_VP, _I, _VP, _I64, _VP, _I64, _VP, _I64, _VP, _I64, _I], _I),
+        "ipmz_qp_kkt_solve_mixed": ([_VP, _I, _VP, _I64, ctypes.c_double, _I, _P], _I),
     }
     for name, (args, res) in sig.items():
         fn = getattr(lib, name)
@@ -260,6 +265,24 @@ class Context:
         _check(lib.ipmz_mixed_solve(self.h, N, _VP(K_ptr), ld, _VP(ws_ptr), _VP(b_ptr), tol, max_refine, _dp(stat)),
                "ipmz_mixed_solve")
         return float(stat[0]), int(stat[1])
+
+    def mixed_multi_workspace_bytes(self, N, nrhs):
+        return lib.ipmz_mixed_multi_workspace_bytes(self.h, N, nrhs)
+
+    def mixed_solve_multi(self, N, K_ptr, ld, ws_ptr, B_ptr, ldb, nrhs, mws_ptr, mws_bytes, tol=1e-12, max_refine=10):
+        """Every row of B (nrhs rows of length N, stride ldb, device) <- K^{-1} row through the
+        fp32 factor in ws; mws: mixed_multi_workspace_bytes(N, nrhs) bytes.  Blocks the host.
+        Returns an (nrhs, 2) array of {ratio reached, corrections applied} per row."""
+        stat = np.zeros((max(nrhs, 0), 2))
+        _check(lib.ipmz_mixed_solve_multi(self.h, N, _VP(K_ptr), ld, _VP(ws_ptr), _VP(B_ptr), ldb, nrhs, tol,
+                                          max_refine, _VP(mws_ptr), mws_bytes, _dp(stat)), "ipmz_mixed_solve_multi")
+        return stat
+
+    def sym_residual_multi(self, N, K_ptr, ld, X_ptr, ldx, B_ptr, ldb, R_ptr, ldr, nrhs):
+        """R = B - X K for nrhs rows (device, asynchronous), K symmetric from its lower triangle;
+        R may alias B."""
+        return _check(lib.ipmz_sym_residual_multi(self.h, N, _VP(K_ptr), ld, _VP(X_ptr), ldx, _VP(B_ptr), ldb,
+                                                  _VP(R_ptr), ldr, nrhs), "ipmz_sym_residual_multi")
 
     # -- Bunch-Kaufman on device memory (f3) --
     BK_AUTO, BK_WORKGROUP, BK_GRID = 0, 1, 2
@@ -508,6 +531,14 @@ class Optimizer:
         K^{-1} row with the KKT matrix of the current iterate (kkt()); returns
         the factor's info.  Single QPs on the fp64 augmented LDL^T only."""
         return _check(lib.ipmz_qp_kkt_solve(self.h, nrhs, _VP(B_ptr), ldb), "ipmz_qp_kkt_solve")
+
+    def kkt_solve_mixed(self, B_ptr, nrhs, ldb, tol=1e-12, max_refine=10):
+        """kkt_solve through the fp32 factor + fp64 refinement, whether or not the steps use mixed
+        precision; returns (the factor's info, (nrhs, 2) array of {ratio, corrections} per row)."""
+        stat = np.zeros((max(nrhs, 0), 2))
+        info = _check(lib.ipmz_qp_kkt_solve_mixed(self.h, nrhs, _VP(B_ptr), ldb, tol, max_refine, _dp(stat)),
+                      "ipmz_qp_kkt_solve_mixed")
+        return info, stat
 
     def set_timing(self, on=True):
         _check(lib.ipmz_qp_set_timing(self.h, 1 if on else 0), "ipmz_qp_set_timing")
