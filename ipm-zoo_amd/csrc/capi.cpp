@@ -452,6 +452,10 @@ int ipmz_ldlt_prepare_solve(ipmz_ctx* ctx, int N, const double* L, int64_t ld, v
 static constexpr int SOLVE_MULTI_PANEL = IPMZ_SOLVE_MULTI_PANEL;
 static constexpr int SOLVE_MULTI_CROSSOVER = 10;
 static_assert(SOLVE_MULTI_PANEL % 128 == 0 && SOLVE_MULTI_PANEL <= IPMZ_TRSM_PANEL_MAX, "panel width");
+// panel width of a blocked solve (fp64 here, fp32 in mixed_multi_impl): the debug bits', else the default
+static int multi_panel_width(int dbg, int dflt) {
+  return (dbg & IPMZ_DEBUG_MULTI_W512) ? 512 : (dbg & IPMZ_DEBUG_MULTI_W128) ? 128 : dflt;
+}
 
 int ipmz_ldlt_solve_multi(ipmz_ctx* ctx, int N, const double* K, int64_t ld, const double* D, const void* ws,
                           double* B, int64_t ldb, int nrhs) {
@@ -470,7 +474,7 @@ int ipmz_ldlt_solve_multi(ipmz_ctx* ctx, int N, const double* K, int64_t ld, con
     for (int r = 0; r < nrhs; ++r)
       HIP_OK(solve_ws(K, ld, N, D, static_cast<const char*>(ws), nbo, ctx->nbi, B + (int64_t)r * ldb, ctx->stream));
   } else {
-    const int w = (dbg & IPMZ_DEBUG_MULTI_W512) ? 512 : (dbg & IPMZ_DEBUG_MULTI_W128) ? 128 : SOLVE_MULTI_PANEL;
+    const int w = multi_panel_width(dbg, SOLVE_MULTI_PANEL);
     HIP_OK(ldlt_solve_multi(K, ld, N, D, reinterpret_cast<const double*>(static_cast<const char*>(ws) + l.linv_off),
                             ctx->nbi, B, ldb, nrhs, w, ctx->stream));
   }
@@ -543,7 +547,7 @@ int ipmz_mixed_solve(ipmz_ctx* ctx, int N, const double* K, int64_t ld, void* ws
 
 }  // extern "C"
 
-// Mixed-precision multi-right-hand-side solve (mixed_multi.hip, trsm32.hip).
+// Mixed-precision multi-right-hand-side solve (mixed_multi.hip, trsm.hip).
 // MIXED_MULTI_PANEL: column panel of the blocked fp32 solve;
 // MIXED_MULTI_CROSSOVER: the number of right-hand sides from which the blocked
 // refinement runs -- below it the rows go through mixed_solve one by one.
@@ -574,7 +578,7 @@ static int mixed_multi_impl(ipmz_ctx* ctx, const double* K, int64_t ld, MixedWs&
       HIP_OK(hipMemcpyAsync(m.stat + 2 * r, w.stat, 2 * sizeof(double), hipMemcpyDeviceToDevice, st));
     }
   } else {
-    const int pw = (dbg & IPMZ_DEBUG_MULTI_W512) ? 512 : (dbg & IPMZ_DEBUG_MULTI_W128) ? 128 : MIXED_MULTI_PANEL;
+    const int pw = multi_panel_width(dbg, MIXED_MULTI_PANEL);
     HIP_OK(mixed_solve_multi(K, ld, w, m, B, ldb, nrhs, tol, max_refine, pw, st));
   }
   if (stat) HIP_OK(hipMemcpyAsync(stat, m.stat, (size_t)nrhs * 2 * sizeof(double), hipMemcpyDeviceToHost, st));

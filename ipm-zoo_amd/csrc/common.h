@@ -49,6 +49,8 @@ __device__ __forceinline__ double4_t mfma_f64_16x16x4(double a, double b, double
 // the accumulator map that differs: f64 rows (l >> 4) + 4 r, f32 rows
 // 4 (l >> 4) + r (cdna_hip_programming.md §3; the f32 form is an exact f32
 // fma chain at 2x the f64 rate, 32 vs 64 cycles per instruction).
+// vec16_t: the 16-byte vector of one global load / LDS store, V elements
+// (HIP's own types: register rings of ext_vector_type values allocate worse).
 typedef float float4_t __attribute__((ext_vector_type(4)));
 template <typename T>
 struct Mfma;
@@ -56,6 +58,8 @@ template <>
 struct Mfma<double> {
   typedef double4_t acc_t;
   typedef double2 vec2_t;
+  typedef double2 vec16_t;
+  static constexpr int V = 2;
   static __device__ __forceinline__ acc_t mma(double a, double b, acc_t c) { return mfma_f64_16x16x4(a, b, c); }
   static __device__ __forceinline__ int row(int lane, int r) { return (lane >> 4) + 4 * r; }
 };
@@ -63,11 +67,32 @@ template <>
 struct Mfma<float> {
   typedef float4_t acc_t;
   typedef float2 vec2_t;
+  typedef float4 vec16_t;
+  static constexpr int V = 4;
   static __device__ __forceinline__ acc_t mma(float a, float b, acc_t c) {
     return __builtin_amdgcn_mfma_f32_16x16x4f32(a, b, c, 0, 0, 0);
   }
   static __device__ __forceinline__ int row(int lane, int r) { return 4 * (lane >> 4) + r; }
 };
+
+// Mfma<T>::V consecutive elements, zero where masked: ok0 = the first is
+// valid, nv = how many are.  Branch-free, so that the loads of a register ring
+// stay in flight behind counted waits (a branch around a load makes the
+// compiler drain every load at the join): a fully masked lane loads the
+// always-valid, 16-byte aligned `safe` instead and discards it.  p is 16-byte
+// aligned whenever ok0 (leading dimensions and column offsets multiples of V);
+// the discarded tail of a partly valid load lies in the row's padding or in
+// Linv's identity padding.
+template <typename T>
+__device__ __forceinline__ typename Mfma<T>::vec16_t fetch16(const T* p, const T* safe, bool ok0, int nv) {
+  // (loaded and masked as one native vector: through element accesses to
+  // HIP's double2 the load is split and its first half predicated -- a branch)
+  typedef T nat_t __attribute__((ext_vector_type(Mfma<T>::V)));
+  nat_t t = *reinterpret_cast<const nat_t*>(ok0 ? p : safe);
+#pragma unroll
+  for (int e = 0; e < Mfma<T>::V; ++e) t[e] = ok0 && (e == 0 || nv > e) ? t[e] : T(0);
+  return __builtin_bit_cast(typename Mfma<T>::vec16_t, t);
+}
 
 // Wave-level all-reductions (wave64) on the VALU: DPP inside 16-lane rows
 // (xor 1, xor 2, rotate 4, rotate 8), then v_permlane16_swap / 32_swap across

@@ -172,11 +172,16 @@ hipError_t ldlt_solve(const double* K, int64_t ld, int N, const double* D, const
 // trsm.hip: the same solve for nrhs right-hand sides at once.  B: nrhs rows of
 // length N (row r = right-hand side r, stride ldb >= N), solved in place;
 // blocked over column panels of width w (a multiple of 128, <=
-// IPMZ_TRSM_PANEL_MAX) on fp64 MFMA.  ld and ldb even, K and B 16-byte
-// aligned.  Stream-ordered launches only: no cross-workgroup waiting.
+// IPMZ_TRSM_PANEL_MAX) on fp64 / fp32 MFMA.  Stream-ordered launches only: no
+// cross-workgroup waiting.  Instantiated for
+//   double  the fp64 factor (nbi 64 or 128): ld and ldb even, K and B 16-byte
+//           aligned;
+//   float   the fp32 factor of the mixed-precision path (nbi == 64): ld a
+//           multiple of 64, ldb of 4, K / Linv / B 16-byte aligned.
 #define IPMZ_TRSM_PANEL_MAX 512
-hipError_t ldlt_solve_multi(const double* K, int64_t ld, int N, const double* D, const double* Linv, int nbi,
-                            double* B, int64_t ldb, int nrhs, int w, hipStream_t st);
+template <typename T>
+hipError_t ldlt_solve_multi(const T* K, int64_t ld, int N, const T* D, const T* Linv, int nbi, T* B, int64_t ldb,
+                            int nrhs, int w, hipStream_t st);
 
 // one workgroup per QP of a batch (small N); b: batch of rhs, stride sb
 hipError_t ldlt_solve_batched(const double* K, int64_t ld, int N, const double* D, const double* Linv, int nbi,
@@ -238,12 +243,6 @@ hipError_t mixed_factor(const double* K, int64_t ld, MixedWs& w, hipStream_t st,
 // b <- K^{-1} b by iterative refinement (device-side stop test)
 hipError_t mixed_solve(const double* K, int64_t ld, MixedWs& w, double* b, double tol, int max_refine,
                        hipStream_t st);
-
-// trsm32.hip: ldlt_solve_multi for the fp32 factor (nbi = 64).  B: nrhs rows
-// of fp32, solved in place; ld a multiple of 64, ldb of 4, K / Linv / B 16-byte
-// aligned, w a multiple of 128 (<= IPMZ_TRSM_PANEL_MAX)
-hipError_t ldlt_solve_multi(const float* K, int64_t ld, int N, const float* D, const float* Linv, float* B,
-                            int64_t ldb, int nrhs, int w, hipStream_t st);
 
 // mixed_multi.hip: the refinement of mixed_solve for nrhs right-hand sides
 // (rows of B) around the blocked fp32 solve, per-row stop test, frozen rows

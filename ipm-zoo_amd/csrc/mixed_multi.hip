@@ -2,7 +2,7 @@
 // mixed.hip with every right-hand side a row of B (stride ldb),
 //
 //   x = 0, r = b                                       (per row)
-//   pass: d = (S K S)^{-1}_{fp32} fp32(S r)            blocked fp32 solve, trsm32.hip
+//   pass: d = (S K S)^{-1}_{fp32} fp32(S r)            blocked fp32 solve, trsm.hip
 //         x += S d                                     rows still running
 //         r = b - x K (fp64), ratio = max|r| / max|b|  sym_residual_kernel + k_mm_check
 //         a row with ratio <= tol is FROZEN: its x, ratio and correction
@@ -36,15 +36,6 @@ namespace ipmz {
 namespace {
 
 constexpr int MM_NT = 256;
-
-// two consecutive doubles, zero where masked (ok1 implies ok0); branch-free,
-// a fully masked lane loads the always-valid `safe` (trsm.hip fetch2)
-__device__ __forceinline__ double2 ld2(const double* p, const double* safe, bool ok0, bool ok1) {
-  double2 t = *reinterpret_cast<const double2*>(ok0 ? p : safe);
-  t.x = ok0 ? t.x : 0.0;
-  t.y = ok1 ? t.y : 0.0;
-  return t;
-}
 
 // max over the 16 lanes of a DPP row (the lanes that hold one accumulator row)
 __device__ __forceinline__ double row16_max(double v) {
@@ -97,12 +88,11 @@ __global__ __launch_bounds__(SR_NT) void sym_residual_kernel(const double* __res
     const bool live = t < nch, nn = t >= ntNT;
     const int kk = nn ? j0 + (t - ntNT) * SR_BK : t * SR_BK;
     const int k = kk + ak;
-    st.ra = ld2(X + (int64_t)ai * ldx + k, X, live && ai < M && k < N, live && ai < M && k + 1 < N);
+    st.ra = fetch16(X + (int64_t)ai * ldx + k, X, live && ai < M && k < N, N - k);
     const int row = nn ? kk + nnr : ntr, col = nn ? nnc : kk + ntc;
     // the lower triangle only: NT takes k <= j, NN k > j (col + 1 < ld: ld is even)
-    const bool rok = live && row < N;
-    st.rb = ld2(K + (int64_t)row * ld + col, K, rok && (nn ? col < row : col <= row),
-                rok && (nn ? col + 1 < row : col + 1 <= row));
+    const int cend = nn ? row : row + 1;
+    st.rb = fetch16(K + (int64_t)row * ld + col, K, live && row < N && col < cend, cend - col);
   };
   auto store = [&](const ResStage& st, int t, double* as, double* bs) {
     *reinterpret_cast<double2*>(&as[soffNT]) = st.ra;
@@ -294,7 +284,8 @@ hipError_t mixed_solve_multi(const double* K, int64_t ld, const MixedWs& w, cons
   hipError_t e;
   hipLaunchKernelGGL(k_mm_begin, gv, bt, 0, st, N, nrhs, B, ldb, w.s, m.x, m.ldx, m.r32, m.ld32, m.done, m.stat);
   for (int pass = 0; pass <= max_refine; ++pass) {
-    if ((e = ldlt_solve_multi(w.K32, w.ld32, N, w.D32, w.Linv32, m.r32, m.ld32, nrhs, pw, st)) != hipSuccess) return e;
+    if ((e = ldlt_solve_multi(w.K32, w.ld32, N, w.D32, w.Linv32, 64, m.r32, m.ld32, nrhs, pw, st)) != hipSuccess)
+      return e;
     hipLaunchKernelGGL(k_mm_accum, gv, bt, 0, st, N, nrhs, w.s, m.r32, m.ld32, m.x, m.ldx, m.done);
     if ((e = launch_residual(K, ld, N, m.x, m.ldx, B, ldb, nullptr, 0, nrhs, w.s, m.r32, m.ld32, m.part, m.done,
                              st)) != hipSuccess)

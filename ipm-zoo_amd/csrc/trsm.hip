@@ -1,17 +1,20 @@
 // Multi-right-hand-side solve with the LDL^T factor: every row of B (one
 // right-hand side per row, stride ldb) becomes x = L^{-T} D^{-1} L^{-1} b
-// (LinearSolvers.cpp:44-74 applied to each row), i.e. B <- B K^{-1}.
+// (LinearSolvers.cpp:44-74 applied to each row), i.e. B <- B K^{-1}.  One
+// template for the fp64 factor and for the fp32 factor of the mixed-precision
+// path (mixed.hip, mixed_multi.hip).
 //
 // Blocked, right-looking over column panels of width w (a multiple of the
-// factor's inner block nbi), everything on v_mfma_f64_16x16x4_f64:
+// factor's inner block nbi), everything on v_mfma_f64_16x16x4_f64 /
+// v_mfma_f32_16x16x4_f32:
 //
 //   forward, panels ascending:
-//     panel solve  Y[:, P] = B[:, P] L_PP^{-T}        (trsm_panel_kernel<false>)
-//     update       B[:, p1:] -= Y[:, P] L[p1:, P]^T   (trsm_update_kernel<false>, NT)
+//     panel solve  Y[:, P] = B[:, P] L_PP^{-T}        (trsm_panel_kernel<.., false>)
+//     update       B[:, p1:] -= Y[:, P] L[p1:, P]^T   (trsm_update_kernel<T, false>, NT)
 //   B[:, j] /= D[j]                                   (trsm_scale_kernel)
 //   backward, panels descending:
-//     panel solve  X[:, P] = Z[:, P] L_PP^{-1}        (trsm_panel_kernel<true>)
-//     update       B[:, :p0] -= X[:, P] L[P, :p0]     (trsm_update_kernel<true>, NN)
+//     panel solve  X[:, P] = Z[:, P] L_PP^{-1}        (trsm_panel_kernel<.., true>)
+//     update       B[:, :p0] -= X[:, P] L[P, :p0]     (trsm_update_kernel<T, true>, NN)
 //
 // The panel solve walks the panel's diagonal blocks J with the inverted
 // diagonal blocks the factor left (Linv, nbi x nbi each, identity-padded):
@@ -25,8 +28,23 @@
 //
 // L is only read strictly below the diagonal blocks (the diagonal blocks go
 // through Linv), with row-contiguous 16-byte loads staged through LDS; an L
-// tile is shared by all right-hand-side rows of its workgroup.  Needs even
-// ld / ldb, 16-byte aligned K / B and K allocated as N rows of ld elements.
+// tile is shared by all right-hand-side rows of its workgroup.  A 16-byte
+// load carries V = 2 doubles or 4 floats (Mfma<T>::V): column offsets, k
+// offsets and every leading dimension are multiples of V, K and B 16-byte
+// aligned and K allocated as N rows of ld elements.
+//
+// What the element type changes besides V:
+//   * the accumulator holds rows (lane >> 4) + 4 r in fp64 and 4 (lane >> 4) + r
+//     in fp32 (Mfma<T>::row);
+//   * the LDS row pads are one vector.  A fragment read has lanes (c = lane &
+//     15, q = lane >> 4) at c * stride + q ([n][k] stages, the slab, T) or
+//     q * stride + c ([k][n] stages).  In fp32 (64 banks of 4 bytes) c * 36 mod
+//     64 runs over the 16 multiples of 4 and q fills the gaps; q * 80 mod 64 =
+//     16 q.  So [n][k] rows are BK + V elements (slab w + V, T nbi + V) and
+//     [k][n] rows 64 + 16 in both types, all multiples of V for the 16-byte
+//     stores;
+//   * the fp32 factor's inner block is always 64, a compile-time constant of
+//     its panel solve (PanelNbi).
 #include "common.h"
 #include "kernels.h"
 
@@ -38,61 +56,59 @@ constexpr int TM_NT = 256;                 // threads: 4 waves
 constexpr int TM_G = 16;                   // right-hand sides per panel-solve workgroup (the MFMA M)
 constexpr int TM_SB = 64;                  // columns per sub-block: 4 waves x one 16-column tile
 constexpr int TM_BK = 32;                  // k-depth of one staged L tile
-constexpr int TM_PADK = TM_BK + 2;         // NT stage [n][k]: row stride (conflict-free fragment reads)
-constexpr int TM_PADN = TM_SB + 16;        // NN stage [k][n]: row stride (k rows 32 banks apart)
-constexpr int TM_STAGE = TM_BK * TM_PADN;  // doubles per stage buffer
-static_assert(TM_STAGE >= TM_SB * TM_PADK, "stage buffer holds either form");
+constexpr int TM_PADN = TM_SB + 16;        // NN stage [k][n]: row stride (k rows 32 banks apart in fp64)
+constexpr int TM_STAGE = TM_BK * TM_PADN;  // elements per stage buffer
+constexpr int TM_PD = 4;  // L chunks in flight (a register ring): hides the load latency of the product chain
+// NT stage [n][k]: row stride (conflict-free fragment reads)
+template <typename T>
+constexpr int TM_PADK = TM_BK + Mfma<T>::V;
+static_assert(TM_STAGE >= TM_SB * TM_PADK<float>, "stage buffer holds either form");
 
-// Two consecutive doubles, zero where masked (ok1 implies ok0).  Branch-free,
-// so that the loads of a register ring stay in flight behind counted waits
-// (a branch around a load makes the compiler drain every load at the join):
-// a fully masked lane loads the always-valid, 16-byte aligned `safe` instead
-// and discards it.  p is 16-byte aligned whenever ok0 (even leading
-// dimensions, even column offsets); with ok0 && !ok1 the discarded second
-// element is the row's pad element (even ld / ldb) or Linv's identity padding.
-__device__ __forceinline__ double2 fetch2(const double* p, const double* safe, bool ok0, bool ok1) {
-  double2 t = *reinterpret_cast<const double2*>(ok0 ? p : safe);
-  t.x = ok0 ? t.x : 0.0;
-  t.y = ok1 ? t.y : 0.0;
-  return t;
-}
+// The inner block as a template parameter of the panel solve: 0 = the
+// run-time nbi (fp64: 64 or 128).  The fp32 factor's is the constant 64 = one
+// sub-block, which folds the sub-block index away (66 VGPRs and no spills
+// against 118-120 and up to 27 SGPR spills with a run-time nbi).
+template <typename T>
+constexpr int PanelNbi = std::is_same<T, float>::value ? TM_SB : 0;
 
 // One 64 (n) x TM_BK (k) tile of the operator Op[k][n], global -> registers
 // -> LDS.  NT: Op[k][n] = M[n * ldm + k] (rows n contiguous along k), NN:
 // Op[k][n] = M[k * ldm + n] (rows k contiguous along n); n < nlim, k < kd,
 // zero outside.
-template <bool NN>
+template <typename T, bool NN>
 struct OpStage {
-  static constexpr int Q = TM_SB * TM_BK / 2 / TM_NT;  // double2 per thread
-  double2 r[Q];
-  __device__ __forceinline__ void load(const double* __restrict__ M, int64_t ldm, int nlim, int kd, int kk) {
+  typedef typename Mfma<T>::vec16_t vec_t;
+  static constexpr int V = Mfma<T>::V, Q = TM_SB * TM_BK / V / TM_NT;  // vectors per thread
+  vec_t r[Q];
+  __device__ __forceinline__ void load(const T* __restrict__ M, int64_t ldm, int nlim, int kd, int kk) {
 #pragma unroll
     for (int q = 0; q < Q; ++q) {
       const int ch = threadIdx.x + TM_NT * q;
       if (NN) {
-        const int k = kk + ch / (TM_SB / 2), n = (ch % (TM_SB / 2)) * 2;
-        r[q] = fetch2(M + (int64_t)k * ldm + n, M, k < kd && n < nlim, k < kd && n + 1 < nlim);
+        const int k = kk + ch / (TM_SB / V), n = (ch % (TM_SB / V)) * V;
+        r[q] = fetch16(M + (int64_t)k * ldm + n, M, k < kd && n < nlim, nlim - n);
       } else {
-        const int n = ch / (TM_BK / 2), k = kk + (ch % (TM_BK / 2)) * 2;
-        r[q] = fetch2(M + (int64_t)n * ldm + k, M, n < nlim && k < kd, n < nlim && k + 1 < kd);
+        const int n = ch / (TM_BK / V), k = kk + (ch % (TM_BK / V)) * V;
+        r[q] = fetch16(M + (int64_t)n * ldm + k, M, n < nlim && k < kd, kd - k);
       }
     }
   }
-  __device__ __forceinline__ void store(double* Ls) const {
+  __device__ __forceinline__ void store(T* Ls) const {
 #pragma unroll
     for (int q = 0; q < Q; ++q) {
       const int ch = threadIdx.x + TM_NT * q;
-      const int off = NN ? (ch / (TM_SB / 2)) * TM_PADN + (ch % (TM_SB / 2)) * 2
-                         : (ch / (TM_BK / 2)) * TM_PADK + (ch % (TM_BK / 2)) * 2;
-      *reinterpret_cast<double2*>(&Ls[off]) = r[q];
+      const int off = NN ? (ch / (TM_SB / V)) * TM_PADN + (ch % (TM_SB / V)) * V
+                         : (ch / (TM_BK / V)) * TM_PADK<T> + (ch % (TM_BK / V)) * V;
+      *reinterpret_cast<vec_t*>(&Ls[off]) = r[q];
     }
   }
 };
 
 // dynamic LDS of the panel solve: the 16 x w slab of B, T of one diagonal
-// block, two stage buffers
+// block, two stage buffers (fp32: 57.9 KB at w = 512; fp64: up to 90 KB)
+template <typename T>
 inline size_t panel_lds_bytes(int w, int nbi) {
-  return (size_t)(TM_G * (w + 2) + TM_G * (nbi + 2) + 2 * TM_STAGE) * sizeof(double);
+  return (size_t)(TM_G * (w + Mfma<T>::V) + TM_G * (nbi + Mfma<T>::V) + 2 * TM_STAGE) * sizeof(T);
 }
 
 // The panel solve as a stream of products acc (16 x 64) = A (16 x kd, LDS) *
@@ -101,22 +117,24 @@ inline size_t panel_lds_bytes(int w, int nbi) {
 // (forward) / block column (backward) of J, phase 1 T times Linv_J.  Where the
 // operands are depends only on (J, phase, u), never on data, so the L chunks
 // of later products are loaded while earlier ones are still multiplied.
+template <typename T>
 struct PanelGeom {
-  const double* K;
+  const T* K;
   int64_t ld;
   int N;
-  const double* Linv;
+  const T* Linv;
   int nbi, p0, p1, SP, TP;
 };
+template <typename T>
 struct Prod {
-  const double* M;  // Op's first element
+  const T* M;  // Op's first element
   int64_t ldm;
-  int nlim, kd;  // valid columns (of 64) and depth
+  int nlim, kd;   // valid columns (of 64) and depth
   int aofs, lda;  // A: offset and row stride in the slab (phase 0) or in T (phase 1)
 };
-template <bool BWD>
-__device__ __forceinline__ Prod panel_prod(const PanelGeom& g, int j0, int phase, int u) {
-  Prod p;
+template <typename T, bool BWD>
+__device__ __forceinline__ Prod<T> panel_prod(const PanelGeom<T>& g, int j0, int phase, int u) {
+  Prod<T> p;
   const int bj = g.N - j0 < g.nbi ? g.N - j0 : g.nbi;
   const int ko = TM_SB * u;
   if (phase == 0) {
@@ -135,7 +153,7 @@ __device__ __forceinline__ Prod panel_prod(const PanelGeom& g, int j0, int phase
       p.aofs = 0;
     }
   } else {
-    const double* LinvJ = g.Linv + (int64_t)(j0 / g.nbi) * g.nbi * g.nbi;
+    const T* LinvJ = g.Linv + (int64_t)(j0 / g.nbi) * g.nbi * g.nbi;
     p.nlim = bj - ko < TM_SB ? bj - ko : TM_SB;
     p.ldm = g.nbi;
     p.lda = g.TP;
@@ -152,18 +170,20 @@ __device__ __forceinline__ Prod panel_prod(const PanelGeom& g, int j0, int phase
   return p;
 }
 // position in the stream: chunk t of product (j0, phase, u)
+template <typename T>
 struct Cursor {
   int j0, phase, u, t, nch;
   bool valid;
-  Prod p;
+  Prod<T> p;
 };
-template <bool BWD>
-__device__ __forceinline__ void cursor_next(const PanelGeom& g, Cursor& c) {
+// NBI: the panel kernel's; a constant inner block is one sub-block, and u stays 0
+template <typename T, int NBI, bool BWD>
+__device__ __forceinline__ void cursor_next(const PanelGeom<T>& g, Cursor<T>& c) {
   if (++c.t < c.nch) return;
   c.t = 0;
   for (;;) {
     const int bj = g.N - c.j0 < g.nbi ? g.N - c.j0 : g.nbi;
-    if (++c.u >= (bj + TM_SB - 1) / TM_SB) {
+    if (NBI == TM_SB || ++c.u >= (bj + TM_SB - 1) / TM_SB) {
       c.u = 0;
       if (++c.phase > 1) {
         c.phase = 0;
@@ -174,120 +194,127 @@ __device__ __forceinline__ void cursor_next(const PanelGeom& g, Cursor& c) {
         }
       }
     }
-    c.p = panel_prod<BWD>(g, c.j0, c.phase, c.u);
+    c.p = panel_prod<T, BWD>(g, c.j0, c.phase, c.u);
     c.nch = (c.p.kd + TM_BK - 1) / TM_BK;
     if (c.nch > 0) return;  // (only the first block's phase 0 is empty, and the stream starts after it)
   }
 }
-
-constexpr int TM_PD = 4;  // L chunks in flight (a register ring): hides the load latency of the product chain
 
 // Panel solve of columns [p0, min(p0 + w, N)) for right-hand sides
 // [16 * blockIdx.x, +16): the slab lives in LDS from the first load to the
 // last store.  One barrier per chunk: chunk c is written to LDS buffer c & 1,
 // the barrier passed, the ring slot refilled with chunk c + TM_PD, chunk c
 // multiplied; a product's result is written (T, or the slab) right after its
-// last chunk, one barrier before anything reads it.
-template <bool BWD>
-__global__ __launch_bounds__(TM_NT) void trsm_panel_kernel(const double* __restrict__ K, int64_t ld, int N,
-                                                           const double* __restrict__ Linv, int nbi, double* B,
-                                                           int64_t ldb, int nrhs, int p0, int w) {
-  extern __shared__ __attribute__((aligned(16))) double trsm_sm[];
-  const int SP = w + 2, TP = nbi + 2;
-  double* slab = trsm_sm;         // [16][SP]: B[:, P], overwritten block by block with the solution
-  double* Ts = slab + TM_G * SP;  // [16][TP]: T of the current diagonal block
-  double* Ls = Ts + TM_G * TP;    // [2][TM_STAGE]
+// last chunk, one barrier before anything reads it.  NBI: the inner block as a
+// constant, or 0 for nbi_rt.
+template <typename T, int NBI, bool BWD>
+__global__ __launch_bounds__(TM_NT) void trsm_panel_kernel(const T* __restrict__ K, int64_t ld, int N,
+                                                           const T* __restrict__ Linv, int nbi_rt, T* B, int64_t ldb,
+                                                           int nrhs, int p0, int w) {
+  typedef typename Mfma<T>::vec16_t vec_t;
+  typedef typename Mfma<T>::acc_t acc_t;
+  constexpr int V = Mfma<T>::V, PADK = TM_PADK<T>;
+  static_assert(NBI == 0 || NBI == TM_SB, "a constant inner block is one sub-block");
+  extern __shared__ __attribute__((aligned(16))) unsigned char trsm_sm[];
+  const int nbi = NBI ? NBI : nbi_rt;
+  const int SP = w + V, TP = nbi + V;
+  T* slab = reinterpret_cast<T*>(trsm_sm);  // [16][SP]: B[:, P], overwritten block by block with the solution
+  T* Ts = slab + TM_G * SP;                 // [16][TP]: T of the current diagonal block
+  T* Ls = Ts + TM_G * TP;                   // [2][TM_STAGE]
   const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
   const int r0 = blockIdx.x * TM_G;
   const int p1 = p0 + w < N ? p0 + w : N;
-  const int hw = w / 2;
-  const PanelGeom g = {K, ld, N, Linv, nbi, p0, p1, SP, TP};
+  const int vw = w / V;
+  const PanelGeom<T> g = {K, ld, N, Linv, nbi, p0, p1, SP, TP};
 
   // the stream starts at phase 1 of the first block (its phase 0 is empty: T = B[:, J])
   const int jfirst = BWD ? p0 + ((p1 - p0 - 1) / nbi) * nbi : p0;
-  Cursor cc;
+  Cursor<T> cc;
   cc.j0 = jfirst;
   cc.phase = 1;
   cc.u = 0;
   cc.t = 0;
   cc.valid = true;
-  cc.p = panel_prod<BWD>(g, jfirst, 1, 0);
+  cc.p = panel_prod<T, BWD>(g, jfirst, 1, 0);
   cc.nch = (cc.p.kd + TM_BK - 1) / TM_BK;
-  Cursor lc = cc;
-  OpStage<BWD> ring[TM_PD];
+  Cursor<T> lc = cc;
+  OpStage<T, BWD> ring[TM_PD];
   // (past the end of the stream the ring still loads -- all lanes masked, the
   // product's first element -- and never branches around a load: only then
   // does the compiler keep the later slots in flight behind counted waits)
 #pragma unroll
   for (int d = 0; d < TM_PD; ++d) {
     ring[d].load(lc.p.M, lc.p.ldm, lc.valid ? lc.p.nlim : 0, lc.p.kd, lc.t * TM_BK);
-    if (lc.valid) cursor_next<BWD>(g, lc);
+    if (lc.valid) cursor_next<T, NBI, BWD>(g, lc);
   }
 
-  for (int idx = tid; idx < TM_G * hw; idx += TM_NT) {
-    const int r = idx / hw, c = (idx % hw) * 2;
+  for (int idx = tid; idx < TM_G * vw; idx += TM_NT) {
+    const int r = idx / vw, c = (idx % vw) * V;
     const bool rok = r0 + r < nrhs;
-    const double2 v = fetch2(B + (int64_t)(r0 + r) * ldb + p0 + c, B + (int64_t)r0 * ldb + p0, rok && p0 + c < p1,
-                             rok && p0 + c + 1 < p1);
-    *reinterpret_cast<double2*>(&slab[r * SP + c]) = v;
+    const vec_t v = fetch16(B + (int64_t)(r0 + r) * ldb + p0 + c, B + (int64_t)r0 * ldb + p0, rok && p0 + c < p1,
+                            p1 - p0 - c);
+    *reinterpret_cast<vec_t*>(&slab[r * SP + c]) = v;
   }
   __syncthreads();
   for (int idx = tid; idx < TM_G * TP; idx += TM_NT) {
     const int r = idx / TP, c = idx % TP;
-    Ts[idx] = c < nbi ? slab[r * SP + (jfirst - p0) + c] : 0.0;
+    Ts[idx] = c < nbi ? slab[r * SP + (jfirst - p0) + c] : T(0);
   }
 
   const int col = 16 * wave + (lane & 15);  // this lane's column inside a sub-block
-  const int frag = BWD ? (lane >> 4) * TM_PADN + col : col * TM_PADK + (lane >> 4);
-  double4_t acc = {0.0, 0.0, 0.0, 0.0};
+  const int frag = BWD ? (lane >> 4) * TM_PADN + col : col * PADK + (lane >> 4);
+  acc_t acc = {T(0), T(0), T(0), T(0)};
   int buf = 0;
   for (;;) {
 #pragma unroll
     for (int d = 0; d < TM_PD; ++d) {
       if (!cc.valid) goto done;
-      double* bs = Ls + buf * TM_STAGE;
+      T* bs = Ls + buf * TM_STAGE;
       ring[d].store(bs);
       __syncthreads();
       ring[d].load(lc.p.M, lc.p.ldm, lc.valid ? lc.p.nlim : 0, lc.p.kd, lc.t * TM_BK);
-      if (lc.valid) cursor_next<BWD>(g, lc);
-      const double* As = (cc.phase == 0 ? slab : Ts) + cc.p.aofs + (lane & 15) * cc.p.lda + (lane >> 4) + cc.t * TM_BK;
+      if (lc.valid) cursor_next<T, NBI, BWD>(g, lc);
+      const T* As = (cc.phase == 0 ? slab : Ts) + cc.p.aofs + (lane & 15) * cc.p.lda + (lane >> 4) + cc.t * TM_BK;
 #pragma unroll
       for (int s = 0; s < TM_BK / 4; ++s)
-        acc = mfma_f64_16x16x4(As[4 * s], bs[frag + (BWD ? 4 * s * TM_PADN : 4 * s)], acc);
+        acc = Mfma<T>::mma(As[4 * s], bs[frag + (BWD ? 4 * s * TM_PADN : 4 * s)], acc);
       if (cc.t == cc.nch - 1) {
         const int so = cc.j0 - p0 + TM_SB * cc.u + col;  // slab column
 #pragma unroll
         for (int r = 0; r < 4; ++r) {
-          const int row = (lane >> 4) + 4 * r;
+          const int row = Mfma<T>::row(lane, r);
           if (cc.phase == 0) Ts[row * TP + TM_SB * cc.u + col] = slab[row * SP + so] - acc[r];
           else slab[row * SP + so] = acc[r];
         }
-        acc = (double4_t){0.0, 0.0, 0.0, 0.0};
+        acc = (acc_t){T(0), T(0), T(0), T(0)};
       }
-      cursor_next<BWD>(g, cc);
+      cursor_next<T, NBI, BWD>(g, cc);
       buf ^= 1;
     }
   }
 done:
   __syncthreads();
 
-  for (int idx = tid; idx < TM_G * hw; idx += TM_NT) {
-    const int r = idx / hw, c = (idx % hw) * 2;
+  for (int idx = tid; idx < TM_G * vw; idx += TM_NT) {
+    const int r = idx / vw, c = (idx % vw) * V;
     if (r0 + r >= nrhs || p0 + c >= p1) continue;
-    double* dst = B + (int64_t)(r0 + r) * ldb + p0 + c;
-    if (p0 + c + 1 < p1) *reinterpret_cast<double2*>(dst) = *reinterpret_cast<const double2*>(&slab[r * SP + c]);
-    else dst[0] = slab[r * SP + c];
+    T* dst = B + (int64_t)(r0 + r) * ldb + p0 + c;
+    const T* src = &slab[r * SP + c];
+    if (p0 + c + V - 1 < p1) *reinterpret_cast<vec_t*>(dst) = *reinterpret_cast<const vec_t*>(src);
+    else
+      for (int e = 0; p0 + c + e < p1; ++e) dst[e] = src[e];
   }
 }
 
 // between the sweeps: B[r][j] /= D[j] (a division, LinearSolvers.cpp:62-64)
-__global__ __launch_bounds__(TM_NT) void trsm_scale_kernel(double* B, int64_t ldb, int nrhs, int N,
-                                                           const double* __restrict__ D) {
+template <typename T>
+__global__ __launch_bounds__(TM_NT) void trsm_scale_kernel(T* B, int64_t ldb, int nrhs, int N,
+                                                           const T* __restrict__ D) {
   const int j = blockIdx.x * TM_NT + threadIdx.x;
   if (j >= N) return;
-  const double d = D[j];
+  const T d = D[j];
   for (int r = blockIdx.y; r < nrhs; r += gridDim.y) {
-    double* p = B + (int64_t)r * ldb + j;
+    T* p = B + (int64_t)r * ldb + j;
     *p = *p / d;
   }
 }
@@ -297,72 +324,62 @@ __global__ __launch_bounds__(TM_NT) void trsm_scale_kernel(double* B, int64_t ld
 //   forward  (NT)  Op[k][j] = L[j * ldl + k]: B[:, p1:] -= Y[:, P] L[p1:, P]^T
 //   backward (NN)  Op[k][j] = L[k * ldl + j]: B[:, :p0] -= X[:, P] L[P, :p0]
 // 64 x 64 tile, 8 waves in 2 x 4 (32 x 16 each: two waves per SIMD, so one
-// wave's LDS reads and barrier wait run under the other's MFMAs), 16-deep
-// k-chunks through two LDS buffers with one barrier per chunk as gemm.h's NT
-// engine does, but UN_PD chunks in flight in a register ring: Kd is only one
-// panel deep, so a tile is a short serial chain and nothing else hides its
+// wave's LDS reads and barrier wait run under the other's MFMAs), k-chunks of
+// one vector of X and one of L per thread (8 V: 16 deep in fp64, 32 in fp32)
+// through two LDS buffers with one barrier per chunk as gemm.h's NT engine
+// does, but UN_PD chunks in flight in a register ring: Kd is only one panel
+// deep, so a tile is a short serial chain and nothing else hides its
 // latencies.  The L tile is staged [j][k] (NT) or [k][j] (NN).  Workgroups
 // that share an L tile (the right-hand-side groups of one column tile) have
 // consecutive ids.
-constexpr int UN_NT = 512, UN_BM = 64, UN_BN = 64, UN_BK = 16, UN_PADA = UN_BK + 2, UN_PADB = UN_BN + 16, UN_PD = 3;
-constexpr int UN_BSTAGE = UN_BK * UN_PADB;
-static_assert(UN_BSTAGE >= UN_BN * UN_PADA, "B stage buffer holds either form");
+constexpr int UN_NT = 512, UN_BM = 64, UN_BN = 64, UN_PADB = UN_BN + 16, UN_PD = 3;
+template <typename T>
 struct UpdStage {
-  static constexpr int QA = UN_BM * UN_BK / 2 / UN_NT, QB = UN_BK * UN_BN / 2 / UN_NT;
-  static_assert(QA * UN_NT * 2 == UN_BM * UN_BK && QB * UN_NT * 2 == UN_BK * UN_BN, "whole double2 chunks per thread");
-  double2 ra[QA], rb[QB];
+  typename Mfma<T>::vec16_t ra, rb;
 };
-template <bool NN>
-__global__ __launch_bounds__(UN_NT) void trsm_update_kernel(const double* X, int64_t ldx, const double* __restrict__ L,
-                                                            int64_t ldl, double* C, int64_t ldc, int M, int Nc, int Kd,
+template <typename T, bool NN>
+__global__ __launch_bounds__(UN_NT) void trsm_update_kernel(const T* X, int64_t ldx, const T* __restrict__ L,
+                                                            int64_t ldl, T* C, int64_t ldc, int M, int Nc, int Kd,
                                                             int ntm) {
-  __shared__ __attribute__((aligned(16))) double As[2][UN_BM * UN_PADA];
-  __shared__ __attribute__((aligned(16))) double Bs[2][UN_BSTAGE];
+  typedef typename Mfma<T>::vec16_t vec_t;
+  typedef typename Mfma<T>::acc_t acc_t;
+  constexpr int V = Mfma<T>::V, BK = 8 * V, PADA = BK + V, BSTAGE = BK * UN_PADB;
+  static_assert(BSTAGE >= UN_BN * PADA, "B stage buffer holds either form");
+  static_assert(UN_BM * BK / V == UN_NT && BK * UN_BN / V == UN_NT, "one vector of each operand per thread");
+  __shared__ __attribute__((aligned(16))) T As[2][UN_BM * PADA];
+  __shared__ __attribute__((aligned(16))) T Bs[2][BSTAGE];
   const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
   const int wr = wave >> 2, wc = wave & 3;
   const int i0 = (blockIdx.x % ntm) * UN_BM, j0 = (blockIdx.x / ntm) * UN_BN;
-  auto load = [&](UpdStage& st, int kk) {
-#pragma unroll
-    for (int q = 0; q < UpdStage::QA; ++q) {
-      const int ch = tid + UN_NT * q, i = i0 + ch / (UN_BK / 2), k = kk + (ch % (UN_BK / 2)) * 2;
-      st.ra[q] = fetch2(X + (int64_t)i * ldx + k, X, i < M && k < Kd, i < M && k + 1 < Kd);
+  auto load = [&](UpdStage<T>& st, int kk) {
+    {
+      const int i = i0 + tid / (BK / V), k = kk + (tid % (BK / V)) * V;
+      st.ra = fetch16(X + (int64_t)i * ldx + k, X, i < M && k < Kd, Kd - k);
     }
-#pragma unroll
-    for (int q = 0; q < UpdStage::QB; ++q) {
-      const int ch = tid + UN_NT * q;
-      if (NN) {
-        const int k = kk + ch / (UN_BN / 2), j = j0 + (ch % (UN_BN / 2)) * 2;
-        st.rb[q] = fetch2(L + (int64_t)k * ldl + j, L, k < Kd && j < Nc, k < Kd && j + 1 < Nc);
-      } else {
-        const int j = j0 + ch / (UN_BK / 2), k = kk + (ch % (UN_BK / 2)) * 2;
-        st.rb[q] = fetch2(L + (int64_t)j * ldl + k, L, j < Nc && k < Kd, j < Nc && k + 1 < Kd);
-      }
+    if (NN) {
+      const int k = kk + tid / (UN_BN / V), j = j0 + (tid % (UN_BN / V)) * V;
+      st.rb = fetch16(L + (int64_t)k * ldl + j, L, k < Kd && j < Nc, Nc - j);
+    } else {
+      const int j = j0 + tid / (BK / V), k = kk + (tid % (BK / V)) * V;
+      st.rb = fetch16(L + (int64_t)j * ldl + k, L, j < Nc && k < Kd, Kd - k);
     }
   };
-  auto store = [&](const UpdStage& st, double* as, double* bs) {
-#pragma unroll
-    for (int q = 0; q < UpdStage::QA; ++q) {
-      const int ch = tid + UN_NT * q;
-      *reinterpret_cast<double2*>(&as[(ch / (UN_BK / 2)) * UN_PADA + (ch % (UN_BK / 2)) * 2]) = st.ra[q];
-    }
-#pragma unroll
-    for (int q = 0; q < UpdStage::QB; ++q) {
-      const int ch = tid + UN_NT * q;
-      const int off = NN ? (ch / (UN_BN / 2)) * UN_PADB + (ch % (UN_BN / 2)) * 2
-                         : (ch / (UN_BK / 2)) * UN_PADA + (ch % (UN_BK / 2)) * 2;
-      *reinterpret_cast<double2*>(&bs[off]) = st.rb[q];
-    }
+  auto store = [&](const UpdStage<T>& st, T* as, T* bs) {
+    *reinterpret_cast<vec_t*>(&as[(tid / (BK / V)) * PADA + (tid % (BK / V)) * V]) = st.ra;
+    const int off = NN ? (tid / (UN_BN / V)) * UN_PADB + (tid % (UN_BN / V)) * V
+                       : (tid / (BK / V)) * PADA + (tid % (BK / V)) * V;
+    *reinterpret_cast<vec_t*>(&bs[off]) = st.rb;
   };
-  double4_t acc[2];
+  acc_t acc[2];
 #pragma unroll
-  for (int a = 0; a < 2; ++a) acc[a] = (double4_t){0.0, 0.0, 0.0, 0.0};
-  const int nch = (Kd + UN_BK - 1) / UN_BK;
-  UpdStage ring[UN_PD];
+  for (int a = 0; a < 2; ++a) acc[a] = (acc_t){T(0), T(0), T(0), T(0)};
+  const int nch = (Kd + BK - 1) / BK;
+  UpdStage<T> ring[UN_PD];
   // (loads past Kd are fully masked, never branched around: see trsm_panel_kernel)
 #pragma unroll
-  for (int d = 0; d < UN_PD; ++d) load(ring[d], d * UN_BK);
-  const int aoff = (wr * 32 + (lane & 15)) * UN_PADA + (lane >> 4);
-  const int boff = NN ? (lane >> 4) * UN_PADB + wc * 16 + (lane & 15) : (wc * 16 + (lane & 15)) * UN_PADA + (lane >> 4);
+  for (int d = 0; d < UN_PD; ++d) load(ring[d], d * BK);
+  const int aoff = (wr * 32 + (lane & 15)) * PADA + (lane >> 4);
+  const int boff = NN ? (lane >> 4) * UN_PADB + wc * 16 + (lane & 15) : (wc * 16 + (lane & 15)) * PADA + (lane >> 4);
   for (int t0 = 0;; t0 += UN_PD) {
 #pragma unroll
     for (int d = 0; d < UN_PD; ++d) {
@@ -371,14 +388,14 @@ __global__ __launch_bounds__(UN_NT) void trsm_update_kernel(const double* X, int
       const int cur = t & 1;
       store(ring[d], As[cur], Bs[cur]);
       __syncthreads();
-      load(ring[d], (t + UN_PD) * UN_BK);
-      const double* as = As[cur];
-      const double* bs = Bs[cur];
+      load(ring[d], (t + UN_PD) * BK);
+      const T* as = As[cur];
+      const T* bs = Bs[cur];
 #pragma unroll
-      for (int s = 0; s < UN_BK / 4; ++s) {
-        const double bf = bs[boff + (NN ? 4 * s * UN_PADB : 4 * s)];
+      for (int s = 0; s < BK / 4; ++s) {
+        const T bf = bs[boff + (NN ? 4 * s * UN_PADB : 4 * s)];
 #pragma unroll
-        for (int a = 0; a < 2; ++a) acc[a] = mfma_f64_16x16x4(as[aoff + a * 16 * UN_PADA + 4 * s], bf, acc[a]);
+        for (int a = 0; a < 2; ++a) acc[a] = Mfma<T>::mma(as[aoff + a * 16 * PADA + 4 * s], bf, acc[a]);
       }
     }
   }
@@ -388,64 +405,75 @@ done:
   for (int a = 0; a < 2; ++a)
 #pragma unroll
     for (int r = 0; r < 4; ++r) {
-      const int i = i0 + wr * 32 + a * 16 + (lane >> 4) + 4 * r;
+      const int i = i0 + wr * 32 + a * 16 + Mfma<T>::row(lane, r);
       if (i < M && j < Nc) {
-        double* cp = C + (int64_t)i * ldc + j;
+        T* cp = C + (int64_t)i * ldc + j;
         *cp = *cp - acc[a][r];
       }
     }
 }
 
-template <bool NN>
-hipError_t launch_update(const double* X, int64_t ldx, const double* L, int64_t ldl, double* C, int64_t ldc, int M,
-                         int Nc, int Kd, hipStream_t st) {
+template <typename T, bool NN>
+hipError_t launch_update(const T* X, int64_t ldx, const T* L, int64_t ldl, T* C, int64_t ldc, int M, int Nc, int Kd,
+                         hipStream_t st) {
   const int ntm = (M + UN_BM - 1) / UN_BM, ntn = (Nc + UN_BN - 1) / UN_BN;
-  hipLaunchKernelGGL((trsm_update_kernel<NN>), dim3((unsigned)(ntm * ntn)), dim3(UN_NT), 0, st, X, ldx, L, ldl, C, ldc,
-                     M, Nc, Kd, ntm);
+  hipLaunchKernelGGL((trsm_update_kernel<T, NN>), dim3((unsigned)(ntm * ntn)), dim3(UN_NT), 0, st, X, ldx, L, ldl, C,
+                     ldc, M, Nc, Kd, ntm);
   return hipGetLastError();
 }
 
-template <bool BWD>
-hipError_t launch_panel(const double* K, int64_t ld, int N, const double* Linv, int nbi, double* B, int64_t ldb,
-                        int nrhs, int p0, int w, hipStream_t st) {
-  // more than the 64 KB a kernel gets by default: raised once per process
-  static const hipError_t attr =
-      hipFuncSetAttribute(reinterpret_cast<const void*>(&trsm_panel_kernel<BWD>),
-                          hipFuncAttributeMaxDynamicSharedMemorySize, (int)panel_lds_bytes(IPMZ_TRSM_PANEL_MAX, 128));
+template <typename T, bool BWD>
+hipError_t launch_panel(const T* K, int64_t ld, int N, const T* Linv, int nbi, T* B, int64_t ldb, int nrhs, int p0,
+                        int w, hipStream_t st) {
+  constexpr int NBI = PanelNbi<T>;
+  // fp64: more than the 64 KB a kernel gets by default; raised once per process
+  static const hipError_t attr = hipFuncSetAttribute(
+      reinterpret_cast<const void*>(&trsm_panel_kernel<T, NBI, BWD>), hipFuncAttributeMaxDynamicSharedMemorySize,
+      (int)panel_lds_bytes<T>(IPMZ_TRSM_PANEL_MAX, NBI ? NBI : 128));
   if (attr != hipSuccess) return attr;
-  hipLaunchKernelGGL((trsm_panel_kernel<BWD>), dim3((nrhs + TM_G - 1) / TM_G), dim3(TM_NT), panel_lds_bytes(w, nbi),
-                     st, K, ld, N, Linv, nbi, B, ldb, nrhs, p0, w);
+  hipLaunchKernelGGL((trsm_panel_kernel<T, NBI, BWD>), dim3((nrhs + TM_G - 1) / TM_G), dim3(TM_NT),
+                     panel_lds_bytes<T>(w, nbi), st, K, ld, N, Linv, nbi, B, ldb, nrhs, p0, w);
   return hipGetLastError();
 }
 
 }  // namespace
 
-hipError_t ldlt_solve_multi(const double* K, int64_t ld, int N, const double* D, const double* Linv, int nbi,
-                            double* B, int64_t ldb, int nrhs, int w, hipStream_t st) {
+template <typename T>
+hipError_t ldlt_solve_multi(const T* K, int64_t ld, int N, const T* D, const T* Linv, int nbi, T* B, int64_t ldb,
+                            int nrhs, int w, hipStream_t st) {
   if (N <= 0 || nrhs <= 0) return hipSuccess;
-  if ((nbi != 64 && nbi != 128) || w < nbi || w % 128 != 0 || w > IPMZ_TRSM_PANEL_MAX || (ld & 1) || (ldb & 1) ||
-      ld < N || ldb < N || ((uintptr_t)K & 15) || ((uintptr_t)B & 15))
+  // fp32: the mixed factor (nbi = 64, rows of whole 64-column blocks); leading dimensions in whole vectors
+  const bool ok = std::is_same<T, float>::value
+                      ? nbi == 64 && !(ld & 63) && !(ldb & 3) && !((uintptr_t)Linv & 15)
+                      : (nbi == 64 || nbi == 128) && !(ld & 1) && !(ldb & 1);
+  if (!ok || w < nbi || w % 128 != 0 || w > IPMZ_TRSM_PANEL_MAX || ld < N || ldb < N || ((uintptr_t)K & 15) ||
+      ((uintptr_t)B & 15))
     return hipErrorInvalidValue;
   hipError_t e;
   for (int p0 = 0; p0 < N; p0 += w) {
     const int p1 = p0 + w < N ? p0 + w : N;
-    if ((e = launch_panel<false>(K, ld, N, Linv, nbi, B, ldb, nrhs, p0, w, st)) != hipSuccess) return e;
+    if ((e = launch_panel<T, false>(K, ld, N, Linv, nbi, B, ldb, nrhs, p0, w, st)) != hipSuccess) return e;
     if (p1 < N &&  // B[:, p1:] -= Y[:, P] L[p1:, P]^T
-        (e = launch_update<false>(B + p0, ldb, K + (int64_t)p1 * ld + p0, ld, B + p1, ldb, nrhs, N - p1, p1 - p0,
-                                  st)) != hipSuccess)
+        (e = launch_update<T, false>(B + p0, ldb, K + (int64_t)p1 * ld + p0, ld, B + p1, ldb, nrhs, N - p1, p1 - p0,
+                                     st)) != hipSuccess)
       return e;
   }
-  hipLaunchKernelGGL(trsm_scale_kernel, dim3((N + TM_NT - 1) / TM_NT, nrhs < 64 ? nrhs : 64), dim3(TM_NT), 0, st, B,
-                     ldb, nrhs, N, D);
+  hipLaunchKernelGGL(trsm_scale_kernel<T>, dim3((N + TM_NT - 1) / TM_NT, nrhs < 64 ? nrhs : 64), dim3(TM_NT), 0, st,
+                     B, ldb, nrhs, N, D);
   if ((e = hipGetLastError()) != hipSuccess) return e;
   for (int p0 = ((N - 1) / w) * w; p0 >= 0; p0 -= w) {
     const int p1 = p0 + w < N ? p0 + w : N;
-    if ((e = launch_panel<true>(K, ld, N, Linv, nbi, B, ldb, nrhs, p0, w, st)) != hipSuccess) return e;
+    if ((e = launch_panel<T, true>(K, ld, N, Linv, nbi, B, ldb, nrhs, p0, w, st)) != hipSuccess) return e;
     if (p0 > 0 &&  // B[:, :p0] -= X[:, P] L[P, :p0]
-        (e = launch_update<true>(B + p0, ldb, K + (int64_t)p0 * ld, ld, B, ldb, nrhs, p0, p1 - p0, st)) != hipSuccess)
+        (e = launch_update<T, true>(B + p0, ldb, K + (int64_t)p0 * ld, ld, B, ldb, nrhs, p0, p1 - p0, st)) !=
+            hipSuccess)
       return e;
   }
   return hipSuccess;
 }
+template hipError_t ldlt_solve_multi<double>(const double*, int64_t, int, const double*, const double*, int, double*,
+                                             int64_t, int, int, hipStream_t);
+template hipError_t ldlt_solve_multi<float>(const float*, int64_t, int, const float*, const float*, int, float*,
+                                            int64_t, int, int, hipStream_t);
 
 }  // namespace ipmz

@@ -104,9 +104,11 @@ def _solve_sequence(ctx, K, rhs, H):
     try:
         for group in (rhs[:3], rhs[3:]):
             Kd = torch.from_numpy(np.tril(K)).cuda()
+            torch.cuda.synchronize()  # torch's stream filled ws, D and Kd; the context runs on its own
             assert ctx.ldlt_factor(N, Kd.data_ptr(), N, D.data_ptr(), ws.data_ptr(), wsb) == 0
             for b in group:
                 x = torch.from_numpy(b.copy()).cuda()
+                torch.cuda.synchronize()
                 ctx.ldlt_solve(N, Kd.data_ptr(), N, D.data_ptr(), ws.data_ptr(), x.data_ptr())
                 ctx.sync()
                 out.append(x.cpu().numpy())
@@ -135,8 +137,10 @@ def _mixed(ctx, K, b, H):
     ws = torch.zeros(wsb // 8 + 1, dtype=torch.float64, device="cuda")
     I.debug_inject(MASK[H])
     try:
+        torch.cuda.synchronize()  # torch's stream filled ws and Kd; the context runs on its own
         assert ctx.mixed_factor(N, Kd.data_ptr(), N, ws.data_ptr(), wsb) == 0
         x = torch.from_numpy(b.copy()).cuda()
+        torch.cuda.synchronize()
         ctx.mixed_solve(N, Kd.data_ptr(), N, ws.data_ptr(), x.data_ptr(), 1e-30, 0)
         torch.cuda.synchronize()
     finally:
