@@ -839,25 +839,20 @@ struct Meta {
 };
 inline Meta layout(char* base, int n) {
   Meta m;
-  size_t off = 0;
-  auto take = [&](size_t bytes) {
-    char* p = base ? base + off : nullptr;
-    off += (bytes + 255) / 256 * 256;
-    return p;
-  };
-  m.flag = reinterpret_cast<unsigned*>(take(256));
-  m.kind = reinterpret_cast<int*>(take((size_t)n * 4));
-  m.perm = reinterpret_cast<int*>(take((size_t)n * 4));
-  m.srow = reinterpret_cast<int*>(take((size_t)n * 4));
-  m.sa = reinterpret_cast<int*>(take((size_t)n * 4));
-  m.sb = reinterpret_cast<int*>(take((size_t)n * 4));
-  m.slotpos = reinterpret_cast<int*>(take((size_t)2 * n * 4));
-  m.d11 = reinterpret_cast<double*>(take((size_t)n * 8));
-  m.d21 = reinterpret_cast<double*>(take((size_t)n * 8));
-  m.d22 = reinterpret_cast<double*>(take((size_t)n * 8));
-  m.ones = reinterpret_cast<double*>(take((size_t)n * 8));
-  m.t = reinterpret_cast<double*>(take((size_t)n * 8));
-  m.total = off;
+  Carver c{base};
+  m.flag = c.take<unsigned>(64);
+  m.kind = c.take<int>(n);
+  m.perm = c.take<int>(n);
+  m.srow = c.take<int>(n);
+  m.sa = c.take<int>(n);
+  m.sb = c.take<int>(n);
+  m.slotpos = c.take<int>(2 * (int64_t)n);
+  m.d11 = c.take<double>(n);
+  m.d21 = c.take<double>(n);
+  m.d22 = c.take<double>(n);
+  m.ones = c.take<double>(n);
+  m.t = c.take<double>(n);
+  m.total = (size_t)c.off;
   return m;
 }
 

@@ -1,0 +1,173 @@
+// What capi.cpp (contexts, workspaces, the LinearSolvers entry points) and
+// qp.cpp (the Newton-step solver object) share.  Internal to libipmz.
+#pragma once
+#include <hip/hip_runtime.h>
+
+#include <cstdint>
+#include <mutex>
+#include <string>
+#include <vector>
+
+#include "ipmz.h"
+#include "kernels.h"
+
+using namespace ipmz;
+
+// the host layer's own functions and data stay inside libipmz.so: only the
+// C ABI of ipmz.h is exported
+#pragma GCC visibility push(hidden)
+
+// sets ipmz_last_error (one thread_local string, capi.cpp) and returns code
+int fail(int code, const std::string& msg);
+int hip_fail(hipError_t e, const char* expr, const char* file, int line);
+#define HIP_OK(expr)                                                           \
+  do {                                                                         \
+    hipError_t _e = (expr);                                                    \
+    if (_e != hipSuccess) return hip_fail(_e, #expr, __FILE__, __LINE__);      \
+  } while (0)
+
+inline int64_t round_up(int64_t x, int64_t a) { return (x + a - 1) / a * a; }
+
+struct ipmz_ctx {
+  int device = 0;
+  hipStream_t own = nullptr;
+  hipStream_t stream = nullptr;
+  int nbo = 0, nbi = 64;  // nbo 0: by matrix order (nbo_for)
+  // factorization look-ahead: the panel chain on `stream` itself, panel rows
+  // on sC (high priority), trailing updates on sB, the fp32 factor's
+  // look-ahead strips on sD; forked from / joined to `stream` (ldlt_factor)
+  hipStream_t sB = nullptr, sC = nullptr, sD = nullptr;
+  std::vector<hipEvent_t> evpool;
+  // the sticky error words (spin timeouts of the persistent kernels) of the
+  // workspace the last asynchronous device-memory solve used, resolved when
+  // it was enqueued (watch): ipmz_ctx_sync checks and clears them (the caller
+  // keeps that workspace alive until then)
+  const unsigned* check_pe = nullptr;
+  const unsigned* check_se = nullptr;
+  // solvers created on this context and not yet destroyed: a context
+  // destroyed before them (e.g. a garbage collector finalizing both in either
+  // order) is only marked, and freed with the last of them.  Both fields are
+  // read and written only under g_ctx_mutex (ctypes drops the GIL around
+  // every call, and finalizers run on any thread).
+  int users = 0;
+  bool closed = false;
+};
+extern std::mutex g_ctx_mutex;
+void ctx_free(ipmz_ctx* ctx);
+
+// outer panel width for an order-N factor: the context's, or by size --
+// 512 for N > 4096 (kbench factor, N = 11264: 12.95 ms at 384, 12.34 at
+// 512; N = 16384: 32.1 -> 31.2 ms), 384 for 2048 <= N <= 4096 (C2, N = 2560,
+// chain-bound: 679-689 steps/s at 512, 711-718 at 384 in round 5,
+// profiles/r05_s/c2_nbo_ab.txt; 256: 675), 256 below.  Every workspace
+// layout and every factor / solve of an order-N matrix uses this same value.
+inline int nbo_for(const ipmz_ctx* ctx, int N) {
+  if (ctx->nbo > 0) return ctx->nbo;
+  if (ctx->nbi != 64 || N < 2048) return 256;
+  return N <= 4096 ? 384 : 512;
+}
+
+// Workspaces (DESIGN.md "Workspaces") -----------------------------------------
+// The fp64 LDL^T factor + solve of one order-N matrix.  W is triple-buffered
+// (look-ahead); y, z, ctrl are the persistent solve's state, P its per-block
+// operators (nbi 64 only: nbi 128 solves by the block-step kernel chain and
+// has no such region).  Sticky error words: pctrl[PANEL_ERR_WORD],
+// ctrl[SOLVE_ERR_WORD].
+struct LdltWs {
+  int* info = nullptr;  // first non-finite pivot (256 B)
+  unsigned* pctrl = nullptr;
+  double *side = nullptr, *Linv = nullptr, *W = nullptr, *y = nullptr, *z = nullptr;
+  unsigned* ctrl = nullptr;  // (256 B)
+  double* P = nullptr;
+  int64_t total = 0;
+};
+inline LdltWs ldlt_ws(char* base, int N, int nbo, int nbi) {
+  LdltWs w;
+  Carver c{base};
+  w.info = c.take<int>(64);
+  w.pctrl = c.take<unsigned>(panel_ctrl_words(N, nbo));
+  w.side = c.take<double>(2 * nbi);
+  w.Linv = c.take<double>((int64_t)((N + nbi - 1) / nbi) * nbi * nbi);
+  w.W = c.take<double>(3 * (int64_t)N * nbo);
+  w.y = c.take<double>(solve_vec_elems(N));
+  w.z = c.take<double>(solve_vec_elems(N));
+  w.ctrl = c.take<unsigned>(64);
+  if (nbi == 64) w.P = c.take<double>(solve_prep_elems(N));
+  w.total = c.off;
+  return w;
+}
+// The normal equations: the definiteness info word (256 B), then the order
+// N = n + mp LDL^T
+struct NormalWs {
+  int* info = nullptr;
+  LdltWs k;
+  int64_t total = 0;
+};
+inline NormalWs normal_ws(char* base, int N, int nbo, int nbi) {
+  NormalWs w;
+  Carver c{base};
+  w.info = c.take<int>(64);
+  w.k = ldlt_ws(base ? base + c.off : nullptr, N, nbo, nbi);
+  w.total = c.off + w.k.total;
+  return w;
+}
+// The device-wide Bunch-Kaufman solve (bk.hip bk_fast_*): the persistent
+// triangular solve's operators for L' (64 x 64 inverse diagonal blocks, the
+// 128-row-block prep), its y / x vectors and ctrl words (sticky error word
+// ctrl[SOLVE_ERR_WORD]), and the interchange bookkeeping (meta)
+struct BkWs {
+  double *Linv = nullptr, *P = nullptr, *y = nullptr, *x = nullptr;
+  unsigned* ctrl = nullptr;
+  char* meta = nullptr;
+  int64_t total = 0;
+};
+inline BkWs bk_ws(char* base, int N) {
+  BkWs w;
+  Carver c{base};
+  w.Linv = c.take<double>((int64_t)((N + 63) / 64) * 64 * 64);
+  w.P = c.take<double>(solve_prep_elems(N));
+  w.y = c.take<double>(solve_vec_elems(N));
+  w.x = c.take<double>(solve_vec_elems(N));
+  w.ctrl = c.take<unsigned>(64);
+  w.meta = c.take<char>((int64_t)bk_fast_meta_bytes(N));
+  w.total = c.off;
+  return w;
+}
+
+// the workspace whose sticky error words the next ipmz_ctx_sync checks
+inline void watch(ipmz_ctx* ctx, const LdltWs& w) {
+  ctx->check_pe = w.pctrl + PANEL_ERR_WORD;
+  ctx->check_se = w.ctrl + SOLVE_ERR_WORD;
+}
+inline void unwatch(ipmz_ctx* ctx) { ctx->check_pe = ctx->check_se = nullptr; }
+
+// capi.cpp --------------------------------------------------------------------
+// One batch of copies and one synchronize: the sticky error words pe (panel
+// factor) and se (persistent solve), then the info word; each may be null.
+// A raised error word is IPMZ_ERR_HIP (never success: the results are
+// invalid), reported before info, as what + pe_text or what + se_text (the
+// two timeout sentences, or a caller's own wording).  Returns info, IPMZ_OK
+// when it is unset.
+extern const char PANEL_TIMEOUT[], SOLVE_TIMEOUT[];
+int ws_result(hipStream_t st, const int* info, const unsigned* pe, const unsigned* se, const char* what,
+              const char* pe_text = PANEL_TIMEOUT, const char* se_text = SOLVE_TIMEOUT);
+int read_info(ipmz_ctx* ctx, const LdltWs& w);  // ws_result of a factor's whole workspace
+// info2: a caller's own info word, reset in the same launch
+int factor_impl(ipmz_ctx* ctx, int N, double* K, int64_t ld, double* D, const LdltWs& w, int nbo, TrailTimer* timer,
+                int* info2 = nullptr);
+hipError_t solve_ws(const double* K, int64_t ld, int N, const double* D, const LdltWs& w, int nbi, double* b,
+                    hipStream_t st);
+int mixed_factor_impl(ipmz_ctx* ctx, const double* K, int64_t ld, MixedWs& w, TrailTimer* timer);
+int mixed_multi_impl(ipmz_ctx* ctx, const double* K, int64_t ld, MixedWs& w, const MixedMultiWs& m, double* B,
+                     int64_t ldb, int nrhs, double tol, int max_refine, double* stat);
+int not_capturing(ipmz_ctx* ctx, const char* who);
+int normal_factor_impl(ipmz_ctx* ctx, int n, int mp, double* K, int64_t ld, double* D, const NormalWs& w, int nbo,
+                       TrailTimer* timer);
+int normal_solve_impl(ipmz_ctx* ctx, int n, int mp, const double* K, int64_t ld, const double* D, const NormalWs& w,
+                      double* b);
+hipError_t bk_setup(const double* F, int64_t ld, int N, const int* ipiv, const int* info, double* LT, double* Lp,
+                    int64_t ldp, const BkWs& w, hipStream_t st);
+hipError_t bk_run(const double* Lp, int64_t ldp, int N, const double* LT, const int* ipiv, const BkWs& w, double* b,
+                  hipStream_t st);
+
+#pragma GCC visibility pop

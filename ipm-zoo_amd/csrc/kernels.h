@@ -72,6 +72,20 @@ void set_debug_inject_mask(int mask);
 constexpr int PANEL_ERR_WORD = 2;
 constexpr int SOLVE_ERR_WORD = 1;
 
+// Host-side carving of one allocation into a workspace's members, in call
+// order, each aligned to 256 bytes.  base == nullptr: sizes only (every take
+// returns nullptr, off still advances to the total).
+struct Carver {
+  char* base;
+  int64_t off = 0;
+  template <typename T>
+  T* take(int64_t count) {  // count elements of T
+    char* p = base ? base + off : nullptr;
+    off += (count * (int64_t)sizeof(T) + 255) / 256 * 256;
+    return reinterpret_cast<T*>(p);
+  }
+};
+
 // ldlt.hip -------------------------------------------------------------------
 // Batched factorization: element strides between consecutive QPs' K, D,
 // L^{-1} blocks and W panels.

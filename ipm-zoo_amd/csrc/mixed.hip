@@ -223,34 +223,29 @@ int64_t mixed_ws_bytes(int N, int nbo) {
 
 int64_t mixed_ws_carve(char* base, int N, int nbo, MixedWs& w) {
   const int64_t nblk = (N + 63) / 64;
-  int64_t off = 0;
-  auto take = [&](int64_t bytes) {
-    char* p = base ? base + off : nullptr;
-    off += (bytes + 255) / 256 * 256;
-    return p;
-  };
+  Carver c{base};
   w.N = N;
   w.nbo = nbo;
   w.ld32 = (N + 63) / 64 * 64;
-  w.K32 = reinterpret_cast<float*>(take((int64_t)N * w.ld32 * 4));
-  w.D32 = reinterpret_cast<float*>(take((int64_t)N * 4));
-  w.Linv32 = reinterpret_cast<float*>(take(nblk * 64 * 64 * 4));
-  w.W32 = reinterpret_cast<float*>(take(3 * (int64_t)N * nbo * 4));
-  w.y32 = reinterpret_cast<float*>(take(solve_vec_elems(N) * 4));
-  w.z32 = reinterpret_cast<float*>(take(solve_vec_elems(N) * 4));
-  w.r32 = reinterpret_cast<float*>(take((int64_t)N * 4));
-  w.ctrl = reinterpret_cast<unsigned*>(take(IPMZ_SOLVE_CTRL_WORDS * 4));
-  w.P32 = reinterpret_cast<float*>(take(solve_prep_elems(N) * 4));
-  w.state = reinterpret_cast<unsigned*>(take(64));
-  w.info = reinterpret_cast<int*>(take(64));
-  w.pctrl = reinterpret_cast<unsigned*>(take(panel_ctrl_words(N, nbo) * 4));
-  w.s = reinterpret_cast<double*>(take((int64_t)N * 8));
-  w.x = reinterpret_cast<double*>(take((int64_t)N * 8));
-  w.colp = reinterpret_cast<double*>(take(nblk * N * 8));
-  w.rowp = reinterpret_cast<double*>(take((int64_t)NSPLIT * N * 8));
-  w.part = reinterpret_cast<double*>(take(2 * ((N + 63) / 64) * 8));
-  w.stat = reinterpret_cast<double*>(take(64));
-  return off;
+  w.K32 = c.take<float>((int64_t)N * w.ld32);
+  w.D32 = c.take<float>(N);
+  w.Linv32 = c.take<float>(nblk * 64 * 64);
+  w.W32 = c.take<float>(3 * (int64_t)N * nbo);
+  w.y32 = c.take<float>(solve_vec_elems(N));
+  w.z32 = c.take<float>(solve_vec_elems(N));
+  w.r32 = c.take<float>(N);
+  w.ctrl = c.take<unsigned>(IPMZ_SOLVE_CTRL_WORDS);
+  w.P32 = c.take<float>(solve_prep_elems(N));
+  w.state = c.take<unsigned>(16);
+  w.info = c.take<int>(16);
+  w.pctrl = c.take<unsigned>(panel_ctrl_words(N, nbo));
+  w.s = c.take<double>(N);
+  w.x = c.take<double>(N);
+  w.colp = c.take<double>(nblk * N);
+  w.rowp = c.take<double>((int64_t)NSPLIT * N);
+  w.part = c.take<double>(2 * ((N + 63) / 64));
+  w.stat = c.take<double>(8);
+  return c.off;
 }
 
 hipError_t mixed_factor(const double* K, int64_t ld, MixedWs& w, hipStream_t st, hipStream_t st2, hipStream_t st3,

@@ -249,22 +249,17 @@ hipError_t launch_residual(const double* K, int64_t ld, int N, const double* X, 
 }  // namespace
 
 int64_t mixed_multi_ws_carve(char* base, int N, int nrhs, MixedMultiWs& m) {
-  int64_t off = 0;
-  auto take = [&](int64_t bytes) {
-    char* p = base ? base + off : nullptr;
-    off += (bytes + 255) / 256 * 256;
-    return p;
-  };
+  Carver c{base};
   m.ldx = (N + 1) / 2 * 2;
   m.ld32 = (N + 63) / 64 * 64;
   m.ntiles = (N + SR_BN - 1) / SR_BN;
-  m.x = reinterpret_cast<double*>(take((int64_t)nrhs * m.ldx * 8));
-  m.r32 = reinterpret_cast<float*>(take((int64_t)nrhs * m.ld32 * 4));
-  m.part = reinterpret_cast<double*>(take((int64_t)nrhs * m.ntiles * 2 * 8));
-  m.stat = reinterpret_cast<double*>(take((int64_t)nrhs * 2 * 8));
-  m.done = reinterpret_cast<unsigned*>(take((int64_t)nrhs * 4));
-  m.word = reinterpret_cast<unsigned*>(take(64));
-  return off;
+  m.x = c.take<double>((int64_t)nrhs * m.ldx);
+  m.r32 = c.take<float>((int64_t)nrhs * m.ld32);
+  m.part = c.take<double>((int64_t)nrhs * m.ntiles * 2);
+  m.stat = c.take<double>((int64_t)nrhs * 2);
+  m.done = c.take<unsigned>(nrhs);
+  m.word = c.take<unsigned>(16);
+  return c.off;
 }
 
 hipError_t sym_residual_multi(const double* K, int64_t ld, int N, const double* X, int64_t ldx, const double* B,

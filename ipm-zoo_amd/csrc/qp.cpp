@@ -1,0 +1,1179 @@
+// C ABI of libipmz (include/ipmz.h), second half: the Newton-step solver
+// object ipmz_qp on the contexts, workspaces and factor / solve paths of
+// capi.cpp (shared through capi.h).
+//
+// Newton-step solver: B QPs with identical dimensions (B = 1 for ipmz_qp_*).
+// Every per-QP array lives in one allocation with a per-QP stride; the
+// kernels take a device array of QPDev descriptors and index it with
+// blockIdx.y, so one launch serves the whole batch.
+#include <algorithm>
+
+#include "capi.h"
+
+struct ipmz_qp {
+  ipmz_ctx* ctx = nullptr;
+  int n = 0, m = 0, p = 0, N = 0, B = 1;
+  int64_t ldn = 0, ldk = 0, state_len = 0;
+  double delta = 1e-4;
+  std::vector<void*> allocs;
+  bool alloc_failed = false;  // sticky: a dev_alloc failed (create_solver checks it once)
+  std::vector<QPDev> hq;   // host copies of the descriptors
+  QPDev* dq = nullptr;     // device array of B descriptors
+  QPBatch qb{};
+  // factor storage
+  double *K = nullptr, *D = nullptr;
+  int64_t sK = 0, sD = 0, sb = 0;
+  // batches of small systems (fused phases, LDL^T): the assembled KKT kept
+  // across steps (off-diagonal part written once per data load, the diagonal
+  // every step); the small factor reads it and writes L to K (strides sK)
+  double* K0 = nullptr;
+  char* ws = nullptr;      // B == 1: ldlt_ws(N); B > 1: bLinv, bW, binfo below
+  int64_t ws_bytes = 0;
+  double *bLinv = nullptr, *bW = nullptr;  // batched factor workspace (B > 1)
+  int* binfo = nullptr;
+  int64_t sL = 0, sW = 0;
+  bool loaded = false;
+  // mixed precision (C5): fp32 factor of S K S + fp64 refinement
+  bool mixed = false;
+  double ir_tol = 1e-12;
+  int ir_max = 10;
+  MixedWs mw;
+  char* mws = nullptr;
+  // ipmz_qp_kkt_solve_mixed: the multi-right-hand-side workspace, for the largest nrhs seen
+  char* mmws = nullptr;
+  int mmws_nrhs = 0;
+  // normal-equations reduction (C2)
+  bool normal = false;
+  // EqualityHandling::None: Bunch-Kaufman factor (pivots per QP)
+  bool eqnone = false;
+  char* bkws = nullptr;  // the whole-device Bunch-Kaufman factor's workspace (B == 1, N >= IPMZ_BK_GRID_MIN)
+  double* bklt = nullptr;  // its factor transposed (N x N): the interchange folding's input, the fallback's factor
+  char* bkfws = nullptr;   // the device-wide solve's workspace (bk_ws), L' in K
+  unsigned* pflags = nullptr;  // B > 1: the two-workgroup small factor's flags + sticky error word
+  int small_kernel = IPMZ_BATCH_FACTOR_AUTO;  // ipmz_batch_set_factor_kernel
+  bool eqpen = false;  // EqualityHandling::PenaltyFunction (LDL^T)
+  // InequalityHandling / Bounds (which Newton slots exist)
+  bool slacks = false, naive = false;
+  // EqualityHandling::SlackedSlacks: m, p below are the step's (m + p equality
+  // rows run as l = u = d inequalities, p = 0); m_usr, p_usr the data's
+  bool eqss = false;
+  int m_usr = 0, p_usr = 0;
+  bool vlo = true, vup = true, alo = true, aup = true;
+  int* ipiv = nullptr;
+  int64_t sP = 0;
+  char* nws = nullptr;
+  hipGraph_t graph = nullptr;
+  hipGraphExec_t gexec = nullptr;
+  int graph_flags = -1;
+  // timing
+  bool timing = false;
+  std::vector<hipEvent_t> ev;  // phase boundary events
+  hipEvent_t (*tr_pairs)[2] = nullptr;
+  // completion of the last multi-stream (eager) step: the next one is not
+  // enqueued before it (queue depth 1, see step_impl)
+  hipEvent_t step_done = nullptr;
+  hipEvent_t step_in = nullptr;  // the caller's stream reached the step (the fork onto ctx->own)
+  bool step_pending = false;
+  int last_step_graph = 0;  // the last ipmz_qp_step replayed a captured hipGraph
+  int tr_cap = 0;
+  double ph_ms[IPMZ_PH_COUNT] = {0};
+  double tr_flops = 0.0;
+  int64_t tr_launches = 0;
+};
+
+namespace {
+// Newton variables present per formulation (SymbolicOptimization.cpp
+// get_variables_: absent blocks are dropped from the Newton order)
+int64_t slot_len(const ipmz_qp* s, int slot) {
+  switch (slot) {
+    case X: return s->n;
+    case LY: return s->vlo ? s->n : 0;
+    case LZ: return s->vup ? s->n : 0;
+    case Y: return (s->vlo && !s->slacks) ? s->n : 0;
+    case Z: return (s->vup && !s->slacks) ? s->n : 0;
+    case LA: case S: return s->naive ? 0 : s->m;
+    case LG: return s->alo ? s->m : 0;
+    case LH: return s->aup ? s->m : 0;
+    case G: return (s->alo && !s->slacks) ? s->m : 0;
+    case H: return (s->aup && !s->slacks) ? s->m : 0;
+    case P: return (s->eqnone || s->eqpen) ? 0 : s->p;
+    default: return s->p;
+  }
+}
+
+// device storage freed with the solver (allocs); a failure is recorded in
+// s->alloc_failed and every later call returns nullptr
+template <typename T>
+T* dev_alloc(ipmz_qp* s, size_t count, bool zero) {
+  void* ptr = nullptr;
+  if (s->alloc_failed || hipMalloc(&ptr, count * sizeof(T)) != hipSuccess) {
+    s->alloc_failed = true;
+    return nullptr;
+  }
+  s->allocs.push_back(ptr);
+  if (zero && hipMemset(ptr, 0, count * sizeof(T)) != hipSuccess) s->alloc_failed = true;
+  return static_cast<T*>(ptr);
+}
+// one allocation of B x stride doubles (stride = per-QP count rounded to 64 B)
+double* dev_array(ipmz_qp* s, int64_t count, int64_t* stride_out = nullptr, bool zero = false) {
+  const int64_t stride = round_up(count < 1 ? 1 : count, 8);
+  if (stride_out) *stride_out = stride;
+  return dev_alloc<double>(s, (size_t)(stride * s->B), zero);
+}
+
+void drop_graph(ipmz_qp* s) {
+  if (s->gexec) hipGraphExecDestroy(s->gexec);
+  if (s->graph) hipGraphDestroy(s->graph);
+  s->gexec = nullptr;
+  s->graph = nullptr;
+}
+
+// slot pointers into one contiguous Newton-order vector (the reference's
+// order; NaiveSlacks puts its duals lambda_g, lambda_h ahead of lambda_C,
+// formulations.txt)
+void carve(const ipmz_qp* s, double* base, double** slots) {
+  static const int naive_order[NSLOT] = {X, LG, LH, LC, P, LY, LZ, G, H, Y, Z, LA, S};
+  int64_t off = 0;
+  for (int k = 0; k < NSLOT; ++k) {
+    const int slot = s->naive ? naive_order[k] : k;
+    slots[slot] = base + off;
+    off += slot_len(s, slot);
+  }
+}
+
+QPDev& q0(ipmz_qp* s) { return s->hq[0]; }
+
+// the solver's own workspaces at the context's current blocking: s->ws
+// (B == 1, augmented LDL^T) and s->nws (normal equations, N = n + m + p)
+LdltWs ldlt_ws_of(const ipmz_qp* s) { return ldlt_ws(s->ws, s->N, nbo_for(s->ctx, s->N), s->ctx->nbi); }
+NormalWs normal_ws_of(const ipmz_qp* s) { return normal_ws(s->nws, s->N, nbo_for(s->ctx, s->N), s->ctx->nbi); }
+
+int solve_batch(ipmz_qp* s, hipStream_t st, int which) {
+  if (s->eqnone && s->bkfws) {  // overwriting_solve_bunch_kaufman, device-wide (L' in K)
+    HIP_OK(bk_run(s->K, s->ldk, s->N, s->bklt, s->ipiv, bk_ws(s->bkfws, s->N), q0(s).b, st));
+  } else if (s->eqnone && s->bklt) {  // overwriting_solve_bunch_kaufman on the transposed factor
+    HIP_OK(bk_solve_lt(s->bklt, s->N, s->ipiv, q0(s).b, st));
+  } else if (s->eqnone) {  // overwriting_solve_bunch_kaufman
+    HIP_OK(bk_solve(s->K, s->ldk, s->N, s->ipiv, q0(s).b, s->B, s->sK, s->sP, s->sb, st));
+  } else if (s->normal) {
+    return normal_solve_impl(s->ctx, s->n, s->m + s->p, s->K, s->ldk, s->D, normal_ws_of(s), q0(s).b);
+  } else if (s->mixed) {
+    HIP_OK(mixed_solve(s->K, s->ldk, s->mw, q0(s).b, s->ir_tol, s->ir_max, st));
+    HIP_OK(hipMemcpyAsync(q0(s).scal + IPMZ_SC_IR_RATIO_AFF + 2 * which, s->mw.stat, 2 * sizeof(double),
+                          hipMemcpyDeviceToDevice, st));
+  } else if (s->B == 1) {
+    HIP_OK(solve_ws(s->K, s->ldk, s->N, s->D, ldlt_ws_of(s), s->ctx->nbi, q0(s).b, st));
+  } else {
+    HIP_OK(ldlt_solve_batched(s->K, s->ldk, s->N, s->D, s->bLinv, s->ctx->nbi, q0(s).b, s->B, s->sK, s->sD, s->sL,
+                              s->sb, st));
+  }
+  return IPMZ_OK;
+}
+
+// info_reset: the caller already reset the batched factor's info word
+bool uses_k0(const ipmz_qp* s);
+int factor_batch(ipmz_qp* s, TrailTimer* tt, bool info_reset) {
+  if (s->eqnone) {  // zero diagonal block: symmetric_indefinite_factorization (reference kp behaviour)
+    if (s->bkws) {
+      HIP_OK(bk_factor_grid(s->K, s->ldk, s->N, s->ipiv, s->binfo, 0, s->bkws, s->ctx->stream));
+      HIP_OK(bk_transpose(s->K, s->ldk, s->N, s->bklt, s->ctx->stream));
+      if (s->bkfws)  // L' into K (the factor is not read again this step)
+        HIP_OK(bk_setup(s->K, s->ldk, s->N, s->ipiv, s->binfo, s->bklt, s->K, s->ldk, bk_ws(s->bkfws, s->N),
+                        s->ctx->stream));
+      return IPMZ_OK;
+    }
+    HIP_OK(bk_factor(s->K, s->ldk, s->N, s->ipiv, s->binfo, 0, s->B, s->sK, s->sP, s->ctx->stream));
+    return IPMZ_OK;
+  }
+  if (s->mixed) return mixed_factor_impl(s->ctx, s->K, s->ldk, s->mw, tt);
+  const int nbo = nbo_for(s->ctx, s->N);
+  if (s->normal)
+    return normal_factor_impl(s->ctx, s->n, s->m + s->p, s->K, s->ldk, s->D, normal_ws_of(s), nbo, tt);
+  if (s->B == 1) return factor_impl(s->ctx, s->N, s->K, s->ldk, s->D, ldlt_ws_of(s), nbo, tt);
+  BatchStrides bs;
+  bs.B = s->B;
+  bs.sK = s->sK;
+  bs.sD = s->sD;
+  bs.sL = s->sL;
+  bs.sW = s->sW;
+  bs.pflags = s->pflags;
+  bs.small_kernel = s->small_kernel;
+  bs.K0 = info_reset && uses_k0(s) ? s->K0 : nullptr;  // (info_reset: the fused step, whose pre phase assembled into K0)
+  if (!info_reset) HIP_OK(hipMemsetAsync(s->binfo, 0x7f, sizeof(int), s->ctx->stream));
+  HIP_OK(ldlt_factor_batched(s->K, s->ldk, s->N, s->D, s->bLinv, s->bW, nbo, s->ctx->nbi, s->binfo, s->ctx->stream,
+                             bs));
+  return IPMZ_OK;
+}
+
+// batches of small systems: the O(N) / O(n^2) phases as three per-QP
+// workgroup kernels (newton.hip k_fused_*)
+bool fused_phases(const ipmz_qp* s) { return s->B > 1 && s->N <= IPMZ_FUSED_NMAX; }
+// ... whose solves are the small batched solve (solve_batch's last branch,
+// nbi 64): then both solves and the phases between them run as one launch
+bool fused_solves(const ipmz_qp* s) {
+  return fused_phases(s) && !s->eqnone && !s->normal && !s->mixed && s->ctx->nbi == 64 && fused_solves_ok(s->N, s->ldk) &&
+         !(debug_inject_mask() & IPMZ_DEBUG_NO_FUSED_SOLVES);
+}
+// the fused step keeps the assembled matrix in K0 when the small batched
+// factor (nbi 64) consumes it; otherwise the whole matrix is assembled into K
+bool uses_k0(const ipmz_qp* s) {
+  return s->K0 && s->ctx->nbi == 64 && s->N <= IPMZ_SMALL_NMAX && !(debug_inject_mask() & IPMZ_DEBUG_NO_K0);
+}
+
+int run_step(ipmz_qp* s, int flags) {
+  hipStream_t st = s->ctx->stream;
+  const QPBatch& qb = s->qb;
+  const bool t = s->timing;
+  auto mark = [&](int i) {
+    IPMZ_TRACE("step: phase mark %d", i);
+    if (t) hipEventRecord(s->ev[i], st);
+  };
+  const bool restart = flags & IPMZ_STEP_RESTART_IF_CONVERGED;
+  const int freeze = restart ? 0 : 1;
+  const bool fused = fused_phases(s);
+  TrailTimer tt;
+  tt.pairs = s->tr_pairs;
+  tt.cap = t ? s->tr_cap : 0;
+  int rc;
+  if (fused) {
+    // phases: assemble = pre (restart, assembly, affine rhs); factor;
+    // solve = the two solves; eval = mid + post
+    mark(0);
+    HIP_OK(qp_fused_pre(qb, restart ? 1 : 0, s->eqnone ? nullptr : s->binfo, st, uses_k0(s) ? KMODE_K0_DIAG : KMODE_K));
+    mark(1);
+    if ((rc = factor_batch(s, nullptr, true))) return rc;
+    mark(2);
+    if (fused_solves(s)) {
+      // both solves and the phases between them in one launch (the solve
+      // phase then holds mid and post too; eval = the evaluation alone)
+      HIP_OK(qp_fused_solves(qb, s->K, s->ldk, s->N, s->D, s->bLinv, q0(s).b, s->sK, s->sD, s->sL, s->sb, freeze, st));
+      mark(3);
+      mark(4);
+      mark(5);
+      HIP_OK(qp_fused_eval(qb, st));
+    } else {
+      if ((rc = solve_batch(s, st, 0))) return rc;
+      mark(3);
+      HIP_OK(qp_fused_mid(qb, st));
+      mark(4);
+      if ((rc = solve_batch(s, st, 1))) return rc;
+      mark(5);
+      HIP_OK(qp_fused_post(qb, freeze, st));
+    }
+    mark(6);
+    mark(7);
+  } else {
+    if (restart) HIP_OK(qp_restart_if_converged(qb, st));
+    mark(0);
+    HIP_OK(qp_assemble(qb, st));
+    mark(1);
+    if ((rc = factor_batch(s, t ? &tt : nullptr, false))) return rc;
+    mark(2);
+    // predictor (affine scaling) direction
+    HIP_OK(qp_rhs(qb, st));
+    if ((rc = solve_batch(s, st, 0))) return rc;
+    mark(3);
+    HIP_OK(qp_backsub(qb, 0, st));
+    HIP_OK(qp_ratio(qb, 0, SC_ALPHA_AFF, st));
+    HIP_OK(qp_mu_aff(qb, st));
+    // centering-corrector direction
+    HIP_OK(qp_corrector_residuals(qb, st));
+    HIP_OK(qp_rhs(qb, st));
+    mark(4);
+    if ((rc = solve_batch(s, st, 1))) return rc;
+    mark(5);
+    HIP_OK(qp_backsub(qb, 1, st));
+    HIP_OK(qp_ratio(qb, 1, SC_ALPHA, st));
+    HIP_OK(qp_update(qb, freeze, st));
+    mark(6);
+    HIP_OK(qp_evaluate(qb, st));
+    mark(7);
+  }
+  if (t) {
+    HIP_OK(hipStreamSynchronize(st));
+    float ms = 0.f;
+    auto el = [&](int a, int b) {
+      hipEventElapsedTime(&ms, s->ev[a], s->ev[b]);
+      return (double)ms;
+    };
+    s->ph_ms[IPMZ_PH_STEP] += el(0, 7);
+    s->ph_ms[IPMZ_PH_ASSEMBLE] += el(0, 1);
+    s->ph_ms[IPMZ_PH_FACTOR] += el(1, 2);
+    s->ph_ms[IPMZ_PH_SOLVE] += el(2, 3) + el(4, 5);
+    s->ph_ms[IPMZ_PH_EVAL] += fused ? el(3, 4) + el(5, 6) : el(6, 7);
+    for (int i = 0; i < tt.used; ++i) {
+      hipEventElapsedTime(&ms, s->tr_pairs[i][0], s->tr_pairs[i][1]);
+      s->ph_ms[IPMZ_PH_TRAILING] += ms;
+    }
+    s->tr_launches += tt.used;
+    s->tr_flops += tt.flops * s->B;
+  }
+  return IPMZ_OK;
+}
+
+// the data on the device just changed: a fresh iterate, evaluated and kept as
+// the restart snapshot; synchronizes
+int initialize(ipmz_qp* s) {
+  HIP_OK(hipSetDevice(s->ctx->device));
+  hipStream_t st = s->ctx->stream;
+  HIP_OK(qp_init_iterate(s->qb, st));
+  if (s->K0) HIP_OK(qp_fused_pre(s->qb, 0, nullptr, st, KMODE_K0_OFFDIAG));
+  HIP_OK(qp_evaluate(s->qb, st));
+  HIP_OK(qp_save_initial(s->qb, st));
+  s->loaded = true;
+  HIP_OK(hipStreamSynchronize(st));
+  return IPMZ_OK;
+}
+
+int create_solver(ipmz_ctx* ctx, const ipmz_qp_config* cfg, int B, ipmz_qp** out) {
+  if (!ctx || !cfg || !out) return fail(IPMZ_ERR_INVALID, "null argument");
+  *out = nullptr;
+  if (cfg->n <= 0 || cfg->m < 0 || cfg->p < 0 || B <= 0)
+    return fail(IPMZ_ERR_INVALID, "dimensions: n > 0, m >= 0, p >= 0, batch > 0");
+  if (cfg->equality_handling != IPMZ_EQ_REGULARIZATION && cfg->equality_handling != IPMZ_EQ_NONE &&
+      cfg->equality_handling != IPMZ_EQ_PENALTY && cfg->equality_handling != IPMZ_EQ_PENALTY_EXTRA_DUAL &&
+      cfg->equality_handling != IPMZ_EQ_SLACKED_SLACKS && cfg->equality_handling != IPMZ_EQ_NAIVE_SLACKS)
+    return fail(IPMZ_ERR_INVALID, "unknown equality handling");
+  const int mk = cfg->inequality_handling == IPMZ_INEQ_NAIVE_SLACKS ? 2 * cfg->m : cfg->m;
+  if (cfg->equality_handling == IPMZ_EQ_NONE && B > 1 && cfg->n + mk + cfg->p > IPMZ_BK_NMAX)
+    return fail(IPMZ_ERR_INVALID, "EqualityHandling::None in batches factors with Bunch-Kaufman one workgroup per "
+                                  "system: N <= " + std::to_string(IPMZ_BK_NMAX));
+  const int ih = cfg->inequality_handling, ib = cfg->inequality_bounds, vb = cfg->variable_bounds;
+  if (ih != IPMZ_INEQ_SLACKED_SLACKS && ih != IPMZ_INEQ_SLACKS && ih != IPMZ_INEQ_NAIVE_SLACKS)
+    return fail(IPMZ_ERR_INVALID, "unknown inequality handling");
+  if (ih == IPMZ_INEQ_NAIVE_SLACKS && cfg->m > 0 && ib != IPMZ_BOUNDS_BOTH)
+    return fail(IPMZ_ERR_INVALID, "InequalityHandling::NaiveSlacks: both inequality bounds");
+  if (cfg->equality_handling == IPMZ_EQ_NAIVE_SLACKS && (ih != IPMZ_INEQ_NAIVE_SLACKS || ib != IPMZ_BOUNDS_BOTH))
+    return fail(IPMZ_ERR_INVALID, "EqualityHandling::NaiveSlacks: with InequalityHandling::NaiveSlacks and both "
+                                  "inequality bounds");
+  if (cfg->equality_handling == IPMZ_EQ_SLACKED_SLACKS && (ih != IPMZ_INEQ_SLACKED_SLACKS || ib != IPMZ_BOUNDS_BOTH))
+    return fail(IPMZ_ERR_INVALID, "EqualityHandling::SlackedSlacks: with InequalityHandling::SlackedSlacks and both "
+                                  "inequality bounds");
+  if (ib < IPMZ_BOUNDS_BOTH || ib > IPMZ_BOUNDS_NONE || vb < IPMZ_BOUNDS_BOTH || vb > IPMZ_BOUNDS_NONE)
+    return fail(IPMZ_ERR_INVALID, "unknown bounds setting");
+  if (cfg->m > 0 && ib == IPMZ_BOUNDS_NONE)
+    return fail(IPMZ_ERR_INVALID, "inequality rows need a lower or an upper bound (inequality_bounds != NONE)");
+  if (ih == IPMZ_INEQ_SLACKS && ((cfg->m > 0 && ib != IPMZ_BOUNDS_BOTH) || vb != IPMZ_BOUNDS_BOTH))
+    return fail(IPMZ_ERR_INVALID, "InequalityHandling::Slacks is built on both bounds (the reference's Slacks "
+                                  "formulation drops one-sided bounds inconsistently)");
+  HIP_OK(hipSetDevice(ctx->device));
+  auto* s = new ipmz_qp();
+  s->ctx = ctx;
+  {
+    std::lock_guard<std::mutex> lk(g_ctx_mutex);
+    if (ctx->closed) {
+      delete s;
+      return fail(IPMZ_ERR_STATE, "context already destroyed");
+    }
+    ++ctx->users;
+  }
+  s->B = B;
+  s->n = cfg->n;
+  s->m_usr = cfg->m;
+  s->p_usr = cfg->p;
+  // equality SlackedSlacks / NaiveSlacks: the p rows appended to the
+  // inequality block of the same handling with l = u = d
+  s->eqss = cfg->equality_handling == IPMZ_EQ_SLACKED_SLACKS || cfg->equality_handling == IPMZ_EQ_NAIVE_SLACKS;
+  s->m = s->eqss ? cfg->m + cfg->p : cfg->m;
+  s->p = s->eqss ? 0 : cfg->p;
+  s->N = cfg->equality_handling == IPMZ_EQ_NAIVE_SLACKS ? cfg->n + 2 * (cfg->m + cfg->p) : cfg->n + mk + cfg->p;
+  s->delta = cfg->delta > 0 ? cfg->delta : 1e-4;
+  s->eqnone = cfg->equality_handling == IPMZ_EQ_NONE;
+  s->eqpen = cfg->equality_handling == IPMZ_EQ_PENALTY || cfg->equality_handling == IPMZ_EQ_PENALTY_EXTRA_DUAL;
+  s->slacks = ih == IPMZ_INEQ_SLACKS;
+  s->naive = ih == IPMZ_INEQ_NAIVE_SLACKS;
+  s->vlo = vb == IPMZ_BOUNDS_BOTH || vb == IPMZ_BOUNDS_LOWER;
+  s->vup = vb == IPMZ_BOUNDS_BOTH || vb == IPMZ_BOUNDS_UPPER;
+  s->alo = ib == IPMZ_BOUNDS_BOTH || ib == IPMZ_BOUNDS_LOWER;
+  s->aup = ib == IPMZ_BOUNDS_BOTH || ib == IPMZ_BOUNDS_UPPER;
+  s->ldn = round_up(s->n, 8);
+  s->ldk = round_up(s->N, 64);
+  s->state_len = 0;
+  for (int k = 0; k < NSLOT; ++k) s->state_len += slot_len(s, k);
+  const int n = s->n, m = s->m, p = s->p, N = s->N;
+  int64_t sQ, sA, sC, sn, sm, sp, sS, sNb, sScal, sPart, sT;
+  double* Q = dev_array(s, (int64_t)n * s->ldn, &sQ);
+  double* A = dev_array(s, (int64_t)m * s->ldn, &sA);
+  double* C = dev_array(s, (int64_t)p * s->ldn, &sC);  // (eqss: C is rows m_usr.. of A)
+  double* c = dev_array(s, n, &sn);
+  double* lx = dev_array(s, n);
+  double* ux = dev_array(s, n);
+  double* Qx = dev_array(s, n);
+  double* ATl = dev_array(s, n);
+  double* CTl = dev_array(s, n);
+  double* lA = dev_array(s, m, &sm);
+  double* uA = dev_array(s, m);
+  double* Ax = dev_array(s, m);
+  double* d = dev_array(s, s->p_usr, &sp);
+  double* Cx = dev_array(s, p);
+  double* v = dev_array(s, s->state_len, &sS);
+  double* r = dev_array(s, s->state_len);
+  double* da = dev_array(s, s->state_len);
+  double* di = dev_array(s, s->state_len);
+  double* v0 = dev_array(s, s->state_len);
+  double* r0 = dev_array(s, s->state_len);
+  double* bvec = dev_array(s, N, &sNb);
+  double* scal = dev_array(s, SC_COUNT, &sScal);
+  double* scal0 = dev_array(s, SC_COUNT);
+  double* part = dev_array(s, 4 * 1024, &sPart);
+  double* tpart = dev_array(s, (int64_t)((m > p ? m : p) + IPMZ_TCHUNK - 1) / IPMZ_TCHUNK * n + 8, &sT);
+  int64_t sDone;
+  double* done = dev_array(s, 1, &sDone, true);
+  s->K = dev_array(s, (int64_t)N * s->ldk, &s->sK);
+  if (B > 1 && N <= IPMZ_FUSED_NMAX && !s->eqnone) {
+    int64_t sK0 = 0;
+    s->K0 = dev_array(s, (int64_t)N * s->ldk, &sK0);
+  }
+  s->D = dev_array(s, N, &s->sD);
+  s->sb = sNb;
+  if (B == 1) {
+    s->ws_bytes = ldlt_ws(nullptr, N, nbo_for(ctx, N), ctx->nbi).total;
+    s->ws = dev_alloc<char>(s, (size_t)s->ws_bytes, true);
+  } else {
+    const int64_t nblk = (N + ctx->nbi - 1) / ctx->nbi;
+    s->bLinv = dev_array(s, nblk * ctx->nbi * ctx->nbi, &s->sL);
+    s->bW = dev_array(s, (int64_t)N * nbo_for(ctx, N), &s->sW);
+    s->binfo = dev_alloc<int>(s, B > 64 ? B : 64, false);  // one info per QP
+    // flags of the two-workgroup small factor (B <= #CU)
+    s->pflags = dev_alloc<unsigned>(s, (size_t)B * IPMZ_PAIR_FLAGS + 1, true);
+  }
+  if (s->eqnone) {
+    s->sP = round_up(N, 16);
+    s->ipiv = dev_alloc<int>(s, (size_t)(s->sP * B), false);
+    if (!s->binfo) s->binfo = dev_alloc<int>(s, 64, false);
+    if (B == 1 && N >= IPMZ_BK_GRID_MIN) {
+      s->bkws = dev_alloc<char>(s, bk_grid_ws_bytes(N), false);
+      s->bklt = dev_alloc<double>(s, (size_t)N * N, false);
+      s->bkfws = dev_alloc<char>(s, (size_t)bk_ws(nullptr, N).total, true);
+    }
+  }
+  s->dq = dev_alloc<QPDev>(s, B, false);
+  // every failure from here on leaves through ipmz_qp_destroy: it frees what
+  // was allocated and gives the context's user count back
+  auto bail = [&](int rc) {
+    ipmz_qp_destroy(s);
+    return rc;
+  };
+  if (s->alloc_failed) return bail(fail(IPMZ_ERR_NOMEM, "device allocation failed"));
+  s->hq.resize(B);
+  for (int i = 0; i < B; ++i) {
+    QPDev& q = s->hq[i];
+    q = QPDev{};
+    q.n = n;
+    q.m = m;
+    q.p = p;
+    q.N = N;
+    q.ldn = s->ldn;
+    q.ldk = s->ldk;
+    q.state_len = s->state_len;
+    q.delta = s->delta;
+    q.eqnone = s->eqnone ? 1 : 0;
+    q.eqpen = s->eqpen ? 1 : 0;
+    q.slacks = s->slacks ? 1 : 0;
+    q.naive = s->naive ? 1 : 0;
+    q.eqss = s->eqss ? 1 : 0;
+    q.m_usr = s->m_usr;
+    q.p_usr = s->p_usr;
+    q.mk = s->naive ? 2 * m : m;
+    q.vlo = s->vlo ? 1 : 0;
+    q.vup = s->vup ? 1 : 0;
+    q.alo = s->alo ? 1 : 0;
+    q.aup = s->aup ? 1 : 0;
+    q.Q = Q + i * sQ;
+    q.A = A + i * sA;
+    q.C = s->eqss ? q.A + (int64_t)s->m_usr * s->ldn : C + i * sC;
+    q.c = c + i * sn;
+    q.lx = lx + i * sn;
+    q.ux = ux + i * sn;
+    q.Qx = Qx + i * sn;
+    q.ATl = ATl + i * sn;
+    q.CTl = CTl + i * sn;
+    q.lA = lA + i * sm;
+    q.uA = uA + i * sm;
+    q.Ax = Ax + i * sm;
+    q.d = d + i * sp;
+    q.Cx = Cx + i * sp;
+    carve(s, v + i * sS, q.v);
+    carve(s, r + i * sS, q.r);
+    carve(s, da + i * sS, q.daff);
+    carve(s, di + i * sS, q.dir);
+    q.v0 = v0 + i * sS;
+    q.r0 = r0 + i * sS;
+    q.b = bvec + i * sNb;
+    q.scal = scal + i * sScal;
+    q.scal0 = scal0 + i * sScal;
+    q.part = part + i * sPart;
+    q.tpart = tpart + i * sT;
+    q.K = s->K + i * s->sK;
+    q.K0 = s->K0 ? s->K0 + i * s->sK : nullptr;
+    q.done = reinterpret_cast<unsigned*>(done + i * sDone);
+  }
+  s->qb = QPBatch{s->dq, s->hq[0], B};
+  hipError_t e = hipMemcpy(s->dq, s->hq.data(), sizeof(QPDev) * B, hipMemcpyHostToDevice);
+  if (e == hipSuccess) e = hipMemsetAsync(scal, 0, (size_t)sScal * B * 8, ctx->stream);
+  if (e == hipSuccess) e = hipMemsetAsync(s->K, 0, (size_t)s->sK * B * 8, ctx->stream);
+  if (e == hipSuccess) e = hipStreamSynchronize(ctx->stream);
+  if (e != hipSuccess) return bail(hip_fail(e, "create_solver: descriptor upload / clear", __FILE__, __LINE__));
+  *out = s;
+  return IPMZ_OK;
+}
+
+int check_index(ipmz_qp* s, int i) {
+  if (!s || i < 0 || i >= s->B) return fail(IPMZ_ERR_INVALID, "QP index out of range");
+  return IPMZ_OK;
+}
+
+int load_one(ipmz_qp* s, int i, const double* Q, const double* c, const double* A, const double* lA, const double* uA,
+             const double* C, const double* d, const double* lx, const double* ux) {
+  if (!Q || !c || !lx || !ux || (s->m_usr && (!A || !lA || !uA)) || (s->p_usr && (!C || !d)))
+    return fail(IPMZ_ERR_INVALID, "load: missing data block");
+  // EnvironmentBuilder.cpp:12-17 (the reference ASSERTs; here an error code)
+  for (int k = 0; k < s->n; ++k)
+    if (!(lx[k] < ux[k])) return fail(IPMZ_ERR_INVALID, "l_x < u_x violated at " + std::to_string(k));
+  for (int k = 0; k < s->m_usr; ++k)
+    if (!(lA[k] <= uA[k])) return fail(IPMZ_ERR_INVALID, "l_A <= u_A violated at " + std::to_string(k));
+  HIP_OK(hipSetDevice(s->ctx->device));
+  hipStream_t st = s->ctx->stream;
+  const QPDev& q = s->hq[i];
+  const size_t rowb = (size_t)s->n * 8, ldb = (size_t)s->ldn * 8;
+  HIP_OK(hipMemcpy2DAsync((void*)q.Q, ldb, Q, rowb, rowb, s->n, hipMemcpyHostToDevice, st));
+  if (s->m_usr) HIP_OK(hipMemcpy2DAsync((void*)q.A, ldb, A, rowb, rowb, s->m_usr, hipMemcpyHostToDevice, st));
+  if (s->p_usr) HIP_OK(hipMemcpy2DAsync((void*)q.C, ldb, C, rowb, rowb, s->p_usr, hipMemcpyHostToDevice, st));
+  HIP_OK(hipMemcpyAsync((void*)q.c, c, rowb, hipMemcpyHostToDevice, st));
+  HIP_OK(hipMemcpyAsync((void*)q.lx, lx, rowb, hipMemcpyHostToDevice, st));
+  HIP_OK(hipMemcpyAsync((void*)q.ux, ux, rowb, hipMemcpyHostToDevice, st));
+  if (s->m_usr) {
+    HIP_OK(hipMemcpyAsync((void*)q.lA, lA, (size_t)s->m_usr * 8, hipMemcpyHostToDevice, st));
+    HIP_OK(hipMemcpyAsync((void*)q.uA, uA, (size_t)s->m_usr * 8, hipMemcpyHostToDevice, st));
+  }
+  if (s->p_usr) HIP_OK(hipMemcpyAsync((void*)q.d, d, (size_t)s->p_usr * 8, hipMemcpyHostToDevice, st));
+  if (s->eqss && s->p_usr) {  // the equality rows as l = u = d
+    HIP_OK(hipMemcpyAsync((void*)(q.lA + s->m_usr), d, (size_t)s->p_usr * 8, hipMemcpyHostToDevice, st));
+    HIP_OK(hipMemcpyAsync((void*)(q.uA + s->m_usr), d, (size_t)s->p_usr * 8, hipMemcpyHostToDevice, st));
+  }
+  HIP_OK(hipStreamSynchronize(st));
+  return IPMZ_OK;
+}
+
+// Does the step's factorization fork onto the look-ahead streams?  Such a
+// step is enqueued eagerly even when IPMZ_STEP_GRAPH is asked for: its graph
+// replay is slower than the eager launches (tools/graph_ab.py, profiles/r03_s3:
+// C2 2.4-3.0 vs 1.75 ms, C3 16.7 vs 14.6, C5 35.3 vs 25.7 ms per step -- the
+// replayed look-ahead loses its stream priorities and overlap), and a
+// multi-millisecond step hides its launch latency anyway.  The capture itself
+// is correct (debug bit IPMZ_INJECT_GRAPH_FORKS; tests/test_gpu_graph.py:
+// bitwise the eager step): it once crashed inside hipStreamEndCapture of the
+// HIP runtime torch bundles, fixed by ldlt.hip's stream_record / stream_wait.
+bool step_forks(const ipmz_qp* s) {
+  if (s->eqnone || s->B > 1) return false;
+  if (debug_inject_mask() & IPMZ_INJECT_GRAPH_FORKS) return false;
+  // the augmented factor and the normal equations' pipelined factor are both
+  // one factor_impl of order N (= n + m + p): it forks from 3 outer panels
+  const int nbo = nbo_for(s->ctx, s->N);
+  return (s->N + nbo - 1) / nbo >= 3;
+}
+
+int step_impl(ipmz_qp* s, int flags) {
+  if (!s || !s->loaded) return fail(IPMZ_ERR_STATE, "load or generate the QP first");
+  HIP_OK(hipSetDevice(s->ctx->device));
+  s->last_step_graph = 0;
+  {
+    // The caller's stream is capturing (torch.cuda.graph around step()): the
+    // whole step goes into the caller's capture on that stream -- no hop to
+    // the own stream, no host wait, no nested capture (the look-ahead
+    // streams order through capture dependencies, ldlt.hip stream_wait; the
+    // mixed solve enqueues all its passes, mixed.hip)
+    hipStreamCaptureStatus cs = hipStreamCaptureStatusNone;
+    HIP_OK(hipStreamIsCapturing(s->ctx->stream, &cs));
+    if (cs != hipStreamCaptureStatusNone) {
+      if (s->timing) return fail(IPMZ_ERR_STATE, "phase timing inside a caller's graph capture");
+      set_capture_origin(s->ctx->stream);
+      const int rc = run_step(s, flags & ~IPMZ_STEP_GRAPH);
+      set_capture_origin(nullptr);
+      return rc;
+    }
+  }
+  if (step_forks(s) && (!s->timing || s->ctx->stream != s->ctx->own)) {  // timing: phase events on own, below
+    // A factorization that forks onto the look-ahead streams is enqueued
+    // eagerly (~130-160 launches and event waits over four queues); with
+    // the next step's packets already queued behind it the command processor
+    // slows the running step down (C2: 3.9 vs 3.1 ms per step back to back;
+    // tools/step_sync_ab.py), so at most one such step is in flight: the host
+    // waits for the previous one before enqueuing the next.
+    if (!s->step_done) HIP_OK(hipEventCreateWithFlags(&s->step_done, hipEventDisableTiming));
+    if (s->step_pending) HIP_OK(hipEventSynchronize(s->step_done));
+    s->step_pending = false;
+    // On a stream the caller made (torch's default or side streams) the step
+    // runs on the context's own stream, forked from the caller's, and the host
+    // waits for it before the caller's stream is joined to it: a join left
+    // pending on the caller's stream while the step runs cost ~1.2 ms per C3
+    // step (15.7 vs 14.5 ms; the step on the caller's stream itself the same),
+    // profiles/r03_s5/origin_stream_ab.log.  The host would wait for the step
+    // before enqueuing the next one anyway (queue depth 1).
+    hipStream_t caller = s->ctx->stream, own = s->ctx->own;
+    const bool hop = caller != own;
+    if (hop) {
+      if (!s->step_in) HIP_OK(hipEventCreateWithFlags(&s->step_in, hipEventDisableTiming));
+      HIP_OK(hipEventRecord(s->step_in, caller));
+      HIP_OK(hipStreamWaitEvent(own, s->step_in, 0));
+      s->ctx->stream = own;
+    }
+    const int rc = run_step(s, flags);
+    s->ctx->stream = caller;
+    if (rc) return rc;
+    HIP_OK(hipEventRecord(s->step_done, own));
+    if (hop) {
+      HIP_OK(hipEventSynchronize(s->step_done));
+      HIP_OK(hipStreamWaitEvent(caller, s->step_done, 0));  // complete: orders nothing pending
+      return IPMZ_OK;
+    }
+    s->step_pending = true;
+    return IPMZ_OK;
+  }
+  if (!(flags & IPMZ_STEP_GRAPH) || s->timing) return run_step(s, flags);
+  hipStream_t st = s->ctx->stream;
+  if (!s->gexec || s->graph_flags != flags) {
+    drop_graph(s);
+    // capture on the context's own stream: the caller's stream may be the
+    // legacy default stream (torch's), which cannot be captured; the graph
+    // is then launched on the caller's stream
+    hipStream_t cap = s->ctx->own;
+    IPMZ_TRACE("capture: begin");
+    set_capture_origin(cap);  // ldlt.hip stream_wait: the look-ahead streams' ordering inside the capture
+    HIP_OK(hipStreamBeginCapture(cap, hipStreamCaptureModeThreadLocal));
+    s->ctx->stream = cap;
+    int rc = run_step(s, flags);
+    s->ctx->stream = st;
+    IPMZ_TRACE("capture: step enqueued rc=%d", rc);
+    hipGraph_t g = nullptr;
+    hipError_t e = hipStreamEndCapture(cap, &g);
+    set_capture_origin(nullptr);
+    IPMZ_TRACE("capture: ended %d", (int)e);
+    if (rc) {
+      if (g) hipGraphDestroy(g);
+      return rc;
+    }
+    if (e != hipSuccess) return fail(IPMZ_ERR_HIP, std::string("graph capture: ") + hipGetErrorString(e));
+    s->graph = g;
+    HIP_OK(hipGraphInstantiate(&s->gexec, g, nullptr, nullptr, 0));
+    IPMZ_TRACE("capture: instantiated");
+    s->graph_flags = flags;
+  }
+  HIP_OK(hipGraphLaunch(s->gexec, st));
+  IPMZ_TRACE("graph launched");
+  s->last_step_graph = 1;
+  return IPMZ_OK;
+}
+
+// sticky error words of every persistent-kernel workspace the step uses
+int qp_status(ipmz_qp* s) {
+  hipStream_t st = s->ctx->stream;
+  if (s->mixed) {
+    const char* text = ": a hand-off inside a persistent kernel of the mixed-precision factor / solve timed out; the "
+                       "step is invalid";
+    return ws_result(st, nullptr, s->mw.pctrl + PANEL_ERR_WORD, s->mw.ctrl + SOLVE_ERR_WORD, "Newton step", text, text);
+  }
+  if (s->normal || (s->B == 1 && !s->eqnone)) {
+    const LdltWs w = s->normal ? normal_ws_of(s).k : ldlt_ws_of(s);
+    return ws_result(st, nullptr, w.pctrl + PANEL_ERR_WORD, w.ctrl + SOLVE_ERR_WORD,
+                     s->normal ? "Newton step (normal equations)" : "Newton step");
+  }
+  // only a step whose factor ran the two-workgroup kernel has a word to read
+  // (that kernel's launch zeroes it; the default wave-specialized factor at
+  // C4's N = 320 has no cross-workgroup hand-off and needs no sync here)
+  if (!s->eqnone && s->ctx->nbi == 64 && small_pair_used(s->small_kernel, s->pflags != nullptr, s->B, s->N))
+    return ws_result(st, nullptr, s->pflags + (size_t)s->B * IPMZ_PAIR_FLAGS, nullptr, "Newton step",
+                     ": a hand-off of the two-workgroup batched factor timed out; the step is invalid");
+  if (s->bkws)  // (the device-wide solve's word only where that solve runs)
+    return ws_result(st, nullptr, bk_grid_err_word(s->bkws, s->N),
+                     s->bkfws ? bk_ws(s->bkfws, s->N).ctrl + SOLVE_ERR_WORD : nullptr, "Newton step",
+                     ": a grid barrier of the whole-device Bunch-Kaufman factor timed out; the step is invalid",
+                     ": a hand-off inside the persistent triangular solve of the Bunch-Kaufman factor timed out; the "
+                     "step is invalid");
+  return IPMZ_OK;  // batched / one-workgroup Bunch-Kaufman kernels have no cross-workgroup spins
+}
+
+int scalars_impl(ipmz_qp* s, double* out, int count) {
+  HIP_OK(hipSetDevice(s->ctx->device));
+  // the B scalar blocks are one allocation with a stride: one 2-D copy
+  const size_t pitch = (s->B > 1 ? (s->hq[1].scal - s->hq[0].scal) : SC_COUNT) * 8;
+  HIP_OK(hipMemcpy2DAsync(out, SC_COUNT * 8, s->hq[0].scal, pitch, SC_COUNT * 8, count, hipMemcpyDeviceToHost,
+                          s->ctx->stream));
+  HIP_OK(hipStreamSynchronize(s->ctx->stream));
+  return s->loaded ? qp_status(s) : IPMZ_OK;
+}
+
+// EqualityHandling::SlackedSlacks / NaiveSlacks: the step's slots hold [lambda_g lambda_v],
+// [lambda_h lambda_w], [g v], [h w]; the reference's Newton order is
+// lambda_g, lambda_h, lambda_v, lambda_w, ..., g, h, v, w (formulations.txt).
+// perm[k] = the step-vector index of reference-order element k.
+std::vector<int64_t> eqss_perm(const ipmz_qp* s) {
+  const int64_t n = s->n, m = s->m_usr, p = s->p_usr, mp = m + p;
+  const int64_t ny = s->vlo ? n : 0, nz = s->vup ? n : 0;
+  std::vector<int64_t> perm;
+  perm.reserve((size_t)s->state_len);
+  auto run = [&](int64_t from, int64_t len) {
+    for (int64_t k = 0; k < len; ++k) perm.push_back(from + k);
+  };
+  // x, [lambda_A lambda_C], [s t] (SlackedSlacks) or x alone (NaiveSlacks, no
+  // s / lambda_A): same order
+  int64_t off = s->naive ? n : n + 2 * mp;
+  run(0, off);
+  const int64_t LGo = off, LHo = off + mp;  // [lambda_g lambda_v], [lambda_h lambda_w]
+  run(LGo, m);
+  run(LHo, m);
+  run(LGo + m, p);
+  run(LHo + m, p);
+  off += 2 * mp;
+  run(off, ny + nz);  // lambda_y, lambda_z
+  off += ny + nz;
+  const int64_t Go = off, Ho = off + mp;  // [g v], [h w]
+  run(Go, m);
+  run(Ho, m);
+  run(Go + m, p);
+  run(Ho + m, p);
+  off += 2 * mp;
+  run(off, s->state_len - off);  // y, z
+  return perm;
+}
+
+int get_state_impl(ipmz_qp* s, int i, int which, double* out) {
+  if (which < 0 || which > 3 || !out) return fail(IPMZ_ERR_INVALID, "bad arguments");
+  HIP_OK(hipSetDevice(s->ctx->device));
+  const QPDev& q = s->hq[i];
+  const double* src = which == 0 ? q.v[0] : which == 1 ? q.daff[0] : which == 2 ? q.dir[0] : q.r[0];
+  if (s->eqss) {
+    std::vector<double> tmp((size_t)s->state_len);
+    HIP_OK(hipMemcpyAsync(tmp.data(), src, s->state_len * 8, hipMemcpyDeviceToHost, s->ctx->stream));
+    HIP_OK(hipStreamSynchronize(s->ctx->stream));
+    const auto perm = eqss_perm(s);
+    for (int64_t k = 0; k < s->state_len; ++k) out[k] = tmp[(size_t)perm[(size_t)k]];
+    return IPMZ_OK;
+  }
+  HIP_OK(hipMemcpyAsync(out, src, s->state_len * 8, hipMemcpyDeviceToHost, s->ctx->stream));
+  HIP_OK(hipStreamSynchronize(s->ctx->stream));
+  return IPMZ_OK;
+}
+
+// a host iterate in the reference's order -> the step's order
+std::vector<double> state_in(const ipmz_qp* s, const double* in) {
+  std::vector<double> v(in, in + s->state_len);
+  if (s->eqss) {
+    const auto perm = eqss_perm(s);
+    for (int64_t k = 0; k < s->state_len; ++k) v[(size_t)perm[(size_t)k]] = in[k];
+  }
+  return v;
+}
+}  // namespace
+
+extern "C" {
+
+int ipmz_qp_create(ipmz_ctx* ctx, const ipmz_qp_config* cfg, ipmz_qp** out) { return create_solver(ctx, cfg, 1, out); }
+
+int ipmz_qp_destroy(ipmz_qp* s) {
+  if (!s) return IPMZ_OK;
+  hipSetDevice(s->ctx->device);
+  hipStreamSynchronize(s->ctx->stream);
+  drop_graph(s);
+  for (auto e : s->ev) hipEventDestroy(e);
+  if (s->step_done) hipEventDestroy(s->step_done);
+  if (s->step_in) hipEventDestroy(s->step_in);
+  if (s->tr_pairs) {
+    for (int i = 0; i < s->tr_cap; ++i) {
+      hipEventDestroy(s->tr_pairs[i][0]);
+      hipEventDestroy(s->tr_pairs[i][1]);
+    }
+    delete[] s->tr_pairs;
+  }
+  for (void* p : s->allocs) hipFree(p);
+  if (s->mmws) hipFree(s->mmws);
+  if (s->mw.hev) hipEventDestroy(s->mw.hev);
+  if (s->mw.hst) hipHostFree(s->mw.hst);
+  ipmz_ctx* ctx = s->ctx;
+  delete s;
+  bool last;
+  {
+    std::lock_guard<std::mutex> lk(g_ctx_mutex);
+    last = --ctx->users == 0 && ctx->closed;
+  }
+  if (last) ctx_free(ctx);
+  return IPMZ_OK;
+}
+
+int ipmz_qp_load_host(ipmz_qp* s, const double* Q, const double* c, const double* A, const double* lA,
+                      const double* uA, const double* C, const double* d, const double* lx, const double* ux) {
+  if (!s) return fail(IPMZ_ERR_INVALID, "null qp");
+  for (int i = 0; i < s->B; ++i) {
+    int rc = load_one(s, i, Q, c, A, lA, uA, C, d, lx, ux);
+    if (rc) return rc;
+  }
+  return initialize(s);
+}
+
+int ipmz_qp_generate(ipmz_qp* s, uint64_t seed) {
+  if (!s) return fail(IPMZ_ERR_INVALID, "null qp");
+  HIP_OK(hipSetDevice(s->ctx->device));
+  HIP_OK(qp_generate(s->qb, seed, s->ctx->stream));
+  return initialize(s);
+}
+
+int ipmz_qp_step(ipmz_qp* s, int flags) { return step_impl(s, flags); }
+
+int ipmz_qp_last_step_graph(ipmz_qp* s) { return s ? s->last_step_graph : 0; }
+
+int ipmz_qp_scalars(ipmz_qp* s, double* out) {
+  if (!s || !out) return fail(IPMZ_ERR_INVALID, "null argument");
+  return scalars_impl(s, out, 1);  // QP 0 (the ipmz_qp_* accessors address QP 0)
+}
+
+int ipmz_qp_device_scalars(ipmz_qp* s, double** out) {
+  if (!s || !out) return fail(IPMZ_ERR_INVALID, "null argument");
+  *out = s->hq[0].scal;
+  return IPMZ_OK;
+}
+
+int ipmz_qp_copy_scalars(ipmz_qp* s, double* dst) {
+  if (!s || !dst) return fail(IPMZ_ERR_INVALID, "null argument");
+  HIP_OK(hipSetDevice(s->ctx->device));
+  HIP_OK(hipMemcpyAsync(dst, s->hq[0].scal, SC_COUNT * 8, hipMemcpyDeviceToDevice, s->ctx->stream));
+  return IPMZ_OK;
+}
+
+int ipmz_qp_solve(ipmz_qp* s, int max_iter, double* trace, int* iterations) {
+  if (!s || !s->loaded) return fail(IPMZ_ERR_STATE, "load or generate the QP first");
+  double sc[SC_COUNT];
+  int rc = scalars_impl(s, sc, 1);
+  if (rc) return rc;
+  int it = 0;
+  for (; it < max_iter; ++it) {  // Optimizer.cpp:127-135
+    double* row = trace ? trace + 8 * (int64_t)it : nullptr;
+    if (row) {
+      row[0] = sc[SC_F];
+      row[1] = sc[SC_RES];
+      row[2] = sc[SC_MU];
+      row[7] = sc[SC_CONVERGED];
+      row[3] = row[4] = row[5] = row[6] = 0.0;
+    }
+    if (sc[SC_CONVERGED] != 0.0) break;
+    rc = step_impl(s, 0);
+    if (rc) return rc;
+    rc = scalars_impl(s, sc, 1);
+    if (rc) return rc;
+    if (row) {
+      row[3] = sc[SC_ALPHA_AFF];
+      row[4] = sc[SC_MU_AFF];
+      row[5] = sc[SC_SIGMA];
+      row[6] = sc[SC_ALPHA];
+    }
+  }
+  if (iterations) *iterations = it;
+  return IPMZ_OK;
+}
+
+int64_t ipmz_qp_state_len(ipmz_qp* s) { return s ? s->state_len : 0; }
+
+int ipmz_qp_get_state(ipmz_qp* s, int which, double* out) {
+  if (!s) return fail(IPMZ_ERR_INVALID, "null qp");
+  return get_state_impl(s, 0, which, out);
+}
+
+int ipmz_qp_set_state(ipmz_qp* s, const double* in) {
+  if (!s || !in) return fail(IPMZ_ERR_INVALID, "bad arguments");
+  HIP_OK(hipSetDevice(s->ctx->device));
+  const std::vector<double> v = state_in(s, in);
+  for (int i = 0; i < s->B; ++i)
+    HIP_OK(hipMemcpyAsync(s->hq[i].v[0], v.data(), s->state_len * 8, hipMemcpyHostToDevice, s->ctx->stream));
+  HIP_OK(qp_evaluate(s->qb, s->ctx->stream));
+  HIP_OK(hipStreamSynchronize(s->ctx->stream));
+  s->loaded = true;
+  return IPMZ_OK;
+}
+
+int ipmz_qp_kkt_dim(ipmz_qp* s) { return s ? s->N : 0; }
+
+int ipmz_qp_get_kkt(ipmz_qp* s, double* out) {
+  if (!s || !out) return fail(IPMZ_ERR_INVALID, "bad arguments");
+  HIP_OK(hipSetDevice(s->ctx->device));
+  hipStream_t st = s->ctx->stream;
+  HIP_OK(qp_assemble(s->qb, st));
+  HIP_OK(hipMemcpy2DAsync(out, (size_t)s->N * 8, s->K, s->ldk * 8, (size_t)s->N * 8, s->N, hipMemcpyDeviceToHost,
+                          st));
+  HIP_OK(hipStreamSynchronize(st));
+  for (int i = 0; i < s->N; ++i)
+    for (int j = i + 1; j < s->N; ++j) out[(int64_t)i * s->N + j] = 0.0;
+  return IPMZ_OK;
+}
+
+int ipmz_qp_kkt_solve(ipmz_qp* s, int nrhs, double* B, int64_t ldb) {
+  if (!s) return fail(IPMZ_ERR_INVALID, "null qp");
+  if (s->B != 1) return fail(IPMZ_ERR_INVALID, "ipmz_qp_kkt_solve: single QPs only, this is a batch");
+  if (s->eqnone)
+    return fail(IPMZ_ERR_INVALID, "ipmz_qp_kkt_solve: EqualityHandling::None factors with Bunch-Kaufman, which has "
+                                  "no multi-right-hand-side solve");
+  if (s->normal)
+    return fail(IPMZ_ERR_INVALID, "ipmz_qp_kkt_solve: the normal-equations reduction is enabled (augmented LDL^T only)");
+  if (s->mixed)
+    return fail(IPMZ_ERR_INVALID, "ipmz_qp_kkt_solve: mixed precision is enabled (fp64 LDL^T only)");
+  if (!s->loaded) return fail(IPMZ_ERR_STATE, "load or generate the QP first");
+  if (nrhs < 0 || ldb < s->N || (ldb & 1) || (nrhs > 0 && !B))
+    return fail(IPMZ_ERR_INVALID, "ipmz_qp_kkt_solve: bad arguments (nrhs >= 0, ldb >= N and even)");
+  HIP_OK(hipSetDevice(s->ctx->device));
+  // the step's own assembly and factor, on the storage the next step
+  // overwrites anyway (it assembles and factors again): the iterate is only read
+  HIP_OK(qp_assemble(s->qb, s->ctx->stream));
+  const LdltWs w = ldlt_ws_of(s);
+  int rc = factor_impl(s->ctx, s->N, s->K, s->ldk, s->D, w, nbo_for(s->ctx, s->N), nullptr);
+  if (!rc) rc = ipmz_ldlt_solve_multi(s->ctx, s->N, s->K, s->ldk, s->D, s->ws, B, ldb, nrhs);
+  unwatch(s->ctx);  // s->ws is the solver's: checked here, not at a later sync
+  if (rc) return rc;
+  return read_info(s->ctx, w);  // synchronizes; checks the error words of s->ws itself
+}
+
+// the QP's mixed-precision workspace, allocated once (a captured step keeps its addresses)
+static int ensure_mixed_ws(ipmz_qp* s) {
+  if (s->mws) return IPMZ_OK;
+  // all of it is acquired before any of it is stored in s: a failure leaves
+  // s->mws null, and the next call tries again
+  const int nbo = nbo_for(s->ctx, s->N);
+  const int64_t bytes = mixed_ws_bytes(s->N, nbo);
+  void *w = nullptr, *h = nullptr, *hd = nullptr;
+  hipEvent_t hev = nullptr;
+  int rc = IPMZ_OK;
+  if (hipMalloc(&w, (size_t)bytes) != hipSuccess) rc = fail(IPMZ_ERR_NOMEM, "device allocation failed");
+  // the stop test's host-mapped word (eager solves wait on it)
+  else if (hipHostMalloc(&h, 64, hipHostMallocMapped | hipHostMallocCoherent) != hipSuccess)
+    rc = fail(IPMZ_ERR_NOMEM, "host allocation failed");
+  else {
+    hipError_t e = hipMemset(w, 0, (size_t)bytes);  // sticky error words start clear
+    if (e == hipSuccess) e = hipHostGetDevicePointer(&hd, h, 0);
+    if (e == hipSuccess) e = hipEventCreateWithFlags(&hev, hipEventDisableTiming);
+    if (e != hipSuccess) rc = hip_fail(e, "ensure_mixed_ws", __FILE__, __LINE__);
+  }
+  if (rc) {
+    if (hev) hipEventDestroy(hev);
+    if (h) hipHostFree(h);
+    hipFree(w);
+    return rc;
+  }
+  s->allocs.push_back(w);
+  s->mws = static_cast<char*>(w);
+  mixed_ws_carve(s->mws, s->N, nbo, s->mw);
+  s->mw.hst = static_cast<unsigned*>(h);
+  s->mw.hst[0] = s->mw.hst[1] = 0u;
+  s->mw.hst_dev = static_cast<unsigned*>(hd);
+  s->mw.hev = hev;
+  return IPMZ_OK;
+}
+
+int ipmz_qp_kkt_solve_mixed(ipmz_qp* s, int nrhs, double* B, int64_t ldb, double tol, int max_refine, double* stat) {
+  if (!s) return fail(IPMZ_ERR_INVALID, "null qp");
+  if (s->B != 1) return fail(IPMZ_ERR_INVALID, "ipmz_qp_kkt_solve_mixed: single QPs only, this is a batch");
+  if (s->eqnone)
+    return fail(IPMZ_ERR_INVALID, "ipmz_qp_kkt_solve_mixed: EqualityHandling::None factors with Bunch-Kaufman, which "
+                                  "has no mixed-precision form");
+  if (s->eqpen)
+    return fail(IPMZ_ERR_INVALID, "ipmz_qp_kkt_solve_mixed: EqualityHandling::PenaltyFunction has no mixed-precision "
+                                  "form");
+  if (s->normal)
+    return fail(IPMZ_ERR_INVALID, "ipmz_qp_kkt_solve_mixed: the normal-equations reduction is enabled (augmented "
+                                  "system only)");
+  if (!s->loaded) return fail(IPMZ_ERR_STATE, "load or generate the QP first");
+  if (nrhs < 0 || max_refine < 0 || ldb < s->N || (ldb & 1) || (nrhs > 0 && !B))
+    return fail(IPMZ_ERR_INVALID, "ipmz_qp_kkt_solve_mixed: bad arguments (nrhs >= 0, max_refine >= 0, ldb >= N and "
+                                  "even)");
+  if (nrhs > 0 && ((uintptr_t)B & 15)) return fail(IPMZ_ERR_INVALID, "ipmz_qp_kkt_solve_mixed: B must be 16-byte aligned");
+  ipmz_ctx* ctx = s->ctx;
+  HIP_OK(hipSetDevice(ctx->device));
+  int rc = not_capturing(ctx, "ipmz_qp_kkt_solve_mixed");
+  if (rc) return rc;
+  if (s->step_pending) {  // a forked step still in flight uses the event pool the factor below takes
+    HIP_OK(hipEventSynchronize(s->step_done));
+    s->step_pending = false;
+  }
+  if ((rc = ensure_mixed_ws(s))) return rc;
+  const int cap = std::max(nrhs, 1);
+  if (cap > s->mmws_nrhs) {
+    HIP_OK(hipStreamSynchronize(ctx->stream));
+    if (s->mmws) hipFree(s->mmws);
+    s->mmws = nullptr;
+    s->mmws_nrhs = 0;
+    MixedMultiWs m;
+    void* p = nullptr;
+    if (hipMalloc(&p, (size_t)mixed_multi_ws_carve(nullptr, s->N, cap, m)) != hipSuccess)
+      return fail(IPMZ_ERR_NOMEM, "device allocation failed");
+    s->mmws = static_cast<char*>(p);
+    s->mmws_nrhs = cap;
+  }
+  // the step's own assembly, and the fp32 factor in the workspace a mixed step
+  // factors into again before it solves: the iterate is only read
+  hipStream_t st = ctx->stream;
+  HIP_OK(qp_assemble(s->qb, st));
+  MixedWs w = s->mw;
+  w.hst = nullptr;  // looped solves enqueue all passes: the steps' learned pass count stays theirs
+  w.hst_dev = nullptr;
+  w.hev = nullptr;
+  if ((rc = mixed_factor_impl(ctx, s->K, s->ldk, w, nullptr))) return rc;
+  MixedMultiWs m;
+  mixed_multi_ws_carve(s->mmws, s->N, cap, m);
+  if (nrhs == 1) {
+    HIP_OK(mixed_solve(s->K, s->ldk, w, B, tol, max_refine, st));
+    HIP_OK(hipMemcpyAsync(m.stat, w.stat, 2 * sizeof(double), hipMemcpyDeviceToDevice, st));
+    if (stat) HIP_OK(hipMemcpyAsync(stat, m.stat, 2 * sizeof(double), hipMemcpyDeviceToHost, st));
+  } else if (nrhs > 1) {
+    if ((rc = mixed_multi_impl(ctx, s->K, s->ldk, w, m, B, ldb, nrhs, tol, max_refine, stat))) return rc;
+  }
+  const char* text = ": a hand-off inside a persistent kernel of the mixed-precision factor / solve timed out; the "
+                     "result is invalid";
+  return ws_result(st, w.info, w.pctrl + PANEL_ERR_WORD, w.ctrl + SOLVE_ERR_WORD, "ipmz_qp_kkt_solve_mixed", text,
+                   text);
+}
+
+int ipmz_qp_set_mixed_precision(ipmz_qp* s, int enable, double tol, int max_refine) {
+  if (!s) return fail(IPMZ_ERR_INVALID, "null qp");
+  if (enable && (s->B != 1 || !(tol > 0.0) || max_refine < 0 || s->normal || s->eqnone || s->eqpen))
+    return fail(IPMZ_ERR_INVALID, "mixed precision: single QPs, tol > 0, max_refine >= 0, augmented reduction, "
+                                  "Regularization equalities");
+  HIP_OK(hipSetDevice(s->ctx->device));
+  if (enable) {
+    const int rc = ensure_mixed_ws(s);
+    if (rc) return rc;
+  }
+  s->mixed = enable != 0;
+  s->ir_tol = tol;
+  s->ir_max = max_refine;
+  drop_graph(s);  // the captured step has the other solver baked in
+  return IPMZ_OK;
+}
+
+int ipmz_qp_set_reduction(ipmz_qp* s, int reduction) {
+  if (!s) return fail(IPMZ_ERR_INVALID, "null qp");
+  if (reduction != IPMZ_REDUCTION_AUGMENTED && reduction != IPMZ_REDUCTION_NORMAL)
+    return fail(IPMZ_ERR_INVALID, "unknown reduction");
+  if (reduction == IPMZ_REDUCTION_NORMAL && (s->B != 1 || s->mixed || s->eqnone || s->eqpen || s->naive))
+    return fail(IPMZ_ERR_INVALID, "normal equations: single QPs, not with mixed precision, Regularization equalities");
+  HIP_OK(hipSetDevice(s->ctx->device));
+  if (reduction == IPMZ_REDUCTION_NORMAL && !s->nws) {
+    const int64_t bytes = normal_ws_of(s).total;  // (s->nws is null: sizes only; no NaiveSlacks here, N = n + m + p)
+    void* w = nullptr;
+    if (hipMalloc(&w, (size_t)bytes) != hipSuccess) return fail(IPMZ_ERR_NOMEM, "device allocation failed");
+    s->allocs.push_back(w);
+    HIP_OK(hipMemset(w, 0, (size_t)bytes));  // sticky error words start clear
+    s->nws = static_cast<char*>(w);
+  }
+  s->normal = reduction == IPMZ_REDUCTION_NORMAL;
+  drop_graph(s);
+  return IPMZ_OK;
+}
+
+int ipmz_qp_set_timing(ipmz_qp* s, int enable) {
+  if (!s) return fail(IPMZ_ERR_INVALID, "null qp");
+  HIP_OK(hipSetDevice(s->ctx->device));
+  s->timing = enable != 0;
+  if (s->timing && s->ev.empty()) {
+    s->ev.resize(8);
+    for (size_t i = 0; i < s->ev.size(); ++i) HIP_OK(hipEventCreate(&s->ev[i]));
+    s->tr_cap = (s->N + 63) / 64 + 8;
+    s->tr_pairs = new hipEvent_t[s->tr_cap][2];
+    for (int i = 0; i < s->tr_cap; ++i) {
+      HIP_OK(hipEventCreate(&s->tr_pairs[i][0]));
+      HIP_OK(hipEventCreate(&s->tr_pairs[i][1]));
+    }
+  }
+  for (double& x : s->ph_ms) x = 0.0;
+  s->tr_flops = 0.0;
+  s->tr_launches = 0;
+  return IPMZ_OK;
+}
+
+int ipmz_qp_phase_times(ipmz_qp* s, double* ms, double* flops, int64_t* launches) {
+  if (!s) return fail(IPMZ_ERR_INVALID, "null qp");
+  if (ms)
+    for (int i = 0; i < IPMZ_PH_COUNT; ++i) ms[i] = s->ph_ms[i];
+  if (flops) *flops = s->tr_flops;
+  if (launches) *launches = s->tr_launches;
+  return IPMZ_OK;
+}
+
+// ---- batches of independent QPs (config C4) ---------------------------------
+int ipmz_batch_create(ipmz_ctx* ctx, const ipmz_qp_config* cfg, int batch, ipmz_qp** out) {
+  return create_solver(ctx, cfg, batch, out);
+}
+int ipmz_batch_size(ipmz_qp* s) { return s ? s->B : 0; }
+int ipmz_batch_load_host(ipmz_qp* s, int index, const double* Q, const double* c, const double* A, const double* lA,
+                         const double* uA, const double* C, const double* d, const double* lx, const double* ux) {
+  int rc = check_index(s, index);
+  if (rc) return rc;
+  if ((rc = load_one(s, index, Q, c, A, lA, uA, C, d, lx, ux))) return rc;
+  // the kept KKT matrix K0 (off-diagonal part written only by
+  // initialize) and the residuals still hold the old data: no step
+  // until ipmz_batch_initialize rebuilds them
+  s->loaded = false;
+  return IPMZ_OK;
+}
+int ipmz_batch_initialize(ipmz_qp* s) {
+  return s ? initialize(s) : fail(IPMZ_ERR_INVALID, "null qp");
+}
+int ipmz_batch_scalars(ipmz_qp* s, double* out) {
+  if (!s || !out) return fail(IPMZ_ERR_INVALID, "null argument");
+  return scalars_impl(s, out, s->B);
+}
+int ipmz_batch_get_state(ipmz_qp* s, int index, int which, double* out) {
+  int rc = check_index(s, index);
+  if (rc) return rc;
+  return get_state_impl(s, index, which, out);
+}
+int ipmz_batch_set_state(ipmz_qp* s, int index, const double* in) {
+  int rc = check_index(s, index);
+  if (rc) return rc;
+  if (!in) return fail(IPMZ_ERR_INVALID, "null state");
+  HIP_OK(hipSetDevice(s->ctx->device));
+  const std::vector<double> v = state_in(s, in);
+  HIP_OK(hipMemcpyAsync(s->hq[index].v[0], v.data(), s->state_len * 8, hipMemcpyHostToDevice, s->ctx->stream));
+  HIP_OK(qp_evaluate(s->qb, s->ctx->stream));
+  HIP_OK(hipStreamSynchronize(s->ctx->stream));
+  return IPMZ_OK;
+}
+int ipmz_batch_copy_scalars(ipmz_qp* s, double* dst) {
+  if (!s || !dst) return fail(IPMZ_ERR_INVALID, "null argument");
+  HIP_OK(hipSetDevice(s->ctx->device));
+  // the B scalar blocks are one allocation with a stride of SC_COUNT doubles
+  HIP_OK(hipMemcpy2DAsync(dst, SC_COUNT * 8, s->hq[0].scal, (s->B > 1 ? (s->hq[1].scal - s->hq[0].scal) : SC_COUNT) * 8,
+                          SC_COUNT * 8, s->B, hipMemcpyDeviceToDevice, s->ctx->stream));
+  return IPMZ_OK;
+}
+int ipmz_batch_summary(ipmz_qp* s, double* dst) {
+  if (!s || !dst) return fail(IPMZ_ERR_INVALID, "null argument");
+  HIP_OK(hipSetDevice(s->ctx->device));
+  HIP_OK(qp_batch_summary(s->qb, dst, s->ctx->stream));
+  return IPMZ_OK;
+}
+// Steps until every QP converged or max_iter; a converged QP keeps its
+// iterate.  converged_count: host, may be NULL.
+int ipmz_batch_solve(ipmz_qp* s, int max_iter, int* iterations, int* converged_count) {
+  if (!s || !s->loaded) return fail(IPMZ_ERR_STATE, "load or generate the batch first");
+  std::vector<double> sc((size_t)s->B * SC_COUNT);
+  int it = 0, nconv = 0;
+  for (;; ++it) {
+    int rc = scalars_impl(s, sc.data(), s->B);
+    if (rc) return rc;
+    nconv = 0;
+    for (int i = 0; i < s->B; ++i) nconv += sc[(size_t)i * SC_COUNT + SC_CONVERGED] != 0.0;
+    if (nconv == s->B || it >= max_iter) break;
+    if ((rc = step_impl(s, 0))) return rc;
+  }
+  if (iterations) *iterations = it;
+  if (converged_count) *converged_count = nconv;
+  return IPMZ_OK;
+}
+int ipmz_batch_set_factor_kernel(ipmz_qp* s, int kernel) {
+  if (!s || kernel < IPMZ_BATCH_FACTOR_AUTO || kernel > IPMZ_BATCH_FACTOR_LEFT)
+    return fail(IPMZ_ERR_INVALID, "ipmz_batch_set_factor_kernel: bad arguments");
+  if (kernel == IPMZ_BATCH_FACTOR_PAIR && !(s->pflags && small_pair_eligible(s->B, s->N)))
+    return fail(IPMZ_ERR_INVALID, "ipmz_batch_set_factor_kernel: two workgroups per QP need a batch of small systems "
+                                  "(N <= 1024) with 2 * batch <= #CU");
+  drop_graph(s);  // the captured step has the other kernel baked in
+  s->small_kernel = kernel;
+  return IPMZ_OK;
+}
+
+}  // extern "C"

@@ -297,7 +297,7 @@ class EqSlackedOracle:
     """OracleQP over eqss_merge(qp), in the reference's variable order
     (x, lambda_A, lambda_C, s, t, lambda_g, lambda_h, lambda_v, lambda_w,
     lambda_y, lambda_z, g, h, v, w, y, z) and with t starting at 1
-    (EnvironmentBuilder.cpp:62), as capi.cpp's eqss_perm.
+    (EnvironmentBuilder.cpp:62), as qp.cpp's eqss_perm.
 
     naive=True: EqualityHandling::NaiveSlacks with NaiveSlacks inequalities
     (SymbolicOptimization.cpp:163-171 against 104-116: C x - v = d, C x + w = d
