@@ -21,8 +21,11 @@ assertion before asserting it.
 
 Follow-up, not covered here: the batched small-system kernels (small.hip: ONE,
 PAIR, LEFT) and ldlt_diag64_blk_kernel take the colpass16_spec pass and are
-reachable only through generated QPs, whose pivots are never zero; testing
-them needs a way to hand a batch of matrices to the batched factor.
+reachable only through a Batch's Newton step, which factors the KKT matrix it
+assembled from QP data (generated, or handed over with Batch.load_one) --
+never with a zero pivot; testing them needs a way to hand the batched factor
+a KKT matrix itself.  (The batched kernel chain and solves at ordinary pivots:
+test_gpu_batch_large.py.)
 """
 import contextlib
 
