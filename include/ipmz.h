@@ -22,6 +22,11 @@
  *                                  right-hand sides through the fp32 factor (blocked fp32
  *                                  solve) with fp64 refinement and a per-row stop test;
  *                                  the refinement's residual R = B - X K on its own
+ *   ipmz_bk_prepare_solve, ipmz_bk_solve_multi, ipmz_overwriting_solve_bunch_kaufman_multi,
+ *   ipmz_qp_kkt_solve_bk, ipmz_normal_solve_multi
+ *                               <- no reference counterpart: overwriting_solve_bunch_kaufman
+ *                                  and the normal-equations solve for a block of right-hand
+ *                                  sides, on the same blocked triangular solve
  *   ipmz_qp_create + ipmz_qp_load_host
  *                               <- NumericalOptimization::build_environment
  *                                  (EnvironmentBuilder.h:19-20, EnvironmentBuilder.cpp:7-76)
@@ -158,8 +163,8 @@ int ipmz_ldlt_prepare_solve(ipmz_ctx* ctx, int N, const double* L, int64_t ld, v
  * columns on fp64 MFMA (L read once per sweep; stream-ordered launches, no
  * cross-workgroup waiting, deterministic), below it one after the other.
  * ws as for ipmz_ldlt_solve.  The multi-right-hand-side form of
- * ipmz_mixed_solve is ipmz_mixed_solve_multi (below).  Out of scope:
- * multi-right-hand-side forms of ipmz_normal_solve and ipmz_bk_solve. */
+ * ipmz_mixed_solve is ipmz_mixed_solve_multi, those of ipmz_normal_solve and
+ * ipmz_bk_solve are ipmz_normal_solve_multi and ipmz_bk_solve_multi (all below). */
 #define IPMZ_SOLVE_MULTI_PANEL 256
 int ipmz_ldlt_solve_multi(ipmz_ctx* ctx, int N, const double* K, int64_t ld, const double* D, const void* ws,
                           double* B, int64_t ldb, int nrhs);
@@ -220,6 +225,12 @@ int ipmz_normal_factor(ipmz_ctx* ctx, int n, int mp, double* K, int64_t ld, doub
 /* b = [r0; r1] (device) <- [x; l]:  l = S^{-1} (B H^{-1} r0 - r1),
  * x = H^{-1} (r0 - B^T l). */
 int ipmz_normal_solve(ipmz_ctx* ctx, int n, int mp, const double* K, int64_t ld, const double* D, void* ws, double* b);
+/* every row of B (device, nrhs rows, stride ldb >= n + mp) <- the
+ * ipmz_normal_solve of that row: ipmz_ldlt_solve_multi on the factor
+ * ipmz_normal_factor left (same crossover, kernels and alignment rules: ld and
+ * ldb even, K and B 16-byte aligned; nrhs == 1 is ipmz_normal_solve, bitwise). */
+int ipmz_normal_solve_multi(ipmz_ctx* ctx, int n, int mp, const double* K, int64_t ld, const double* D, void* ws,
+                            double* B, int64_t ldb, int nrhs);
 
 /* ---- Bunch-Kaufman (symmetric indefinite) ---------
  * LinearSolvers::symmetric_indefinite_factorization (LinearSolvers.h:23-26,
@@ -244,10 +255,39 @@ int ipmz_bk_factor_ex(ipmz_ctx* ctx, int N, double* A, int64_t ld, int* ipiv, in
  * N = 512 it reads a transposed copy of F made on the context's stream
  * (N * N doubles, stream-ordered allocation freed after the solve). */
 int ipmz_bk_solve(ipmz_ctx* ctx, int N, const double* F, int64_t ld, const int* ipiv, double* b);
+/* The same solve prepared once per factor and applied to a block of
+ * right-hand sides (no reference counterpart).  A^{-1} = P^T L'^{-T} D^{-1}
+ * L'^{-1} P with L' unit lower (every later interchange folded into L's
+ * columns), D block diagonal and P one permutation.
+ * workspace of a prepared Bunch-Kaufman solve of order N (bytes) */
+int64_t ipmz_bk_solve_workspace_bytes(ipmz_ctx* ctx, int N);
+/* once per factor: from ipmz_bk_factor's F and ipiv (device; F is only read) build in ws the
+ * transposed factor, L' (leading dimension round_up(N, 64)), the inverted 64-column diagonal
+ * blocks, the persistent solve's operators and the interchange bookkeeping.  Asynchronous. */
+int ipmz_bk_prepare_solve(ipmz_ctx* ctx, int N, const double* F, int64_t ld, const int* ipiv,
+                          void* ws, int64_t ws_bytes);
+/* every row of B (device, nrhs rows, stride ldb >= N, even, 16-byte aligned) <- A^{-1} row;
+ * in place, asynchronous, no allocation; B[r][N .. ldb) is never written.  F, ld, ipiv as given
+ * to ipmz_bk_prepare_solve and unchanged since.  Below a crossover nrhs the rows go one by one
+ * through the launches of ipmz_bk_solve (every such row, nrhs == 1 included, is bitwise the
+ * ipmz_bk_solve of that row); from it on together: row permutation, blocked forward sweep on
+ * L' (fp64 MFMA, column panels as ipmz_ldlt_solve_multi), the D solve in the reference's
+ * arithmetic, blocked backward sweep, inverse permutation -- stream-ordered launches, no
+ * cross-workgroup waiting, deterministic, a row's result independent of its neighbours.  A
+ * factor the reference solves in its own interleaved order only (a singular one with its
+ * kp = 0 defect, or N > 16384) runs those sweeps instead, one workgroup per row, chosen on
+ * the device.  ws must stay allocated until the next ipmz_ctx_sync, which reports a hand-off
+ * timeout of the looped solves as IPMZ_ERR_HIP. */
+int ipmz_bk_solve_multi(ipmz_ctx* ctx, int N, const double* F, int64_t ld, const int* ipiv,
+                        const void* ws, double* B, int64_t ldb, int nrhs);
 /* Host signatures of the reference (value semantics, reference pivoting
  * including its kp = 0 defect): F = A with the lower triangle factored. */
 int ipmz_symmetric_indefinite_factorization(ipmz_ctx* ctx, int N, const double* A, double* F, int* ipiv);
 int ipmz_overwriting_solve_bunch_kaufman(ipmz_ctx* ctx, int N, const double* F, const int* ipiv, double* b);
+/* The same for nrhs right-hand sides (ipmz_bk_prepare_solve + ipmz_bk_solve_multi):
+ * B host, nrhs x N row-major, every row overwritten with its solution. */
+int ipmz_overwriting_solve_bunch_kaufman_multi(ipmz_ctx* ctx, int N, const double* F, const int* ipiv,
+                                               double* B, int nrhs);
 
 /* ---- LinearSolvers with the reference's host signatures ------------------ */
 /* A: host N x N row-major (lower triangle read).  L: host N x N, written
@@ -378,6 +418,14 @@ int ipmz_qp_kkt_dim(ipmz_qp* qp);
  * step itself is untouched: its two solves depend on each other and stay
  * single-vector.  The mixed-precision form is ipmz_qp_kkt_solve_mixed. */
 int ipmz_qp_kkt_solve(ipmz_qp* qp, int nrhs, double* B, int64_t ldb);
+/* ipmz_qp_kkt_solve for single QPs with IPMZ_EQ_NONE: the step's own assembly
+ * and Bunch-Kaufman factor on the QP's storage, then ipmz_bk_solve_multi (B
+ * 16-byte aligned, ldb >= N and even).  Returns the factor's info like
+ * ipmz_bk_factor (synchronizes); the iterate and all later steps are unchanged
+ * (bitwise).  IPMZ_ERR_INVALID for batches, any other equality handling, an
+ * enabled normal-equations reduction or mixed precision; IPMZ_ERR_STATE
+ * before a load. */
+int ipmz_qp_kkt_solve_bk(ipmz_qp* qp, int nrhs, double* B, int64_t ldb);
 /* ipmz_qp_kkt_solve through the fp32 factor + fp64 refinement
  * (ipmz_mixed_factor + ipmz_mixed_solve_multi on the assembled KKT matrix),
  * whether or not the QP's steps use mixed precision.  B 16-byte aligned; tol,

@@ -1048,6 +1048,74 @@ __global__ void k_dsolve(double* __restrict__ y, int n, Meta m) {
     y[k + 1] = (akm1 * bk - bkm1) / denom;
   }
 }
+
+// The same three stages for a block of right-hand sides (one per row of B,
+// stride ldb, even; B 16-byte aligned), in place; columns [n, ldb) of a row
+// are never touched.  Gated like the single-vector kernels.
+constexpr int ROWT = 1024;
+// row <- P row ((P b)[p] = b[perm[p]]): one workgroup per row, the whole row
+// staged in LDS (n <= LDS_MAX_N: at most 128 KB), written back two entries
+// per 16-byte store
+__global__ __launch_bounds__(ROWT) void k_gather_rows(double* __restrict__ B, int64_t ldb, int n, Meta m) {
+  if (m.flag[0]) return;
+  extern __shared__ __attribute__((aligned(16))) double rowbuf[];
+  double* b = B + (int64_t)blockIdx.x * ldb;
+  const int tid = threadIdx.x, n2 = n >> 1;
+  for (int i = tid; i < n2; i += ROWT) reinterpret_cast<double2*>(rowbuf)[i] = reinterpret_cast<const double2*>(b)[i];
+  if ((n & 1) && tid == 0) rowbuf[n - 1] = b[n - 1];
+  __syncthreads();
+  for (int i = tid; i < n2; i += ROWT) {
+    const int2 pp = reinterpret_cast<const int2*>(m.perm)[i];
+    reinterpret_cast<double2*>(b)[i] = make_double2(rowbuf[pp.x], rowbuf[pp.y]);
+  }
+  if ((n & 1) && tid == 0) b[n - 1] = rowbuf[m.perm[n - 1]];
+}
+// the mirror: b[perm[p]] = b'[p]
+__global__ __launch_bounds__(ROWT) void k_scatter_rows(double* __restrict__ B, int64_t ldb, int n, Meta m) {
+  if (m.flag[0]) return;
+  extern __shared__ __attribute__((aligned(16))) double rowbuf[];
+  double* b = B + (int64_t)blockIdx.x * ldb;
+  const int tid = threadIdx.x, n2 = n >> 1;
+  for (int i = tid; i < n2; i += ROWT) {
+    const double2 v = reinterpret_cast<const double2*>(b)[i];
+    const int2 pp = reinterpret_cast<const int2*>(m.perm)[i];
+    rowbuf[pp.x] = v.x;
+    rowbuf[pp.y] = v.y;
+  }
+  if ((n & 1) && tid == 0) rowbuf[m.perm[n - 1]] = b[n - 1];
+  __syncthreads();
+  for (int i = tid; i < n2; i += ROWT) reinterpret_cast<double2*>(b)[i] = reinterpret_cast<const double2*>(rowbuf)[i];
+  if ((n & 1) && tid == 0) b[n - 1] = rowbuf[n - 1];
+}
+// every row <- row D^{-1}: k_dsolve's arithmetic, one thread per (row, k).
+// The thread on the first row of a 2x2 pivot writes both entries of its pair
+// (wherever k + 1 lies: nothing here knows of blocks or panels), the thread
+// on its second row does nothing
+__global__ __launch_bounds__(256) void k_dsolve_rows(double* __restrict__ B, int64_t ldb, int nrhs, int n, Meta m) {
+  if (m.flag[0]) return;
+  const int k = blockIdx.x * blockDim.x + threadIdx.x;
+  if (k >= n) return;
+  const int kd = m.kind[k];
+  if (kd == 0) {
+    const double d = m.d11[k];
+    for (int r = blockIdx.y; r < nrhs; r += gridDim.y) {
+      double* y = B + (int64_t)r * ldb;
+      y[k] = y[k] / d;
+    }
+  } else if (kd == 1 && k + 1 < n) {
+    const double akm1k = m.d21[k];
+    const double akm1 = m.d11[k] / akm1k;
+    const double ak = m.d22[k] / akm1k;
+    const double denom = akm1 * ak - 1.0;
+    for (int r = blockIdx.y; r < nrhs; r += gridDim.y) {
+      double* y = B + (int64_t)r * ldb;
+      const double bkm1 = y[k] / akm1k;
+      const double bk = y[k + 1] / akm1k;
+      y[k] = (ak * bkm1 - bk) / denom;
+      y[k + 1] = (akm1 * bk - bkm1) / denom;
+    }
+  }
+}
 }  // namespace bkf
 
 size_t bk_fast_meta_bytes(int n) { return bkf::layout(nullptr, n).total; }
@@ -1089,6 +1157,37 @@ hipError_t bk_fast_scatter(double* b, int n, void* meta, hipStream_t st) {
 }
 hipError_t bk_fast_fallback(const double* LT, int n, const int* ipiv, double* b, const void* meta, hipStream_t st) {
   hipLaunchKernelGGL(k_bk_solve<true>, dim3(1), dim3(BKT), 0, st, LT, (int64_t)n, n, 0, ipiv, 0, b, 0,
+                     bk_fast_flag(meta));
+  return hipGetLastError();
+}
+
+// the row permutations stage a row of up to LDS_MAX_N doubles: more than the
+// 64 KB a kernel gets by default; raised once per process
+template <void (*kern)(double*, int64_t, int, bkf::Meta)>
+static hipError_t launch_rows_perm(double* B, int64_t ldb, int nrhs, int n, void* meta, hipStream_t st) {
+  if (n > bkf::LDS_MAX_N) return hipSuccess;  // (the prepare set the fallback flag: nothing to permute)
+  static const hipError_t attr =
+      hipFuncSetAttribute(reinterpret_cast<const void*>(kern), hipFuncAttributeMaxDynamicSharedMemorySize,
+                          (int)(bkf::LDS_MAX_N * sizeof(double)));
+  if (attr != hipSuccess) return attr;
+  hipLaunchKernelGGL(kern, dim3(nrhs), dim3(bkf::ROWT), (size_t)(n + (n & 1)) * sizeof(double), st, B, ldb, n,
+                     bkf::layout(static_cast<char*>(meta), n));
+  return hipGetLastError();
+}
+hipError_t bk_multi_gather(double* B, int64_t ldb, int nrhs, int n, void* meta, hipStream_t st) {
+  return launch_rows_perm<bkf::k_gather_rows>(B, ldb, nrhs, n, meta, st);
+}
+hipError_t bk_multi_scatter(double* B, int64_t ldb, int nrhs, int n, void* meta, hipStream_t st) {
+  return launch_rows_perm<bkf::k_scatter_rows>(B, ldb, nrhs, n, meta, st);
+}
+hipError_t bk_multi_dsolve(double* B, int64_t ldb, int nrhs, int n, void* meta, hipStream_t st) {
+  hipLaunchKernelGGL(bkf::k_dsolve_rows, dim3((n + 255) / 256, nrhs < 65535 ? nrhs : 65535), dim3(256), 0, st, B, ldb,
+                     nrhs, n, bkf::layout(static_cast<char*>(meta), n));
+  return hipGetLastError();
+}
+hipError_t bk_multi_fallback(const double* LT, int n, const int* ipiv, double* B, int64_t ldb, int nrhs,
+                             const void* meta, hipStream_t st) {
+  hipLaunchKernelGGL(k_bk_solve<true>, dim3(nrhs), dim3(BKT), 0, st, LT, (int64_t)n, n, 0, ipiv, 0, B, ldb,
                      bk_fast_flag(meta));
   return hipGetLastError();
 }

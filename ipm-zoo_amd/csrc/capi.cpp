@@ -188,6 +188,61 @@ static int multi_panel_width(int dbg, int dflt) {
   return (dbg & IPMZ_DEBUG_MULTI_W512) ? 512 : (dbg & IPMZ_DEBUG_MULTI_W128) ? 128 : dflt;
 }
 
+// nrhs >= 2 rows through the LDL^T factor in w: looped single-vector solves
+// below the crossover, the blocked solve from it on
+static int ldlt_multi_impl(ipmz_ctx* ctx, int N, const double* K, int64_t ld, const double* D, const LdltWs& w,
+                           double* B, int64_t ldb, int nrhs) {
+  const int dbg = debug_inject_mask();
+  if (nrhs < SOLVE_MULTI_CROSSOVER && !(dbg & IPMZ_DEBUG_MULTI_BLOCKED)) {
+    for (int r = 0; r < nrhs; ++r) HIP_OK(solve_ws(K, ld, N, D, w, ctx->nbi, B + (int64_t)r * ldb, ctx->stream));
+  } else {
+    const int pw = multi_panel_width(dbg, SOLVE_MULTI_PANEL);
+    HIP_OK(ldlt_solve_multi<double>(K, ld, N, D, w.Linv, ctx->nbi, B, ldb, nrhs, pw, ctx->stream));
+  }
+  watch(ctx, w);  // as ipmz_ldlt_solve: the workspace's error words are checked by ipmz_ctx_sync
+  return IPMZ_OK;
+}
+
+// Multi-right-hand-side Bunch-Kaufman solve (bk.hip bk_multi_*, trsm.hip on
+// L').  The blocked kernels are the LDL^T solve's, so the panel width is
+// SOLVE_MULTI_PANEL.  BK_MULTI_CROSSOVER: the number of right-hand sides from
+// which the blocked path runs, from tools/bk_multi_bench.py
+// (profiles/bk_multi/crossover_scan.json and bench.json, DESIGN.md
+// "Multi-right-hand-side Bunch-Kaufman solve"): a looped row on the prepared
+// workspace costs 71 us (N = 2560) / 382 us (N = 11264), the blocked path 0.76
+// / 3.66 ms at ten rows, so they break even at 10.7 / 9.6 rows; 12 is the
+// first count at which the blocked path leads by more than the loop's own
+// spread at both orders (1.10x / 1.25x; at 10 it loses at N = 2560, at 11 it
+// leads by 1.01x, inside the spread).
+static constexpr int BK_MULTI_CROSSOVER = 12;
+
+int bk_multi_impl(ipmz_ctx* ctx, int N, const double* F, int64_t ld, const int* ipiv, const double* LT,
+                  const double* Lp, int64_t ldp, const BkWs& w, double* B, int64_t ldb, int nrhs) {
+  const int dbg = debug_inject_mask();
+  hipStream_t st = ctx->stream;
+  if (nrhs < BK_MULTI_CROSSOVER && !(nrhs >= 2 && (dbg & IPMZ_DEBUG_MULTI_BLOCKED))) {
+    // exactly ipmz_bk_solve's launches for this order, row by row
+    for (int r = 0; r < nrhs; ++r) {
+      double* b = B + (int64_t)r * ldb;
+      if (N < IPMZ_BK_GRID_MIN) HIP_OK(bk_solve(F, ld, N, ipiv, b, 1, 0, 0, 0, st));
+      else HIP_OK(bk_run(Lp, ldp, N, LT, ipiv, w, b, st));
+    }
+  } else {
+    // every stage exits on the fallback flag, read on the device; the
+    // fallback launch is gated the other way
+    const unsigned* flag = bk_fast_flag(w.meta);
+    const int pw = multi_panel_width(dbg, SOLVE_MULTI_PANEL);
+    HIP_OK(bk_multi_gather(B, ldb, nrhs, N, w.meta, st));
+    HIP_OK(trsm_sweep<double>(Lp, ldp, N, w.Linv, 64, B, ldb, nrhs, pw, false, st, flag));
+    HIP_OK(bk_multi_dsolve(B, ldb, nrhs, N, w.meta, st));
+    HIP_OK(trsm_sweep<double>(Lp, ldp, N, w.Linv, 64, B, ldb, nrhs, pw, true, st, flag));
+    HIP_OK(bk_multi_scatter(B, ldb, nrhs, N, w.meta, st));
+    HIP_OK(bk_multi_fallback(LT, N, ipiv, B, ldb, nrhs, w.meta, st));
+  }
+  watch(ctx, w);  // the persistent sweeps' error word is checked by ipmz_ctx_sync
+  return IPMZ_OK;
+}
+
 // Mixed-precision multi-right-hand-side solve (mixed_multi.hip, trsm.hip).
 // MIXED_MULTI_PANEL: column panel of the blocked fp32 solve;
 // MIXED_MULTI_CROSSOVER: the number of right-hand sides from which the blocked
@@ -354,7 +409,7 @@ int ipmz_ctx_sync(ipmz_ctx* ctx) {
   HIP_OK(hipStreamSynchronize(ctx->stream));  // (a failure here leaves the watched words watched)
   const unsigned *pe = ctx->check_pe, *se = ctx->check_se;
   unwatch(ctx);
-  return pe ? ws_result(ctx->stream, nullptr, pe, se, "ipmz_ctx_sync") : IPMZ_OK;
+  return pe || se ? ws_result(ctx->stream, nullptr, pe, se, "ipmz_ctx_sync") : IPMZ_OK;
 }
 
 int ipmz_debug_inject(int mask) {
@@ -434,15 +489,7 @@ int ipmz_ldlt_solve_multi(ipmz_ctx* ctx, int N, const double* K, int64_t ld, con
     return fail(IPMZ_ERR_INVALID, "ipmz_ldlt_solve_multi: K and B must be 16-byte aligned");
   HIP_OK(hipSetDevice(ctx->device));
   const LdltWs w = ldlt_ws(static_cast<char*>(const_cast<void*>(ws)), N, nbo_for(ctx, N), ctx->nbi);
-  const int dbg = debug_inject_mask();
-  if (nrhs < SOLVE_MULTI_CROSSOVER && !(dbg & IPMZ_DEBUG_MULTI_BLOCKED)) {
-    for (int r = 0; r < nrhs; ++r) HIP_OK(solve_ws(K, ld, N, D, w, ctx->nbi, B + (int64_t)r * ldb, ctx->stream));
-  } else {
-    const int pw = multi_panel_width(dbg, SOLVE_MULTI_PANEL);
-    HIP_OK(ldlt_solve_multi<double>(K, ld, N, D, w.Linv, ctx->nbi, B, ldb, nrhs, pw, ctx->stream));
-  }
-  watch(ctx, w);  // as ipmz_ldlt_solve: the workspace's error words are checked by ipmz_ctx_sync
-  return IPMZ_OK;
+  return ldlt_multi_impl(ctx, N, K, ld, D, w, B, ldb, nrhs);
 }
 
 // Mixed precision (config C5) -------------------------------------------------
@@ -549,6 +596,22 @@ int ipmz_normal_solve(ipmz_ctx* ctx, int n, int mp, const double* K, int64_t ld,
   return normal_solve_impl(ctx, n, mp, K, ld, D, w, b);
 }
 
+int ipmz_normal_solve_multi(ipmz_ctx* ctx, int n, int mp, const double* K, int64_t ld, const double* D, void* ws,
+                            double* B, int64_t ldb, int nrhs) {
+  const int N = n + mp;
+  if (!ctx || n <= 0 || mp < 0 || nrhs < 0 || ld < N || ldb < N || (ld & 1) || (ldb & 1))
+    return fail(IPMZ_ERR_INVALID, "ipmz_normal_solve_multi: bad arguments (n > 0, nrhs >= 0, ld >= n + mp, "
+                                  "ldb >= n + mp, both even)");
+  if (nrhs == 0) return IPMZ_OK;
+  if (!K || !D || !ws || !B) return fail(IPMZ_ERR_INVALID, "ipmz_normal_solve_multi: null pointer");
+  if (nrhs == 1) return ipmz_normal_solve(ctx, n, mp, K, ld, D, ws, B);
+  if (((uintptr_t)K & 15) || ((uintptr_t)B & 15))
+    return fail(IPMZ_ERR_INVALID, "ipmz_normal_solve_multi: K and B must be 16-byte aligned");
+  HIP_OK(hipSetDevice(ctx->device));
+  const NormalWs w = normal_ws(static_cast<char*>(ws), N, nbo_for(ctx, N), ctx->nbi);
+  return ldlt_multi_impl(ctx, N, K, ld, D, w.k, B, ldb, nrhs);
+}
+
 // Bunch-Kaufman (f3) ----------------------------------------------------------
 int ipmz_bk_factor(ipmz_ctx* ctx, int N, double* A, int64_t ld, int* ipiv, int fix_kp) {
   return ipmz_bk_factor_ex(ctx, N, A, ld, ipiv, fix_kp, IPMZ_BK_AUTO);
@@ -612,6 +675,37 @@ int ipmz_bk_solve(ipmz_ctx* ctx, int N, const double* F, int64_t ld, const int* 
   return rc;
 }
 
+int64_t ipmz_bk_solve_workspace_bytes(ipmz_ctx* ctx, int N) {
+  if (!ctx || N < 0) return 0;
+  return bk_solve_ws(nullptr, N).total;
+}
+
+int ipmz_bk_prepare_solve(ipmz_ctx* ctx, int N, const double* F, int64_t ld, const int* ipiv, void* ws,
+                          int64_t ws_bytes) {
+  if (!ctx || N < 0 || ld < N) return fail(IPMZ_ERR_INVALID, "ipmz_bk_prepare_solve: bad arguments (ld >= N)");
+  if (N == 0) return IPMZ_OK;
+  if (!F || !ipiv || !ws) return fail(IPMZ_ERR_INVALID, "ipmz_bk_prepare_solve: null pointer");
+  const BkSolveWs w = bk_solve_ws(static_cast<char*>(ws), N);
+  if (ws_bytes < w.total)
+    return fail(IPMZ_ERR_INVALID, "ipmz_bk_prepare_solve: workspace too small (ipmz_bk_solve_workspace_bytes(N))");
+  HIP_OK(hipSetDevice(ctx->device));
+  HIP_OK(bk_transpose(F, ld, N, w.LT, ctx->stream));
+  HIP_OK(bk_setup(F, ld, N, ipiv, nullptr, w.LT, w.Lp, w.ldp, w.k, ctx->stream));
+  return IPMZ_OK;
+}
+
+int ipmz_bk_solve_multi(ipmz_ctx* ctx, int N, const double* F, int64_t ld, const int* ipiv, const void* ws, double* B,
+                        int64_t ldb, int nrhs) {
+  if (!ctx || N < 0 || nrhs < 0 || ld < N || ldb < N || (ldb & 1))
+    return fail(IPMZ_ERR_INVALID, "ipmz_bk_solve_multi: bad arguments (nrhs >= 0, ld >= N, ldb >= N and even)");
+  if (N == 0 || nrhs == 0) return IPMZ_OK;
+  if (!F || !ipiv || !ws || !B) return fail(IPMZ_ERR_INVALID, "ipmz_bk_solve_multi: null pointer");
+  if ((uintptr_t)B & 15) return fail(IPMZ_ERR_INVALID, "ipmz_bk_solve_multi: B must be 16-byte aligned");
+  HIP_OK(hipSetDevice(ctx->device));
+  const BkSolveWs w = bk_solve_ws(static_cast<char*>(const_cast<void*>(ws)), N);
+  return bk_multi_impl(ctx, N, F, ld, ipiv, w.LT, w.Lp, w.ldp, w.k, B, ldb, nrhs);
+}
+
 // Host adapters with the reference's signatures ------------------------------
 int ipmz_symmetric_indefinite_factorization(ipmz_ctx* ctx, int N, const double* A, double* F, int* ipiv) {
   if (!ctx || N < 0 || (N > 0 && (!A || !F || !ipiv)))
@@ -646,6 +740,36 @@ int ipmz_overwriting_solve_bunch_kaufman(ipmz_ctx* ctx, int N, const double* F, 
   const int rc = ipmz_bk_solve(ctx, N, dF, N, dp, db);
   if (rc) return rc;
   if (!rows_out(b, db.p, N, N, 1, st) || hipStreamSynchronize(st) != hipSuccess)
+    return fail(IPMZ_ERR_HIP, "copy-out failed");
+  return IPMZ_OK;
+}
+
+int ipmz_overwriting_solve_bunch_kaufman_multi(ipmz_ctx* ctx, int N, const double* F, const int* ipiv, double* B,
+                                               int nrhs) {
+  if (!ctx || N < 0 || nrhs < 0)
+    return fail(IPMZ_ERR_INVALID, "ipmz_overwriting_solve_bunch_kaufman_multi: bad arguments");
+  if (N == 0 || nrhs == 0) return IPMZ_OK;
+  if (!F || !ipiv || !B) return fail(IPMZ_ERR_INVALID, "null pointer");
+  HIP_OK(hipSetDevice(ctx->device));
+  hipStream_t st = ctx->stream;
+  const int64_t nn = (int64_t)N * N, ldb = round_up(N, 2);
+  const int64_t wsb = bk_solve_ws(nullptr, N).total;
+  DevBuf<double> dF, dB;
+  DevBuf<int> dp;
+  DevBuf<char> ws;
+  if (!dF.alloc(nn) || !dB.alloc(ldb * nrhs) || !dp.alloc(N) || !ws.alloc(wsb))
+    return fail(IPMZ_ERR_NOMEM, "device allocation failed");
+  if (!rows_in(dF.p, nn, F, nn, 1, st) || !rows_in(dB.p, ldb, B, N, nrhs, st) || !rows_in(dp.p, N, ipiv, N, 1, st))
+    return fail(IPMZ_ERR_HIP, "copy-in failed");
+  int rc = ipmz_bk_prepare_solve(ctx, N, dF, N, dp, ws, wsb);
+  if (!rc) rc = ipmz_bk_solve_multi(ctx, N, dF, N, dp, ws, dB, ldb, nrhs);
+  // ws is freed on return: check the solve's error word now, not at a later sync
+  unwatch(ctx);
+  if (!rc)
+    rc = ws_result(st, nullptr, nullptr, bk_solve_ws(ws, N).k.ctrl + SOLVE_ERR_WORD,
+                   "ipmz_overwriting_solve_bunch_kaufman_multi");
+  if (rc) return rc;
+  if (!rows_out(B, dB.p, ldb, N, nrhs, st) || hipStreamSynchronize(st) != hipSuccess)
     return fail(IPMZ_ERR_HIP, "copy-out failed");
   return IPMZ_OK;
 }

@@ -133,12 +133,35 @@ inline BkWs bk_ws(char* base, int N) {
   w.total = c.off;
   return w;
 }
-
-// the workspace whose sticky error words the next ipmz_ctx_sync checks
-inline void watch(ipmz_ctx* ctx, const LdltWs& w) {
-  ctx->check_pe = w.pctrl + PANEL_ERR_WORD;
-  ctx->check_se = w.ctrl + SOLVE_ERR_WORD;
+// A prepared Bunch-Kaufman solve (ipmz_bk_prepare_solve, once per factor):
+// the factor transposed (LT, N x N: the interchange folding's input and the
+// fallback's factor), L' (N x ldp, ldp = round_up(N, 64)) and the device-wide
+// solve's workspace above
+struct BkSolveWs {
+  double *LT = nullptr, *Lp = nullptr;
+  int64_t ldp = 0;
+  BkWs k;
+  int64_t total = 0;
+};
+inline BkSolveWs bk_solve_ws(char* base, int N) {
+  BkSolveWs w;
+  Carver c{base};
+  w.ldp = round_up(N, 64);
+  w.LT = c.take<double>((int64_t)N * N);
+  w.Lp = c.take<double>((int64_t)N * w.ldp);
+  w.k = bk_ws(base ? base + c.off : nullptr, N);
+  w.total = c.off + w.k.total;
+  return w;
 }
+
+// the workspace whose sticky error words the next ipmz_ctx_sync checks (pe:
+// a panel factor's, may be null; se: a persistent solve's)
+inline void watch(ipmz_ctx* ctx, const unsigned* pe, const unsigned* se) {
+  ctx->check_pe = pe;
+  ctx->check_se = se;
+}
+inline void watch(ipmz_ctx* ctx, const LdltWs& w) { watch(ctx, w.pctrl + PANEL_ERR_WORD, w.ctrl + SOLVE_ERR_WORD); }
+inline void watch(ipmz_ctx* ctx, const BkWs& w) { watch(ctx, nullptr, w.ctrl + SOLVE_ERR_WORD); }
 inline void unwatch(ipmz_ctx* ctx) { ctx->check_pe = ctx->check_se = nullptr; }
 
 // capi.cpp --------------------------------------------------------------------
@@ -169,5 +192,11 @@ hipError_t bk_setup(const double* F, int64_t ld, int N, const int* ipiv, const i
                     int64_t ldp, const BkWs& w, hipStream_t st);
 hipError_t bk_run(const double* Lp, int64_t ldp, int N, const double* LT, const int* ipiv, const BkWs& w, double* b,
                   hipStream_t st);
+// the nrhs rows of B <- A^{-1} row from a prepared factor (LT, L' in Lp, w);
+// F: the factor itself, read only below IPMZ_BK_GRID_MIN (the one-workgroup
+// solve of rows below the crossover).  Asynchronous; arguments checked by the
+// caller (ldb even, B 16-byte aligned)
+int bk_multi_impl(ipmz_ctx* ctx, int N, const double* F, int64_t ld, const int* ipiv, const double* LT,
+                  const double* Lp, int64_t ldp, const BkWs& w, double* B, int64_t ldb, int nrhs);
 
 #pragma GCC visibility pop

@@ -40,7 +40,8 @@ namespace ipmz {
 // 16384 = batches run the two solves and the phases between them as separate launches (A/B),
 // 65536 = ipmz_ldlt_solve_multi runs its blocked path from 2 right-hand sides on (no looped single-vector
 //         solves below the crossover) (A/B, tools/solve_multi_bench.py); ipmz_mixed_solve_multi and
-//         ipmz_qp_kkt_solve_mixed likewise (tools/mixed_multi_bench.py),
+//         ipmz_qp_kkt_solve_mixed likewise (tools/mixed_multi_bench.py), and ipmz_normal_solve_multi,
+//         ipmz_bk_solve_multi and ipmz_qp_kkt_solve_bk (tools/bk_multi_bench.py),
 // 131072 / 262144 = ... with 512- / 128-column panels instead of IPMZ_SOLVE_MULTI_PANEL (A/B),
 // 524288 / 1048576 = the persistent solve splits every 128-row block over 2 / 4 workgroups, whatever
 //         its table says; both bits = the unsplit solve (all three bitwise alike,
@@ -197,6 +198,13 @@ template <typename T>
 hipError_t ldlt_solve_multi(const T* K, int64_t ld, int N, const T* D, const T* Linv, int nbi, T* B, int64_t ldb,
                             int nrhs, int w, hipStream_t st);
 
+// one of its sweeps alone: forward B <- B L^{-T}, backward B <- B L^{-1} (the
+// middle stage is the caller's; same argument rules).  gate (device word, may
+// be null): when set, every launch ends at once if *gate != 0
+template <typename T>
+hipError_t trsm_sweep(const T* K, int64_t ld, int N, const T* Linv, int nbi, T* B, int64_t ldb, int nrhs, int w,
+                      bool backward, hipStream_t st, const unsigned* gate);
+
 // one workgroup per QP of a batch (small N); b: batch of rhs, stride sb
 hipError_t ldlt_solve_batched(const double* K, int64_t ld, int N, const double* D, const double* Linv, int nbi,
                               double* b, int B, int64_t sK, int64_t sD, int64_t sL, int64_t sb, hipStream_t st);
@@ -322,6 +330,17 @@ hipError_t bk_fast_gather(const double* b, int n, void* meta, hipStream_t st);
 hipError_t bk_fast_dsolve(double* y, int n, void* meta, hipStream_t st);
 hipError_t bk_fast_scatter(double* b, int n, void* meta, hipStream_t st);
 hipError_t bk_fast_fallback(const double* LT, int n, const int* ipiv, double* b, const void* meta, hipStream_t st);
+// The same solve for the nrhs rows of B (stride ldb, even; B 16-byte aligned),
+// in place: bk_multi_gather -> trsm_sweep forward on L' (gate = the fallback
+// flag) -> bk_multi_dsolve -> trsm_sweep backward -> bk_multi_scatter, then
+// bk_multi_fallback (one launch, a workgroup per row, run only when the flag
+// is set).  Stream-ordered, nothing waits across workgroups; columns
+// [n, ldb) of B are never written.
+hipError_t bk_multi_gather(double* B, int64_t ldb, int nrhs, int n, void* meta, hipStream_t st);
+hipError_t bk_multi_dsolve(double* B, int64_t ldb, int nrhs, int n, void* meta, hipStream_t st);
+hipError_t bk_multi_scatter(double* B, int64_t ldb, int nrhs, int n, void* meta, hipStream_t st);
+hipError_t bk_multi_fallback(const double* LT, int n, const int* ipiv, double* B, int64_t ldb, int nrhs,
+                             const void* meta, hipStream_t st);
 
 // newton.hip -----------------------------------------------------------------
 enum Slot { X = 0, LA, LC, S, P, LG, LH, LY, LZ, G, H, Y, Z, NSLOT };

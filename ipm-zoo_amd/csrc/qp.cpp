@@ -49,6 +49,7 @@ struct ipmz_qp {
   char* bkws = nullptr;  // the whole-device Bunch-Kaufman factor's workspace (B == 1, N >= IPMZ_BK_GRID_MIN)
   double* bklt = nullptr;  // its factor transposed (N x N): the interchange folding's input, the fallback's factor
   char* bkfws = nullptr;   // the device-wide solve's workspace (bk_ws), L' in K
+  char* bkmws = nullptr;   // ipmz_qp_kkt_solve_bk below that order: its prepared solve (bk_solve_ws), on first use
   unsigned* pflags = nullptr;  // B > 1: the two-workgroup small factor's flags + sticky error word
   int small_kernel = IPMZ_BATCH_FACTOR_AUTO;  // ipmz_batch_set_factor_kernel
   bool eqpen = false;  // EqualityHandling::PenaltyFunction (LDL^T)
@@ -908,8 +909,8 @@ int ipmz_qp_kkt_solve(ipmz_qp* s, int nrhs, double* B, int64_t ldb) {
   if (!s) return fail(IPMZ_ERR_INVALID, "null qp");
   if (s->B != 1) return fail(IPMZ_ERR_INVALID, "ipmz_qp_kkt_solve: single QPs only, this is a batch");
   if (s->eqnone)
-    return fail(IPMZ_ERR_INVALID, "ipmz_qp_kkt_solve: EqualityHandling::None factors with Bunch-Kaufman, which has "
-                                  "no multi-right-hand-side solve");
+    return fail(IPMZ_ERR_INVALID, "ipmz_qp_kkt_solve: EqualityHandling::None factors with Bunch-Kaufman: its "
+                                  "multi-right-hand-side solve is ipmz_qp_kkt_solve_bk");
   if (s->normal)
     return fail(IPMZ_ERR_INVALID, "ipmz_qp_kkt_solve: the normal-equations reduction is enabled (augmented LDL^T only)");
   if (s->mixed)
@@ -927,6 +928,56 @@ int ipmz_qp_kkt_solve(ipmz_qp* s, int nrhs, double* B, int64_t ldb) {
   unwatch(s->ctx);  // s->ws is the solver's: checked here, not at a later sync
   if (rc) return rc;
   return read_info(s->ctx, w);  // synchronizes; checks the error words of s->ws itself
+}
+
+int ipmz_qp_kkt_solve_bk(ipmz_qp* s, int nrhs, double* B, int64_t ldb) {
+  if (!s) return fail(IPMZ_ERR_INVALID, "null qp");
+  if (s->B != 1) return fail(IPMZ_ERR_INVALID, "ipmz_qp_kkt_solve_bk: single QPs only, this is a batch");
+  if (!s->eqnone)
+    return fail(IPMZ_ERR_INVALID, "ipmz_qp_kkt_solve_bk: EqualityHandling::None only (the Bunch-Kaufman factor); "
+                                  "the LDL^T handlings solve with ipmz_qp_kkt_solve");
+  if (s->normal) return fail(IPMZ_ERR_INVALID, "ipmz_qp_kkt_solve_bk: the normal-equations reduction is enabled");
+  if (s->mixed) return fail(IPMZ_ERR_INVALID, "ipmz_qp_kkt_solve_bk: mixed precision is enabled");
+  if (!s->loaded) return fail(IPMZ_ERR_STATE, "load or generate the QP first");
+  if (nrhs < 0 || ldb < s->N || (ldb & 1) || (nrhs > 0 && !B))
+    return fail(IPMZ_ERR_INVALID, "ipmz_qp_kkt_solve_bk: bad arguments (nrhs >= 0, ldb >= N and even)");
+  if (nrhs > 0 && ((uintptr_t)B & 15)) return fail(IPMZ_ERR_INVALID, "ipmz_qp_kkt_solve_bk: B must be 16-byte aligned");
+  HIP_OK(hipSetDevice(s->ctx->device));
+  hipStream_t st = s->ctx->stream;
+  if (s->step_pending) {  // a forked step still in flight reads the storage factored below
+    HIP_OK(hipEventSynchronize(s->step_done));
+    s->step_pending = false;
+  }
+  // below IPMZ_BK_GRID_MIN the steps solve on F itself: the prepared solve's
+  // workspace is this call's own, allocated on first use and kept
+  if (!s->bkfws && !s->bkmws) {
+    void* w = nullptr;
+    if (hipMalloc(&w, (size_t)bk_solve_ws(nullptr, s->N).total) != hipSuccess)
+      return fail(IPMZ_ERR_NOMEM, "device allocation failed");
+    s->allocs.push_back(w);
+    s->bkmws = static_cast<char*>(w);
+  }
+  // the step's own assembly and factor, on the storage the next step
+  // overwrites anyway (it assembles and factors again): the iterate is only read
+  HIP_OK(qp_assemble(s->qb, st));
+  int rc = factor_batch(s, nullptr, false);
+  if (rc) return rc;
+  const unsigned* se = nullptr;
+  if (s->bkfws) {  // factor_batch left LT in bklt, L' in K and the operators in bkfws
+    const BkWs w = bk_ws(s->bkfws, s->N);
+    rc = bk_multi_impl(s->ctx, s->N, s->K, s->ldk, s->ipiv, s->bklt, s->K, s->ldk, w, B, ldb, nrhs);
+    se = w.ctrl + SOLVE_ERR_WORD;
+  } else {
+    const BkSolveWs w = bk_solve_ws(s->bkmws, s->N);
+    HIP_OK(bk_transpose(s->K, s->ldk, s->N, w.LT, st));
+    HIP_OK(bk_setup(s->K, s->ldk, s->N, s->ipiv, s->binfo, w.LT, w.Lp, w.ldp, w.k, st));
+    rc = bk_multi_impl(s->ctx, s->N, s->K, s->ldk, s->ipiv, w.LT, w.Lp, w.ldp, w.k, B, ldb, nrhs);
+    se = w.k.ctrl + SOLVE_ERR_WORD;
+  }
+  unwatch(s->ctx);  // the workspace is the solver's: checked here, not at a later sync
+  if (rc) return rc;
+  return ws_result(st, s->binfo, s->bkws ? bk_grid_err_word(s->bkws, s->N) : nullptr, se, "ipmz_qp_kkt_solve_bk",
+                   ": a grid barrier of the whole-device Bunch-Kaufman factor timed out; the factor is invalid");
 }
 
 // the QP's mixed-precision workspace, allocated once (a captured step keeps its addresses)

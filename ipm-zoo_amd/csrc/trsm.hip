@@ -21,6 +21,11 @@
 //   forward   T = B[:, J] - sum_{K < J in P} Y[:, K] L_JK^T,  Y[:, J] = T Linv_J^T
 //   backward  T = Z[:, J] - sum_{K > J in P} X[:, K] L_KJ,    X[:, J] = T Linv_J
 //
+// Every panel-solve and update launch takes a gate (a device word, may be
+// null): a non-null gate whose word is not 0 ends the kernel before any load
+// (the Bunch-Kaufman solve's fallback flag, bk.hip); the LDL^T callers pass
+// null.
+//
 // No kernel here waits for another workgroup: right-hand sides are
 // independent, a panel-solve workgroup owns 16 of them, an update workgroup
 // one output tile, and the order between launches is stream order.  No spins,
@@ -210,7 +215,8 @@ __device__ __forceinline__ void cursor_next(const PanelGeom<T>& g, Cursor<T>& c)
 template <typename T, int NBI, bool BWD>
 __global__ __launch_bounds__(TM_NT) void trsm_panel_kernel(const T* __restrict__ K, int64_t ld, int N,
                                                            const T* __restrict__ Linv, int nbi_rt, T* B, int64_t ldb,
-                                                           int nrhs, int p0, int w) {
+                                                           int nrhs, int p0, int w, const unsigned* gate) {
+  if (gate && *gate != 0u) return;
   typedef typename Mfma<T>::vec16_t vec_t;
   typedef typename Mfma<T>::acc_t acc_t;
   constexpr int V = Mfma<T>::V, PADK = TM_PADK<T>;
@@ -340,7 +346,8 @@ struct UpdStage {
 template <typename T, bool NN>
 __global__ __launch_bounds__(UN_NT) void trsm_update_kernel(const T* X, int64_t ldx, const T* __restrict__ L,
                                                             int64_t ldl, T* C, int64_t ldc, int M, int Nc, int Kd,
-                                                            int ntm) {
+                                                            int ntm, const unsigned* gate) {
+  if (gate && *gate != 0u) return;
   typedef typename Mfma<T>::vec16_t vec_t;
   typedef typename Mfma<T>::acc_t acc_t;
   constexpr int V = Mfma<T>::V, BK = 8 * V, PADA = BK + V, BSTAGE = BK * UN_PADB;
@@ -415,16 +422,16 @@ done:
 
 template <typename T, bool NN>
 hipError_t launch_update(const T* X, int64_t ldx, const T* L, int64_t ldl, T* C, int64_t ldc, int M, int Nc, int Kd,
-                         hipStream_t st) {
+                         hipStream_t st, const unsigned* gate) {
   const int ntm = (M + UN_BM - 1) / UN_BM, ntn = (Nc + UN_BN - 1) / UN_BN;
   hipLaunchKernelGGL((trsm_update_kernel<T, NN>), dim3((unsigned)(ntm * ntn)), dim3(UN_NT), 0, st, X, ldx, L, ldl, C,
-                     ldc, M, Nc, Kd, ntm);
+                     ldc, M, Nc, Kd, ntm, gate);
   return hipGetLastError();
 }
 
 template <typename T, bool BWD>
 hipError_t launch_panel(const T* K, int64_t ld, int N, const T* Linv, int nbi, T* B, int64_t ldb, int nrhs, int p0,
-                        int w, hipStream_t st) {
+                        int w, hipStream_t st, const unsigned* gate) {
   constexpr int NBI = PanelNbi<T>;
   // fp64: more than the 64 KB a kernel gets by default; raised once per process
   static const hipError_t attr = hipFuncSetAttribute(
@@ -432,15 +439,15 @@ hipError_t launch_panel(const T* K, int64_t ld, int N, const T* Linv, int nbi, T
       (int)panel_lds_bytes<T>(IPMZ_TRSM_PANEL_MAX, NBI ? NBI : 128));
   if (attr != hipSuccess) return attr;
   hipLaunchKernelGGL((trsm_panel_kernel<T, NBI, BWD>), dim3((nrhs + TM_G - 1) / TM_G), dim3(TM_NT),
-                     panel_lds_bytes<T>(w, nbi), st, K, ld, N, Linv, nbi, B, ldb, nrhs, p0, w);
+                     panel_lds_bytes<T>(w, nbi), st, K, ld, N, Linv, nbi, B, ldb, nrhs, p0, w, gate);
   return hipGetLastError();
 }
 
 }  // namespace
 
 template <typename T>
-hipError_t ldlt_solve_multi(const T* K, int64_t ld, int N, const T* D, const T* Linv, int nbi, T* B, int64_t ldb,
-                            int nrhs, int w, hipStream_t st) {
+hipError_t trsm_sweep(const T* K, int64_t ld, int N, const T* Linv, int nbi, T* B, int64_t ldb, int nrhs, int w,
+                      bool backward, hipStream_t st, const unsigned* gate) {
   if (N <= 0 || nrhs <= 0) return hipSuccess;
   // fp32: the mixed factor (nbi = 64, rows of whole 64-column blocks); leading dimensions in whole vectors
   const bool ok = std::is_same<T, float>::value
@@ -450,26 +457,42 @@ hipError_t ldlt_solve_multi(const T* K, int64_t ld, int N, const T* D, const T* 
       ((uintptr_t)B & 15))
     return hipErrorInvalidValue;
   hipError_t e;
-  for (int p0 = 0; p0 < N; p0 += w) {
-    const int p1 = p0 + w < N ? p0 + w : N;
-    if ((e = launch_panel<T, false>(K, ld, N, Linv, nbi, B, ldb, nrhs, p0, w, st)) != hipSuccess) return e;
-    if (p1 < N &&  // B[:, p1:] -= Y[:, P] L[p1:, P]^T
-        (e = launch_update<T, false>(B + p0, ldb, K + (int64_t)p1 * ld + p0, ld, B + p1, ldb, nrhs, N - p1, p1 - p0,
-                                     st)) != hipSuccess)
-      return e;
+  if (!backward) {
+    for (int p0 = 0; p0 < N; p0 += w) {
+      const int p1 = p0 + w < N ? p0 + w : N;
+      if ((e = launch_panel<T, false>(K, ld, N, Linv, nbi, B, ldb, nrhs, p0, w, st, gate)) != hipSuccess) return e;
+      if (p1 < N &&  // B[:, p1:] -= Y[:, P] L[p1:, P]^T
+          (e = launch_update<T, false>(B + p0, ldb, K + (int64_t)p1 * ld + p0, ld, B + p1, ldb, nrhs, N - p1, p1 - p0,
+                                       st, gate)) != hipSuccess)
+        return e;
+    }
+    return hipSuccess;
   }
-  hipLaunchKernelGGL(trsm_scale_kernel<T>, dim3((N + TM_NT - 1) / TM_NT, nrhs < 64 ? nrhs : 64), dim3(TM_NT), 0, st,
-                     B, ldb, nrhs, N, D);
-  if ((e = hipGetLastError()) != hipSuccess) return e;
   for (int p0 = ((N - 1) / w) * w; p0 >= 0; p0 -= w) {
     const int p1 = p0 + w < N ? p0 + w : N;
-    if ((e = launch_panel<T, true>(K, ld, N, Linv, nbi, B, ldb, nrhs, p0, w, st)) != hipSuccess) return e;
+    if ((e = launch_panel<T, true>(K, ld, N, Linv, nbi, B, ldb, nrhs, p0, w, st, gate)) != hipSuccess) return e;
     if (p0 > 0 &&  // B[:, :p0] -= X[:, P] L[P, :p0]
-        (e = launch_update<T, true>(B + p0, ldb, K + (int64_t)p0 * ld, ld, B, ldb, nrhs, p0, p1 - p0, st)) !=
+        (e = launch_update<T, true>(B + p0, ldb, K + (int64_t)p0 * ld, ld, B, ldb, nrhs, p0, p1 - p0, st, gate)) !=
             hipSuccess)
       return e;
   }
   return hipSuccess;
+}
+template hipError_t trsm_sweep<double>(const double*, int64_t, int, const double*, int, double*, int64_t, int, int,
+                                       bool, hipStream_t, const unsigned*);
+template hipError_t trsm_sweep<float>(const float*, int64_t, int, const float*, int, float*, int64_t, int, int, bool,
+                                      hipStream_t, const unsigned*);
+
+template <typename T>
+hipError_t ldlt_solve_multi(const T* K, int64_t ld, int N, const T* D, const T* Linv, int nbi, T* B, int64_t ldb,
+                            int nrhs, int w, hipStream_t st) {
+  if (N <= 0 || nrhs <= 0) return hipSuccess;
+  hipError_t e = trsm_sweep<T>(K, ld, N, Linv, nbi, B, ldb, nrhs, w, false, st, nullptr);
+  if (e != hipSuccess) return e;
+  hipLaunchKernelGGL(trsm_scale_kernel<T>, dim3((N + TM_NT - 1) / TM_NT, nrhs < 64 ? nrhs : 64), dim3(TM_NT), 0, st,
+                     B, ldb, nrhs, N, D);
+  if ((e = hipGetLastError()) != hipSuccess) return e;
+  return trsm_sweep<T>(K, ld, N, Linv, nbi, B, ldb, nrhs, w, true, st, nullptr);
 }
 template hipError_t ldlt_solve_multi<double>(const double*, int64_t, int, const double*, const double*, int, double*,
                                              int64_t, int, int, hipStream_t);

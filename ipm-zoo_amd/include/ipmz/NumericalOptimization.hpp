@@ -4,6 +4,9 @@
 //   LinearSolvers::ldlt_decomposition      include/NumericalOptimization/LinearSolvers.h:11
 //   LinearSolvers::overwriting_solve_ldlt  LinearSolvers.h:16-17
 //   LinearSolvers::overwriting_solve_ldlt_multi  (the same, one right-hand side per row of a Matrix)
+//   LinearSolvers::symmetric_indefinite_factorization  LinearSolvers.h:23-24
+//   LinearSolvers::overwriting_solve_bunch_kaufman     LinearSolvers.h:29-31
+//   LinearSolvers::overwriting_solve_bunch_kaufman_multi  (the same, one right-hand side per row of a Matrix)
 //   Data, build_environment                EnvironmentBuilder.h:7-20
 //   Optimizer(...).solve()                 Optimizer.h:15-20
 //
@@ -104,6 +107,67 @@ inline void overwriting_solve_ldlt_multi(const Matrix& L, const Vector& D, Matri
   }
   check(ipmz_overwriting_solve_ldlt_multi(ctx.get(), (int)n, flat.data(), D.data(), rhs.data(), (int)nrhs),
         "ipmz_overwriting_solve_ldlt_multi");
+  for (size_t r = 0; r < nrhs; ++r)
+    for (size_t j = 0; j < n; ++j) B[r][j] = rhs[r * n + j];
+}
+
+// Bunch-Kaufman factorization of a symmetric matrix (LinearSolvers.h:23-24):
+// returns F (the matrix with its lower triangle factored) and ipiv in the
+// reference's convention.
+inline std::pair<Matrix, std::vector<int>> symmetric_indefinite_factorization(const Matrix& A,
+                                                                              Context& ctx = Context::instance()) {
+  const size_t n = A.size();
+  std::vector<double> flat(n * n), F(n * n);
+  std::vector<int> ipiv(n);
+  for (size_t i = 0; i < n; ++i) {
+    if (A[i].size() != n) throw AssertionError("symmetric_indefinite_factorization: matrix is not square");
+    for (size_t j = 0; j < n; ++j) flat[i * n + j] = A[i][j];
+  }
+  check(ipmz_symmetric_indefinite_factorization(ctx.get(), (int)n, flat.data(), F.data(), ipiv.data()),
+        "ipmz_symmetric_indefinite_factorization");
+  Matrix Fm(n, Vector(n));
+  for (size_t i = 0; i < n; ++i)
+    for (size_t j = 0; j < n; ++j) Fm[i][j] = F[i * n + j];
+  return {std::move(Fm), std::move(ipiv)};
+}
+
+namespace detail {
+inline std::vector<double> flatten_factor(const Matrix& F, const std::vector<int>& ipiv, size_t n, const char* who) {
+  if (F.size() != n || ipiv.size() != n) throw AssertionError(std::string(who) + ": size mismatch");
+  std::vector<double> flat(n * n);
+  for (size_t i = 0; i < n; ++i) {
+    if (F[i].size() != n) throw AssertionError(std::string(who) + ": F is not square");
+    for (size_t j = 0; j < n; ++j) flat[i * n + j] = F[i][j];
+  }
+  return flat;
+}
+}  // namespace detail
+
+// Solves A x = b from symmetric_indefinite_factorization's F and ipiv,
+// overwriting b (LinearSolvers.h:29-31).  Empty b is a no-op.
+inline void overwriting_solve_bunch_kaufman(const Matrix& F, const std::vector<int>& ipiv, Vector& b,
+                                            Context& ctx = Context::instance()) {
+  if (b.empty()) return;  // LinearSolvers.cpp:212-214
+  const size_t n = b.size();
+  const std::vector<double> flat = detail::flatten_factor(F, ipiv, n, "overwriting_solve_bunch_kaufman");
+  check(ipmz_overwriting_solve_bunch_kaufman(ctx.get(), (int)n, flat.data(), ipiv.data(), b.data()),
+        "ipmz_overwriting_solve_bunch_kaufman");
+}
+
+// The same for a block of right-hand sides, one per row of B, each overwritten
+// with its solution (no reference counterpart).  Empty B is a no-op.
+inline void overwriting_solve_bunch_kaufman_multi(const Matrix& F, const std::vector<int>& ipiv, Matrix& B,
+                                                  Context& ctx = Context::instance()) {
+  if (B.empty() || B[0].empty()) return;
+  const size_t nrhs = B.size(), n = B[0].size();
+  const std::vector<double> flat = detail::flatten_factor(F, ipiv, n, "overwriting_solve_bunch_kaufman_multi");
+  std::vector<double> rhs(nrhs * n);
+  for (size_t r = 0; r < nrhs; ++r) {
+    if (B[r].size() != n) throw AssertionError("overwriting_solve_bunch_kaufman_multi: rows of B differ in length");
+    for (size_t j = 0; j < n; ++j) rhs[r * n + j] = B[r][j];
+  }
+  check(ipmz_overwriting_solve_bunch_kaufman_multi(ctx.get(), (int)n, flat.data(), ipiv.data(), rhs.data(), (int)nrhs),
+        "ipmz_overwriting_solve_bunch_kaufman_multi");
   for (size_t r = 0; r < nrhs; ++r)
     for (size_t j = 0; j < n; ++j) B[r][j] = rhs[r * n + j];
 }

@@ -48,6 +48,8 @@ EXPORTS = [
     "ipmz_overwriting_solve_bunch_kaufman", "ipmz_debug_inject", "ipmz_batch_summary", "ipmz_batch_set_factor_kernel",
     "ipmz_qp_last_step_graph", "ipmz_ldlt_solve_multi", "ipmz_overwriting_solve_ldlt_multi", "ipmz_qp_kkt_solve",
     "ipmz_mixed_multi_workspace_bytes", "ipmz_mixed_solve_multi", "ipmz_sym_residual_multi", "ipmz_qp_kkt_solve_mixed",
+    "ipmz_bk_solve_workspace_bytes", "ipmz_bk_prepare_solve", "ipmz_bk_solve_multi",
+    "ipmz_overwriting_solve_bunch_kaufman_multi", "ipmz_normal_solve_multi", "ipmz_qp_kkt_solve_bk",
 ]
 SOLVE_MULTI_PANEL = 256  # include/ipmz.h IPMZ_SOLVE_MULTI_PANEL: column panel of the blocked multi-rhs solve
 REDUCTION_AUGMENTED, REDUCTION_NORMAL = 0, 1
@@ -160,6 +162,12 @@ def _load():
         "ipmz_mixed_solve_multi": ([_VP, _I, _VP, _I64, _VP, _VP, _I64, _I, ctypes.c_double, _I, _VP, _I64, _P], _I),
         "ipmz_sym_residual_multi": ([_VP, _I, _VP, _I64, _VP, _I64, _VP, _I64, _VP, _I64, _I], _I),
         "ipmz_qp_kkt_solve_mixed": ([_VP, _I, _VP, _I64, ctypes.c_double, _I, _P], _I),
+        "ipmz_bk_solve_workspace_bytes": ([_VP, _I], _I64),
+        "ipmz_bk_prepare_solve": ([_VP, _I, _VP, _I64, _VP, _VP, _I64], _I),
+        "ipmz_bk_solve_multi": ([_VP, _I, _VP, _I64, _VP, _VP, _VP, _I64, _I], _I),
+        "ipmz_overwriting_solve_bunch_kaufman_multi": ([_VP, _I, _P, ctypes.POINTER(ctypes.c_int), _P, _I], _I),
+        "ipmz_normal_solve_multi": ([_VP, _I, _I, _VP, _I64, _VP, _VP, _VP, _I64, _I], _I),
+        "ipmz_qp_kkt_solve_bk": ([_VP, _I, _VP, _I64], _I),
     }
     for name, (args, res) in sig.items():
         fn = getattr(lib, name)
@@ -296,6 +304,19 @@ class Context:
     def bk_solve(self, N, F_ptr, ld, ipiv_ptr, b_ptr):
         return _check(lib.ipmz_bk_solve(self.h, N, _VP(F_ptr), ld, _VP(ipiv_ptr), _VP(b_ptr)), "ipmz_bk_solve")
 
+    def bk_solve_workspace_bytes(self, N):
+        return lib.ipmz_bk_solve_workspace_bytes(self.h, N)
+
+    def bk_prepare_solve(self, N, F_ptr, ld, ipiv_ptr, ws_ptr, ws_bytes):
+        """Once per factor: the prepared solve of bk_solve_multi, built in ws from bk_factor's F and ipiv."""
+        return _check(lib.ipmz_bk_prepare_solve(self.h, N, _VP(F_ptr), ld, _VP(ipiv_ptr), _VP(ws_ptr), ws_bytes),
+                      "ipmz_bk_prepare_solve")
+
+    def bk_solve_multi(self, N, F_ptr, ld, ipiv_ptr, ws_ptr, B_ptr, ldb, nrhs):
+        """Every row of B (device, nrhs rows, stride ldb) <- A^{-1} row, from the prepared solve in ws."""
+        return _check(lib.ipmz_bk_solve_multi(self.h, N, _VP(F_ptr), ld, _VP(ipiv_ptr), _VP(ws_ptr), _VP(B_ptr), ldb,
+                                              nrhs), "ipmz_bk_solve_multi")
+
     # -- normal equations (C2) --
     def normal_workspace_bytes(self, n, mp):
         return lib.ipmz_normal_workspace_bytes(self.h, n, mp)
@@ -307,6 +328,11 @@ class Context:
     def normal_solve(self, n, mp, K_ptr, ld, D_ptr, ws_ptr, b_ptr):
         return _check(lib.ipmz_normal_solve(self.h, n, mp, _VP(K_ptr), ld, _VP(D_ptr), _VP(ws_ptr), _VP(b_ptr)),
                       "ipmz_normal_solve")
+
+    def normal_solve_multi(self, n, mp, K_ptr, ld, D_ptr, ws_ptr, B_ptr, ldb, nrhs):
+        """normal_solve for every row of B (device, nrhs rows, stride ldb)."""
+        return _check(lib.ipmz_normal_solve_multi(self.h, n, mp, _VP(K_ptr), ld, _VP(D_ptr), _VP(ws_ptr), _VP(B_ptr),
+                                                  ldb, nrhs), "ipmz_normal_solve_multi")
 
 
 def debug_inject(mask):
@@ -401,8 +427,25 @@ def overwriting_solve_bunch_kaufman(F, ipiv, b, ctx=None):
            "ipmz_overwriting_solve_bunch_kaufman")
 
 
+def overwriting_solve_bunch_kaufman_multi(F, ipiv, B, ctx=None):
+    """overwriting_solve_bunch_kaufman for a block of right-hand sides: B is a
+    C-contiguous float64 (nrhs, N) array, one right-hand side per row,
+    overwritten with the solutions and returned."""
+    F = np.ascontiguousarray(F, dtype=np.float64)
+    ipiv = np.ascontiguousarray(ipiv, dtype=np.int32)
+    if not (isinstance(B, np.ndarray) and B.dtype == np.float64 and B.ndim == 2 and B.flags.c_contiguous):
+        raise IpmzError("overwriting_solve_bunch_kaufman_multi: B must be a C-contiguous float64 (nrhs, N) array")
+    nrhs, N = B.shape
+    if F.shape != (N, N) or ipiv.shape != (N,):
+        raise IpmzError("overwriting_solve_bunch_kaufman_multi: size mismatch")
+    _check(lib.ipmz_overwriting_solve_bunch_kaufman_multi((ctx or default_context()).h, N, _dp(F), _ip(ipiv), _dp(B),
+                                                          nrhs), "ipmz_overwriting_solve_bunch_kaufman_multi")
+    return B
+
+
 LinearSolvers.symmetric_indefinite_factorization = staticmethod(symmetric_indefinite_factorization)
 LinearSolvers.overwriting_solve_bunch_kaufman = staticmethod(overwriting_solve_bunch_kaufman)
+LinearSolvers.overwriting_solve_bunch_kaufman_multi = staticmethod(overwriting_solve_bunch_kaufman_multi)
 
 
 class Data:
@@ -531,6 +574,11 @@ class Optimizer:
         K^{-1} row with the KKT matrix of the current iterate (kkt()); returns
         the factor's info.  Single QPs on the fp64 augmented LDL^T only."""
         return _check(lib.ipmz_qp_kkt_solve(self.h, nrhs, _VP(B_ptr), ldb), "ipmz_qp_kkt_solve")
+
+    def kkt_solve_bk(self, B_ptr, nrhs, ldb):
+        """kkt_solve for single QPs with EqualityHandling::None: the step's Bunch-Kaufman
+        factor, then bk_solve_multi on the rows of B; returns the factor's info."""
+        return _check(lib.ipmz_qp_kkt_solve_bk(self.h, nrhs, _VP(B_ptr), ldb), "ipmz_qp_kkt_solve_bk")
 
     def kkt_solve_mixed(self, B_ptr, nrhs, ldb, tol=1e-12, max_refine=10):
         """kkt_solve through the fp32 factor + fp64 refinement, whether or not the steps use mixed
