@@ -27,6 +27,11 @@
  *                               <- no reference counterpart: overwriting_solve_bunch_kaufman
  *                                  and the normal-equations solve for a block of right-hand
  *                                  sides, on the same blocked triangular solve
+ *   ipmz_batch_get_kkt, ipmz_batch_kkt_solve
+ *                               <- no reference counterpart: the KKT matrix of any QP of
+ *                                  a batch, and ipmz_qp_kkt_solve for every QP of a batch at
+ *                                  once (one launch per batch where a QP's right-hand sides
+ *                                  fit a workgroup's LDS)
  *   ipmz_qp_create + ipmz_qp_load_host
  *                               <- NumericalOptimization::build_environment
  *                                  (EnvironmentBuilder.h:19-20, EnvironmentBuilder.cpp:7-76)
@@ -413,7 +418,8 @@ int ipmz_qp_kkt_dim(ipmz_qp* qp);
  * ipmz_ldlt_solve_multi does.  Returns the factor's info like
  * ipmz_ldlt_factor (synchronizes).  Leaves the iterate and all later steps
  * unchanged.  For single QPs whose step factors the augmented system with
- * fp64 LDL^T: IPMZ_ERR_INVALID for batches, IPMZ_EQ_NONE (Bunch-Kaufman), an
+ * fp64 LDL^T: IPMZ_ERR_INVALID for batches (their call is
+ * ipmz_batch_kkt_solve), IPMZ_EQ_NONE (Bunch-Kaufman), an
  * enabled normal-equations reduction or mixed-precision mode.  The Newton
  * step itself is untouched: its two solves depend on each other and stay
  * single-vector.  The mixed-precision form is ipmz_qp_kkt_solve_mixed. */
@@ -499,6 +505,51 @@ int ipmz_batch_solve(ipmz_qp* qp, int max_iter, int* iterations, int* converged_
 #define IPMZ_BATCH_FACTOR_PAIR 2
 #define IPMZ_BATCH_FACTOR_LEFT 3
 int ipmz_batch_set_factor_kernel(ipmz_qp* qp, int kernel);
+/* ipmz_qp_get_kkt for QP `index` of a batch: host N x N row-major, lower triangle
+ * written, upper zero.  index out of range: IPMZ_ERR_INVALID.  (ipmz_qp_get_kkt
+ * on a batch addresses QP 0.) */
+int ipmz_batch_get_kkt(ipmz_qp* qp, int index, double* host_K);
+/* For every QP q of the batch: assemble the KKT matrix of its current iterate
+ * (the matrix ipmz_batch_get_kkt returns), factor it (the step's own batched
+ * assembly and factor, on the storage the next step overwrites anyway) and
+ * solve the nrhs rows at B + q * sB (device, Newton order, row stride ldb) in
+ * place: row <- K_q^{-1} row.
+ *
+ * Arguments: ldb >= N and even; sB >= nrhs * ldb and even; B 16-byte aligned;
+ * nrhs >= 0 (nrhs == 0 still assembles and factors and returns the info word).
+ * Only the first N elements of each of the nrhs rows of a QP are written:
+ * B[q][r][N .. ldb) and everything between nrhs * ldb and sB keep their bits.
+ * A contiguous (batch, nrhs, ldb) array has sB = nrhs * ldb.
+ *
+ * Served: batches whose step factors the augmented system with fp64 LDL^T --
+ * every equality and inequality handling except IPMZ_EQ_NONE, any N, inner
+ * blocks (ipmz_ctx_set_blocking) of 64 and 128.  IPMZ_EQ_NONE batches factor
+ * with Bunch-Kaufman and return IPMZ_ERR_INVALID.  A solver that holds one QP
+ * (ipmz_qp_create, or ipmz_batch_create with batch 1) forwards to
+ * ipmz_qp_kkt_solve; sB is then ignored.  IPMZ_ERR_STATE between a load and
+ * ipmz_batch_initialize, and while the context's stream is capturing (the
+ * call synchronizes).
+ *
+ * Returns the batched factor's info word as a step sees it: ONE word for the
+ * whole batch, IPMZ_OK when every pivot of every QP was finite, otherwise the
+ * smallest 1-based pivot index at which any QP met a non-finite pivot (which
+ * QP is not recorded; the rows of the other QPs are still their solutions).
+ * IPMZ_ERR_HIP when the two-workgroup batched factor ran and a hand-off in it
+ * timed out (its sticky error word).
+ *
+ * The iterate, the matrix the fused steps keep across steps, a captured step
+ * graph (IPMZ_STEP_GRAPH) and all later steps are unchanged, bitwise.  Only
+ * stream-ordered launches, no cross-workgroup waiting and no atomics in the
+ * solve: a row's result does not depend on the other rows of the call, a QP's
+ * not on the other QPs of the batch (given the same kernel selection, which
+ * depends on N, the inner block, nrhs and -- through the single-vector
+ * kernels below the crossover -- the batch size), and equal inputs give equal
+ * bits.  Few right-hand sides run through the step's single-vector batched
+ * solve row by row, more through one blocked launch per batch (systems whose
+ * 16 right-hand sides fit a workgroup's LDS: N <= 832 with inner block 64,
+ * <= 768 with 128, on 160 KiB) or the panel chain of ipmz_ldlt_solve_multi
+ * with the QP on a grid dimension. */
+int ipmz_batch_kkt_solve(ipmz_qp* qp, int nrhs, double* B, int64_t ldb, int64_t sB);
 
 /* Phase timing (HIP events on the context stream; eager launches only).
  * ms: host array of IPMZ_PH_COUNT floats, cumulative since enable. */

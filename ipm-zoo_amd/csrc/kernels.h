@@ -42,7 +42,10 @@ namespace ipmz {
 //         solves below the crossover) (A/B, tools/solve_multi_bench.py); ipmz_mixed_solve_multi and
 //         ipmz_qp_kkt_solve_mixed likewise (tools/mixed_multi_bench.py), and ipmz_normal_solve_multi,
 //         ipmz_bk_solve_multi and ipmz_qp_kkt_solve_bk (tools/bk_multi_bench.py),
-// 131072 / 262144 = ... with 512- / 128-column panels instead of IPMZ_SOLVE_MULTI_PANEL (A/B),
+//         and ipmz_batch_kkt_solve (tools/batch_multi_bench.py),
+// 131072 / 262144 = ... with 512- / 128-column panels instead of IPMZ_SOLVE_MULTI_PANEL (A/B); in
+//         ipmz_batch_kkt_solve either bit also selects the panel chain where the one-launch solve is
+//         eligible, and both together the panel chain at IPMZ_SOLVE_MULTI_PANEL,
 // 524288 / 1048576 = the persistent solve splits every 128-row block over 2 / 4 workgroups, whatever
 //         its table says; both bits = the unsplit solve (all three bitwise alike,
 //         tests/test_gpu_solve_split.py)
@@ -194,16 +197,33 @@ hipError_t ldlt_solve(const double* K, int64_t ld, int N, const double* D, const
 //   float   the fp32 factor of the mixed-precision path (nbi == 64): ld a
 //           multiple of 64, ldb of 4, K / Linv / B 16-byte aligned.
 #define IPMZ_TRSM_PANEL_MAX 512
+// A batch of B systems of one order behind the same launches (fp64 only): a
+// grid dimension is the system, and K, D, Linv and the right-hand sides of
+// consecutive systems lie sK, sD, sL and sB elements apart (sK, sL, sB even:
+// the 16-byte loads).  The default is one system.
+struct TrsmBatch {
+  int B = 1;
+  int64_t sK = 0, sD = 0, sL = 0, sB = 0;
+};
 template <typename T>
 hipError_t ldlt_solve_multi(const T* K, int64_t ld, int N, const T* D, const T* Linv, int nbi, T* B, int64_t ldb,
-                            int nrhs, int w, hipStream_t st);
+                            int nrhs, int w, hipStream_t st, const TrsmBatch& tb = TrsmBatch());
 
 // one of its sweeps alone: forward B <- B L^{-T}, backward B <- B L^{-1} (the
 // middle stage is the caller's; same argument rules).  gate (device word, may
 // be null): when set, every launch ends at once if *gate != 0
 template <typename T>
 hipError_t trsm_sweep(const T* K, int64_t ld, int N, const T* Linv, int nbi, T* B, int64_t ldb, int nrhs, int w,
-                      bool backward, hipStream_t st, const unsigned* gate);
+                      bool backward, hipStream_t st, const unsigned* gate, const TrsmBatch& tb = TrsmBatch());
+
+// The whole fp64 solve of small systems in ONE launch: a workgroup keeps 16
+// right-hand sides of one system in LDS through the forward sweep, the division
+// by D and the backward sweep (B read once and written once, L once per sweep).
+// Eligible when the 16 x round_up(N, nbi) slab, T and the stage buffers fit
+// the LDS of a workgroup on this device; same argument rules as above.
+bool ldlt_solve_fused_eligible(int N, int nbi);
+hipError_t ldlt_solve_fused(const double* K, int64_t ld, int N, const double* D, const double* Linv, int nbi,
+                            double* B, int64_t ldb, int nrhs, hipStream_t st, const TrsmBatch& tb = TrsmBatch());
 
 // one workgroup per QP of a batch (small N); b: batch of rhs, stride sb
 hipError_t ldlt_solve_batched(const double* K, int64_t ld, int N, const double* D, const double* Linv, int nbi,

@@ -432,7 +432,12 @@ int create_solver(ipmz_ctx* ctx, const ipmz_qp_config* cfg, int B, ipmz_qp** out
     s->ws = dev_alloc<char>(s, (size_t)s->ws_bytes, true);
   } else {
     const int64_t nblk = (N + ctx->nbi - 1) / ctx->nbi;
-    s->bLinv = dev_array(s, nblk * ctx->nbi * ctx->nbi, &s->sL);
+    // zeroed once: the wave-specialized small factor writes only the lower
+    // triangle of every inverse (the step's single-vector solve reads no
+    // more), and no factor writes a nonzero above the diagonal; the blocked
+    // multi-right-hand-side solve (ipmz_batch_kkt_solve, trsm.hip) reads whole
+    // blocks and needs the zeros there, as a single QP's workspace has them
+    s->bLinv = dev_array(s, nblk * ctx->nbi * ctx->nbi, &s->sL, true);
     s->bW = dev_array(s, (int64_t)N * nbo_for(ctx, N), &s->sW);
     s->binfo = dev_alloc<int>(s, B > 64 ? B : 64, false);  // one info per QP
     // flags of the two-workgroup small factor (B <= #CU)
@@ -905,9 +910,112 @@ int ipmz_qp_get_kkt(ipmz_qp* s, double* out) {
   return IPMZ_OK;
 }
 
+int ipmz_batch_get_kkt(ipmz_qp* s, int index, double* out) {
+  int rc = check_index(s, index);
+  if (rc) return rc;
+  if (!out) return fail(IPMZ_ERR_INVALID, "bad arguments");
+  HIP_OK(hipSetDevice(s->ctx->device));
+  hipStream_t st = s->ctx->stream;
+  // (the whole matrix of every QP into K, as the non-fused step's assembly: the kept K0 is not touched)
+  HIP_OK(qp_assemble(s->qb, st));
+  HIP_OK(hipMemcpy2DAsync(out, (size_t)s->N * 8, s->hq[index].K, s->ldk * 8, (size_t)s->N * 8, s->N,
+                          hipMemcpyDeviceToHost, st));
+  HIP_OK(hipStreamSynchronize(st));
+  for (int i = 0; i < s->N; ++i)
+    for (int j = i + 1; j < s->N; ++j) out[(int64_t)i * s->N + j] = 0.0;
+  return IPMZ_OK;
+}
+
+// Batched multi-right-hand-side solve (trsm.hip): which of the three paths
+// serves nrhs rows per QP.
+//
+// BATCH_MULTI_CROSSOVER: the number of right-hand sides from which the blocked
+// paths run; below it every row is one launch of the step's own batched
+// single-vector solve (ldlt_solve_batched), all QPs at once.  From
+// tools/batch_multi_bench.py (profiles/batch_multi/bench.json, DESIGN.md
+// "Batched multi-right-hand-side solve"), solve alone = call(nrhs) - call(0):
+// a looped row costs 0.148 ms (C4, N = 320, batch 1024) / 0.032 ms (batch
+// 128), the one-launch solve 0.256 / 0.060 ms for up to 16 rows, so they break
+// even at 1.7 / 1.9 rows.  At 2 rows the blocked path leads by 1.12x at batch
+// 1024 but by 0.005 ms at batch 128, inside the loop's spread there (0.007
+// ms); 4 is the first measured count at which it leads by more than the
+// spread at both (2.3x / 2.2x).  3 rows were not measured (the loop would
+// cost 0.44 / 0.10 ms against about 0.26 / 0.06): they stay looped.
+//
+// Fused or panels: where a QP's slab fits the LDS the one-launch solve is
+// never slower than the panel chain at both C4 batch sizes (at 16 rows 0.28 vs
+// 0.39-0.46 ms and 0.06 vs 0.08-0.12 ms), so eligibility alone decides.  Only
+// at 128 rows and batch 1024 (and N = 832, batch 128) do 128-column panels
+// lead it, by 4-6 %; at batch 128 they lose by 16 %.
+static constexpr int BATCH_MULTI_CROSSOVER = 4;
+
+static int batch_multi_impl(ipmz_qp* s, double* B, int64_t ldb, int64_t sB, int nrhs) {
+  hipStream_t st = s->ctx->stream;
+  const int dbg = debug_inject_mask(), nbi = s->ctx->nbi;
+  if (nrhs < BATCH_MULTI_CROSSOVER && !(nrhs >= 2 && (dbg & IPMZ_DEBUG_MULTI_BLOCKED))) {
+    for (int r = 0; r < nrhs; ++r)
+      HIP_OK(ldlt_solve_batched(s->K, s->ldk, s->N, s->D, s->bLinv, nbi, B + (int64_t)r * ldb, s->B, s->sK, s->sD,
+                                s->sL, sB, st));
+    return IPMZ_OK;
+  }
+  TrsmBatch tb;
+  tb.B = s->B;
+  tb.sK = s->sK;
+  tb.sD = s->sD;
+  tb.sL = s->sL;
+  tb.sB = sB;
+  // one launch per batch where a system's slab fits a workgroup's LDS, unless
+  // a panel width is forced; else the panel chain over all QPs
+  if (!(dbg & (IPMZ_DEBUG_MULTI_W128 | IPMZ_DEBUG_MULTI_W512)) && ldlt_solve_fused_eligible(s->N, nbi)) {
+    HIP_OK(ldlt_solve_fused(s->K, s->ldk, s->N, s->D, s->bLinv, nbi, B, ldb, nrhs, st, tb));
+    return IPMZ_OK;
+  }
+  // (both width bits together: the panel chain at its default width, for tools/batch_multi_bench.py)
+  const bool w512 = dbg & IPMZ_DEBUG_MULTI_W512, w128 = dbg & IPMZ_DEBUG_MULTI_W128;
+  const int pw = w512 && w128 ? IPMZ_SOLVE_MULTI_PANEL : w512 ? 512 : w128 ? 128 : IPMZ_SOLVE_MULTI_PANEL;
+  HIP_OK(ldlt_solve_multi<double>(s->K, s->ldk, s->N, s->D, s->bLinv, nbi, B, ldb, nrhs, pw, st, tb));
+  return IPMZ_OK;
+}
+
+int ipmz_batch_kkt_solve(ipmz_qp* s, int nrhs, double* B, int64_t ldb, int64_t sB) {
+  if (!s) return fail(IPMZ_ERR_INVALID, "null qp");
+  if (s->B == 1) return ipmz_qp_kkt_solve(s, nrhs, B, ldb);
+  if (s->eqnone)
+    return fail(IPMZ_ERR_INVALID, "ipmz_batch_kkt_solve: EqualityHandling::None batches factor with Bunch-Kaufman, "
+                                  "which has no batched multi-right-hand-side solve (fp64 LDL^T batches only)");
+  if (s->normal || s->mixed)
+    return fail(IPMZ_ERR_INVALID, "ipmz_batch_kkt_solve: fp64 augmented LDL^T batches only");
+  if (!s->loaded) return fail(IPMZ_ERR_STATE, "ipmz_batch_kkt_solve: load and initialize the batch first");
+  if (nrhs < 0 || ldb < s->N || (ldb & 1) || sB < (int64_t)nrhs * ldb || (sB & 1) || (nrhs > 0 && !B))
+    return fail(IPMZ_ERR_INVALID, "ipmz_batch_kkt_solve: bad arguments (nrhs >= 0, ldb >= N and even, sB >= nrhs * "
+                                  "ldb and even)");
+  if (nrhs > 0 && ((uintptr_t)B & 15)) return fail(IPMZ_ERR_INVALID, "ipmz_batch_kkt_solve: B must be 16-byte aligned");
+  HIP_OK(hipSetDevice(s->ctx->device));
+  int rc = not_capturing(s->ctx, "ipmz_batch_kkt_solve");
+  if (rc) return rc;
+  hipStream_t st = s->ctx->stream;
+  // (no forked step to wait for: step_forks is false for batches)
+  // The step's own assembly and factor, on the storage the next step
+  // overwrites anyway: the whole matrix of every QP goes into K and is
+  // factored there in place (factor_batch without K0), as the non-fused step
+  // does.  The fused step's kept matrix K0 -- its off-diagonal part written
+  // once per load -- is neither read nor written; that step rewrites K0's
+  // diagonal and all of L in K itself.  The iterate is only read.
+  HIP_OK(qp_assemble(s->qb, st));
+  if ((rc = factor_batch(s, nullptr, false))) return rc;
+  if ((rc = batch_multi_impl(s, B, ldb, sB, nrhs))) return rc;
+  // the info word, and the sticky error word of the two-workgroup factor where
+  // it ran (qp_status's rule); synchronizes
+  const bool pair = s->ctx->nbi == 64 && small_pair_used(s->small_kernel, s->pflags != nullptr, s->B, s->N);
+  return ws_result(st, s->binfo, pair ? s->pflags + (size_t)s->B * IPMZ_PAIR_FLAGS : nullptr, nullptr,
+                   "ipmz_batch_kkt_solve",
+                   ": a hand-off of the two-workgroup batched factor timed out; the factor is invalid");
+}
+
 int ipmz_qp_kkt_solve(ipmz_qp* s, int nrhs, double* B, int64_t ldb) {
   if (!s) return fail(IPMZ_ERR_INVALID, "null qp");
-  if (s->B != 1) return fail(IPMZ_ERR_INVALID, "ipmz_qp_kkt_solve: single QPs only, this is a batch");
+  if (s->B != 1)
+    return fail(IPMZ_ERR_INVALID, "ipmz_qp_kkt_solve: single QPs only, this is a batch (ipmz_batch_kkt_solve)");
   if (s->eqnone)
     return fail(IPMZ_ERR_INVALID, "ipmz_qp_kkt_solve: EqualityHandling::None factors with Bunch-Kaufman: its "
                                   "multi-right-hand-side solve is ipmz_qp_kkt_solve_bk");

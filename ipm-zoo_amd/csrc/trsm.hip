@@ -21,6 +21,14 @@
 //   forward   T = B[:, J] - sum_{K < J in P} Y[:, K] L_JK^T,  Y[:, J] = T Linv_J^T
 //   backward  T = Z[:, J] - sum_{K > J in P} X[:, K] L_KJ,    X[:, J] = T Linv_J
 //
+// A batch of systems of one order (TrsmBatch, fp64) runs behind the same
+// launches: the system is a grid dimension of every kernel, and K, D, Linv and
+// B advance by per-system strides; one system is a grid of height 1 and zero
+// strides.  Small systems have a whole-solve kernel besides
+// (trsm_fused_kernel, ldlt_solve_fused): all N columns as ONE panel whose slab
+// goes through the forward stream, the division by D and the backward stream
+// without leaving LDS -- one launch per batch.
+//
 // Every panel-solve and update launch takes a gate (a device word, may be
 // null): a non-null gate whose word is not 0 ends the kernel before any load
 // (the Bunch-Kaufman solve's fallback flag, bk.hip); the LDL^T callers pass
@@ -205,6 +213,124 @@ __device__ __forceinline__ void cursor_next(const PanelGeom<T>& g, Cursor<T>& c)
   }
 }
 
+// The 16 x w slab of B[r0 .. r0 + 16, p0 .. p0 + w) <-> LDS (row stride SP);
+// rows >= nrhs and columns >= p1 are zero in LDS and never stored.
+template <typename T>
+__device__ __forceinline__ void slab_load(const T* B, int64_t ldb, int nrhs, int r0, int p0, int p1, int w, T* slab,
+                                          int SP) {
+  typedef typename Mfma<T>::vec16_t vec_t;
+  constexpr int V = Mfma<T>::V;
+  const int vw = w / V;
+  for (int idx = threadIdx.x; idx < TM_G * vw; idx += TM_NT) {
+    const int r = idx / vw, c = (idx % vw) * V;
+    const bool rok = r0 + r < nrhs;
+    const vec_t v = fetch16(B + (int64_t)(r0 + r) * ldb + p0 + c, B + (int64_t)r0 * ldb + p0, rok && p0 + c < p1,
+                            p1 - p0 - c);
+    *reinterpret_cast<vec_t*>(&slab[r * SP + c]) = v;
+  }
+}
+template <typename T>
+__device__ __forceinline__ void slab_store(T* B, int64_t ldb, int nrhs, int r0, int p0, int p1, int w, const T* slab,
+                                           int SP) {
+  typedef typename Mfma<T>::vec16_t vec_t;
+  constexpr int V = Mfma<T>::V;
+  const int vw = w / V;
+  for (int idx = threadIdx.x; idx < TM_G * vw; idx += TM_NT) {
+    const int r = idx / vw, c = (idx % vw) * V;
+    if (r0 + r >= nrhs || p0 + c >= p1) continue;
+    T* dst = B + (int64_t)(r0 + r) * ldb + p0 + c;
+    const T* src = &slab[r * SP + c];
+    if (p0 + c + V - 1 < p1) *reinterpret_cast<vec_t*>(dst) = *reinterpret_cast<const vec_t*>(src);
+    else
+      for (int e = 0; p0 + c + e < p1; ++e) dst[e] = src[e];
+  }
+}
+
+// One sweep of the stream over the panel g, on a slab that stays in LDS: both
+// sweeps of trsm_fused_kernel.  It is trsm_panel_kernel's stream, statement by
+// statement, as a device function; that kernel keeps its own inline copy,
+// because built from this function its instantiations take 3-4 more VGPRs and
+// drop one wave of occupancy each (fp64 118 / 120 -> 122 / 123 with 8 AGPRs,
+// occupancy 4 -> 3; fp32 66 / 67 -> 70 / 69, 7 -> 6; DESIGN.md "Batched
+// multi-right-hand-side solve").  A change to one belongs in the other.  One
+// barrier per chunk: chunk c is written to LDS buffer c & 1, the barrier
+// passed, the ring slot refilled with chunk c + TM_PD, chunk c multiplied; a
+// product's result is written (T, or the slab) right after its last chunk, one
+// barrier before anything reads it.  fill(): whatever has to reach the slab
+// before the first product (the load of B; nothing when the slab already holds
+// the sweep's input), issued behind the ring's first loads; a barrier follows
+// it, and one ends the sweep.  NBI: the inner block as a constant, or 0 for
+// g.nbi.
+template <typename T, int NBI, bool BWD, typename Fill>
+__device__ __forceinline__ void panel_stream(const PanelGeom<T>& g, T* slab, T* Ts, T* Ls, Fill&& fill) {
+  typedef typename Mfma<T>::acc_t acc_t;
+  constexpr int PADK = TM_PADK<T>;
+  const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
+  const int nbi = g.nbi, p0 = g.p0, p1 = g.p1, SP = g.SP, TP = g.TP;
+
+  // the stream starts at phase 1 of the first block (its phase 0 is empty: T = B[:, J])
+  const int jfirst = BWD ? p0 + ((p1 - p0 - 1) / nbi) * nbi : p0;
+  Cursor<T> cc;
+  cc.j0 = jfirst;
+  cc.phase = 1;
+  cc.u = 0;
+  cc.t = 0;
+  cc.valid = true;
+  cc.p = panel_prod<T, BWD>(g, jfirst, 1, 0);
+  cc.nch = (cc.p.kd + TM_BK - 1) / TM_BK;
+  Cursor<T> lc = cc;
+  OpStage<T, BWD> ring[TM_PD];
+  // (past the end of the stream the ring still loads -- all lanes masked, the
+  // product's first element -- and never branches around a load: only then
+  // does the compiler keep the later slots in flight behind counted waits)
+#pragma unroll
+  for (int d = 0; d < TM_PD; ++d) {
+    ring[d].load(lc.p.M, lc.p.ldm, lc.valid ? lc.p.nlim : 0, lc.p.kd, lc.t * TM_BK);
+    if (lc.valid) cursor_next<T, NBI, BWD>(g, lc);
+  }
+
+  fill();
+  __syncthreads();
+  for (int idx = tid; idx < TM_G * TP; idx += TM_NT) {
+    const int r = idx / TP, c = idx % TP;
+    Ts[idx] = c < nbi ? slab[r * SP + (jfirst - p0) + c] : T(0);
+  }
+
+  const int col = 16 * wave + (lane & 15);  // this lane's column inside a sub-block
+  const int frag = BWD ? (lane >> 4) * TM_PADN + col : col * PADK + (lane >> 4);
+  acc_t acc = {T(0), T(0), T(0), T(0)};
+  int buf = 0;
+  for (;;) {
+#pragma unroll
+    for (int d = 0; d < TM_PD; ++d) {
+      if (!cc.valid) goto done;
+      T* bs = Ls + buf * TM_STAGE;
+      ring[d].store(bs);
+      __syncthreads();
+      ring[d].load(lc.p.M, lc.p.ldm, lc.valid ? lc.p.nlim : 0, lc.p.kd, lc.t * TM_BK);
+      if (lc.valid) cursor_next<T, NBI, BWD>(g, lc);
+      const T* As = (cc.phase == 0 ? slab : Ts) + cc.p.aofs + (lane & 15) * cc.p.lda + (lane >> 4) + cc.t * TM_BK;
+#pragma unroll
+      for (int s = 0; s < TM_BK / 4; ++s)
+        acc = Mfma<T>::mma(As[4 * s], bs[frag + (BWD ? 4 * s * TM_PADN : 4 * s)], acc);
+      if (cc.t == cc.nch - 1) {
+        const int so = cc.j0 - p0 + TM_SB * cc.u + col;  // slab column
+#pragma unroll
+        for (int r = 0; r < 4; ++r) {
+          const int row = Mfma<T>::row(lane, r);
+          if (cc.phase == 0) Ts[row * TP + TM_SB * cc.u + col] = slab[row * SP + so] - acc[r];
+          else slab[row * SP + so] = acc[r];
+        }
+        acc = (acc_t){T(0), T(0), T(0), T(0)};
+      }
+      cursor_next<T, NBI, BWD>(g, cc);
+      buf ^= 1;
+    }
+  }
+done:
+  __syncthreads();
+}
+
 // Panel solve of columns [p0, min(p0 + w, N)) for right-hand sides
 // [16 * blockIdx.x, +16): the slab lives in LDS from the first load to the
 // last store.  One barrier per chunk: chunk c is written to LDS buffer c & 1,
@@ -215,8 +341,12 @@ __device__ __forceinline__ void cursor_next(const PanelGeom<T>& g, Cursor<T>& c)
 template <typename T, int NBI, bool BWD>
 __global__ __launch_bounds__(TM_NT) void trsm_panel_kernel(const T* __restrict__ K, int64_t ld, int N,
                                                            const T* __restrict__ Linv, int nbi_rt, T* B, int64_t ldb,
-                                                           int nrhs, int p0, int w, const unsigned* gate) {
+                                                           int nrhs, int p0, int w, const unsigned* gate, int64_t sK,
+                                                           int64_t sL, int64_t sB) {
   if (gate && *gate != 0u) return;
+  K += blockIdx.y * sK;
+  Linv += blockIdx.y * sL;
+  B += blockIdx.y * sB;
   typedef typename Mfma<T>::vec16_t vec_t;
   typedef typename Mfma<T>::acc_t acc_t;
   constexpr int V = Mfma<T>::V, PADK = TM_PADK<T>;
@@ -312,12 +442,54 @@ done:
   }
 }
 
-// between the sweeps: B[r][j] /= D[j] (a division, LinearSolvers.cpp:62-64)
+// The whole solve of one small system in one workgroup (fp64): right-hand
+// sides [16 * blockIdx.x, +16) of system blockIdx.y, all N columns as one
+// "panel" of width round_up(N, nbi).  The slab is loaded once, passes through
+// the forward sweep, the division by D and the backward sweep in LDS, and is
+// stored once; L is read once per sweep.  No other workgroup is waited for.
+// NBI: 64 = the inner block as a constant (one sub-block, as the fp32 panel
+// solve's), 0 = nbi_rt (128).
+template <int NBI>
+__global__ __launch_bounds__(TM_NT) void trsm_fused_kernel(const double* __restrict__ K, int64_t ld, int N,
+                                                           const double* __restrict__ D,
+                                                           const double* __restrict__ Linv, int nbi_rt, double* B,
+                                                           int64_t ldb, int nrhs, int64_t sK, int64_t sD, int64_t sL,
+                                                           int64_t sB) {
+  constexpr int V = Mfma<double>::V;
+  static_assert(NBI == 0 || NBI == TM_SB, "a constant inner block is one sub-block");
+  const int nbi = NBI ? NBI : nbi_rt;
+  extern __shared__ __attribute__((aligned(16))) unsigned char trsm_sm[];
+  K += blockIdx.y * sK;
+  D += blockIdx.y * sD;
+  Linv += blockIdx.y * sL;
+  B += blockIdx.y * sB;
+  const int w = (N + nbi - 1) / nbi * nbi;
+  const int SP = w + V, TP = nbi + V;
+  double* slab = reinterpret_cast<double*>(trsm_sm);
+  double* Ts = slab + TM_G * SP;
+  double* Ls = Ts + TM_G * TP;
+  const int r0 = blockIdx.x * TM_G;
+  const PanelGeom<double> g = {K, ld, N, Linv, nbi, 0, N, SP, TP};
+  panel_stream<double, NBI, false>(g, slab, Ts, Ls, [&] { slab_load<double>(B, ldb, nrhs, r0, 0, N, w, slab, SP); });
+  // Z = Y / D (a division, as trsm_scale_kernel; rows past nrhs are zero and never stored)
+  for (int j = threadIdx.x; j < N; j += TM_NT) {
+    const double d = D[j];
+#pragma unroll 4
+    for (int r = 0; r < TM_G; ++r) slab[r * SP + j] = slab[r * SP + j] / d;
+  }
+  panel_stream<double, NBI, true>(g, slab, Ts, Ls, [] {});  // (its first barrier orders the division before T)
+  slab_store<double>(B, ldb, nrhs, r0, 0, N, w, slab, SP);
+}
+
+// between the sweeps: B[r][j] /= D[j] (a division, LinearSolvers.cpp:62-64);
+// system blockIdx.z (strides sB, sD)
 template <typename T>
 __global__ __launch_bounds__(TM_NT) void trsm_scale_kernel(T* B, int64_t ldb, int nrhs, int N,
-                                                           const T* __restrict__ D) {
+                                                           const T* __restrict__ D, int64_t sB, int64_t sD) {
   const int j = blockIdx.x * TM_NT + threadIdx.x;
   if (j >= N) return;
+  B += blockIdx.z * sB;
+  D += blockIdx.z * sD;
   const T d = D[j];
   for (int r = blockIdx.y; r < nrhs; r += gridDim.y) {
     T* p = B + (int64_t)r * ldb + j;
@@ -337,7 +509,7 @@ __global__ __launch_bounds__(TM_NT) void trsm_scale_kernel(T* B, int64_t ldb, in
 // deep, so a tile is a short serial chain and nothing else hides its
 // latencies.  The L tile is staged [j][k] (NT) or [k][j] (NN).  Workgroups
 // that share an L tile (the right-hand-side groups of one column tile) have
-// consecutive ids.
+// consecutive ids.  System blockIdx.y: X and C advance by sX, L by sL.
 constexpr int UN_NT = 512, UN_BM = 64, UN_BN = 64, UN_PADB = UN_BN + 16, UN_PD = 3;
 template <typename T>
 struct UpdStage {
@@ -346,11 +518,14 @@ struct UpdStage {
 template <typename T, bool NN>
 __global__ __launch_bounds__(UN_NT) void trsm_update_kernel(const T* X, int64_t ldx, const T* __restrict__ L,
                                                             int64_t ldl, T* C, int64_t ldc, int M, int Nc, int Kd,
-                                                            int ntm, const unsigned* gate) {
+                                                            int ntm, const unsigned* gate, int64_t sX, int64_t sL) {
   if (gate && *gate != 0u) return;
   typedef typename Mfma<T>::vec16_t vec_t;
   typedef typename Mfma<T>::acc_t acc_t;
   constexpr int V = Mfma<T>::V, BK = 8 * V, PADA = BK + V, BSTAGE = BK * UN_PADB;
+  X += blockIdx.y * sX;
+  C += blockIdx.y * sX;
+  L += blockIdx.y * sL;
   static_assert(BSTAGE >= UN_BN * PADA, "B stage buffer holds either form");
   static_assert(UN_BM * BK / V == UN_NT && BK * UN_BN / V == UN_NT, "one vector of each operand per thread");
   __shared__ __attribute__((aligned(16))) T As[2][UN_BM * PADA];
@@ -422,81 +597,132 @@ done:
 
 template <typename T, bool NN>
 hipError_t launch_update(const T* X, int64_t ldx, const T* L, int64_t ldl, T* C, int64_t ldc, int M, int Nc, int Kd,
-                         hipStream_t st, const unsigned* gate) {
+                         hipStream_t st, const unsigned* gate, const TrsmBatch& tb) {
   const int ntm = (M + UN_BM - 1) / UN_BM, ntn = (Nc + UN_BN - 1) / UN_BN;
-  hipLaunchKernelGGL((trsm_update_kernel<T, NN>), dim3((unsigned)(ntm * ntn)), dim3(UN_NT), 0, st, X, ldx, L, ldl, C,
-                     ldc, M, Nc, Kd, ntm, gate);
+  hipLaunchKernelGGL((trsm_update_kernel<T, NN>), dim3((unsigned)(ntm * ntn), (unsigned)tb.B), dim3(UN_NT), 0, st, X,
+                     ldx, L, ldl, C, ldc, M, Nc, Kd, ntm, gate, tb.sB, tb.sK);
   return hipGetLastError();
 }
 
 template <typename T, bool BWD>
 hipError_t launch_panel(const T* K, int64_t ld, int N, const T* Linv, int nbi, T* B, int64_t ldb, int nrhs, int p0,
-                        int w, hipStream_t st, const unsigned* gate) {
+                        int w, hipStream_t st, const unsigned* gate, const TrsmBatch& tb) {
   constexpr int NBI = PanelNbi<T>;
   // fp64: more than the 64 KB a kernel gets by default; raised once per process
   static const hipError_t attr = hipFuncSetAttribute(
       reinterpret_cast<const void*>(&trsm_panel_kernel<T, NBI, BWD>), hipFuncAttributeMaxDynamicSharedMemorySize,
       (int)panel_lds_bytes<T>(IPMZ_TRSM_PANEL_MAX, NBI ? NBI : 128));
   if (attr != hipSuccess) return attr;
-  hipLaunchKernelGGL((trsm_panel_kernel<T, NBI, BWD>), dim3((nrhs + TM_G - 1) / TM_G), dim3(TM_NT),
-                     panel_lds_bytes<T>(w, nbi), st, K, ld, N, Linv, nbi, B, ldb, nrhs, p0, w, gate);
+  hipLaunchKernelGGL((trsm_panel_kernel<T, NBI, BWD>), dim3((nrhs + TM_G - 1) / TM_G, (unsigned)tb.B), dim3(TM_NT),
+                     panel_lds_bytes<T>(w, nbi), st, K, ld, N, Linv, nbi, B, ldb, nrhs, p0, w, gate, tb.sK, tb.sL,
+                     tb.sB);
   return hipGetLastError();
+}
+
+// LDS one workgroup may use on the current device (cached per process; one device type)
+size_t device_lds_per_workgroup() {
+  static size_t lds = [] {
+    int dev = 0, n = 0;
+    if (hipGetDevice(&dev) != hipSuccess ||
+        hipDeviceGetAttribute(&n, hipDeviceAttributeMaxSharedMemoryPerBlock, dev) != hipSuccess || n <= 0)
+      n = 64 * 1024;
+    return (size_t)n;
+  }();
+  return lds;
+}
+
+// more systems than a grid dimension holds, or strides that break the 16-byte loads
+bool batch_ok(const TrsmBatch& tb) {
+  return tb.B >= 1 && tb.B <= 65535 && (tb.B == 1 || !((tb.sK | tb.sL | tb.sB) & 1));
 }
 
 }  // namespace
 
 template <typename T>
 hipError_t trsm_sweep(const T* K, int64_t ld, int N, const T* Linv, int nbi, T* B, int64_t ldb, int nrhs, int w,
-                      bool backward, hipStream_t st, const unsigned* gate) {
+                      bool backward, hipStream_t st, const unsigned* gate, const TrsmBatch& tb) {
   if (N <= 0 || nrhs <= 0) return hipSuccess;
   // fp32: the mixed factor (nbi = 64, rows of whole 64-column blocks); leading dimensions in whole vectors
   const bool ok = std::is_same<T, float>::value
                       ? nbi == 64 && !(ld & 63) && !(ldb & 3) && !((uintptr_t)Linv & 15)
                       : (nbi == 64 || nbi == 128) && !(ld & 1) && !(ldb & 1);
   if (!ok || w < nbi || w % 128 != 0 || w > IPMZ_TRSM_PANEL_MAX || ld < N || ldb < N || ((uintptr_t)K & 15) ||
-      ((uintptr_t)B & 15))
+      ((uintptr_t)B & 15) || !batch_ok(tb) || (tb.B > 1 && std::is_same<T, float>::value))
     return hipErrorInvalidValue;
   hipError_t e;
   if (!backward) {
     for (int p0 = 0; p0 < N; p0 += w) {
       const int p1 = p0 + w < N ? p0 + w : N;
-      if ((e = launch_panel<T, false>(K, ld, N, Linv, nbi, B, ldb, nrhs, p0, w, st, gate)) != hipSuccess) return e;
+      if ((e = launch_panel<T, false>(K, ld, N, Linv, nbi, B, ldb, nrhs, p0, w, st, gate, tb)) != hipSuccess) return e;
       if (p1 < N &&  // B[:, p1:] -= Y[:, P] L[p1:, P]^T
           (e = launch_update<T, false>(B + p0, ldb, K + (int64_t)p1 * ld + p0, ld, B + p1, ldb, nrhs, N - p1, p1 - p0,
-                                       st, gate)) != hipSuccess)
+                                       st, gate, tb)) != hipSuccess)
         return e;
     }
     return hipSuccess;
   }
   for (int p0 = ((N - 1) / w) * w; p0 >= 0; p0 -= w) {
     const int p1 = p0 + w < N ? p0 + w : N;
-    if ((e = launch_panel<T, true>(K, ld, N, Linv, nbi, B, ldb, nrhs, p0, w, st, gate)) != hipSuccess) return e;
+    if ((e = launch_panel<T, true>(K, ld, N, Linv, nbi, B, ldb, nrhs, p0, w, st, gate, tb)) != hipSuccess) return e;
     if (p0 > 0 &&  // B[:, :p0] -= X[:, P] L[P, :p0]
-        (e = launch_update<T, true>(B + p0, ldb, K + (int64_t)p0 * ld, ld, B, ldb, nrhs, p0, p1 - p0, st, gate)) !=
+        (e = launch_update<T, true>(B + p0, ldb, K + (int64_t)p0 * ld, ld, B, ldb, nrhs, p0, p1 - p0, st, gate, tb)) !=
             hipSuccess)
       return e;
   }
   return hipSuccess;
 }
 template hipError_t trsm_sweep<double>(const double*, int64_t, int, const double*, int, double*, int64_t, int, int,
-                                       bool, hipStream_t, const unsigned*);
+                                       bool, hipStream_t, const unsigned*, const TrsmBatch&);
 template hipError_t trsm_sweep<float>(const float*, int64_t, int, const float*, int, float*, int64_t, int, int, bool,
-                                      hipStream_t, const unsigned*);
+                                      hipStream_t, const unsigned*, const TrsmBatch&);
 
 template <typename T>
 hipError_t ldlt_solve_multi(const T* K, int64_t ld, int N, const T* D, const T* Linv, int nbi, T* B, int64_t ldb,
-                            int nrhs, int w, hipStream_t st) {
+                            int nrhs, int w, hipStream_t st, const TrsmBatch& tb) {
   if (N <= 0 || nrhs <= 0) return hipSuccess;
-  hipError_t e = trsm_sweep<T>(K, ld, N, Linv, nbi, B, ldb, nrhs, w, false, st, nullptr);
+  hipError_t e = trsm_sweep<T>(K, ld, N, Linv, nbi, B, ldb, nrhs, w, false, st, nullptr, tb);
   if (e != hipSuccess) return e;
-  hipLaunchKernelGGL(trsm_scale_kernel<T>, dim3((N + TM_NT - 1) / TM_NT, nrhs < 64 ? nrhs : 64), dim3(TM_NT), 0, st,
-                     B, ldb, nrhs, N, D);
+  hipLaunchKernelGGL(trsm_scale_kernel<T>, dim3((N + TM_NT - 1) / TM_NT, nrhs < 64 ? nrhs : 64, (unsigned)tb.B),
+                     dim3(TM_NT), 0, st, B, ldb, nrhs, N, D, tb.sB, tb.sD);
   if ((e = hipGetLastError()) != hipSuccess) return e;
-  return trsm_sweep<T>(K, ld, N, Linv, nbi, B, ldb, nrhs, w, true, st, nullptr);
+  return trsm_sweep<T>(K, ld, N, Linv, nbi, B, ldb, nrhs, w, true, st, nullptr, tb);
 }
 template hipError_t ldlt_solve_multi<double>(const double*, int64_t, int, const double*, const double*, int, double*,
-                                             int64_t, int, int, hipStream_t);
+                                             int64_t, int, int, hipStream_t, const TrsmBatch&);
 template hipError_t ldlt_solve_multi<float>(const float*, int64_t, int, const float*, const float*, int, float*,
-                                            int64_t, int, int, hipStream_t);
+                                            int64_t, int, int, hipStream_t, const TrsmBatch&);
+
+bool ldlt_solve_fused_eligible(int N, int nbi) {
+  if (N <= 0 || (nbi != 64 && nbi != 128)) return false;
+  return panel_lds_bytes<double>((N + nbi - 1) / nbi * nbi, nbi) <= device_lds_per_workgroup();
+}
+
+hipError_t ldlt_solve_fused(const double* K, int64_t ld, int N, const double* D, const double* Linv, int nbi,
+                            double* B, int64_t ldb, int nrhs, hipStream_t st, const TrsmBatch& tb) {
+  if (N <= 0 || nrhs <= 0) return hipSuccess;
+  if (!ldlt_solve_fused_eligible(N, nbi) || (ld & 1) || (ldb & 1) || ld < N || ldb < N || ((uintptr_t)K & 15) ||
+      ((uintptr_t)B & 15) || !batch_ok(tb))
+    return hipErrorInvalidValue;
+  // all the LDS a workgroup may have; raised once per process
+  static const hipError_t attr = [] {
+    const int lds = (int)device_lds_per_workgroup();
+    hipError_t e = hipFuncSetAttribute(reinterpret_cast<const void*>(&trsm_fused_kernel<TM_SB>),
+                                       hipFuncAttributeMaxDynamicSharedMemorySize, lds);
+    if (e == hipSuccess)
+      e = hipFuncSetAttribute(reinterpret_cast<const void*>(&trsm_fused_kernel<0>),
+                              hipFuncAttributeMaxDynamicSharedMemorySize, lds);
+    return e;
+  }();
+  if (attr != hipSuccess) return attr;
+  const dim3 grid((nrhs + TM_G - 1) / TM_G, (unsigned)tb.B);
+  const size_t lds = panel_lds_bytes<double>((N + nbi - 1) / nbi * nbi, nbi);
+  if (nbi == TM_SB)
+    hipLaunchKernelGGL(trsm_fused_kernel<TM_SB>, grid, dim3(TM_NT), lds, st, K, ld, N, D, Linv, nbi, B, ldb, nrhs, tb.sK,
+                       tb.sD, tb.sL, tb.sB);
+  else
+    hipLaunchKernelGGL(trsm_fused_kernel<0>, grid, dim3(TM_NT), lds, st, K, ld, N, D, Linv, nbi, B, ldb, nrhs, tb.sK,
+                       tb.sD, tb.sL, tb.sB);
+  return hipGetLastError();
+}
 
 }  // namespace ipmz

@@ -50,6 +50,7 @@ EXPORTS = [
     "ipmz_mixed_multi_workspace_bytes", "ipmz_mixed_solve_multi", "ipmz_sym_residual_multi", "ipmz_qp_kkt_solve_mixed",
     "ipmz_bk_solve_workspace_bytes", "ipmz_bk_prepare_solve", "ipmz_bk_solve_multi",
     "ipmz_overwriting_solve_bunch_kaufman_multi", "ipmz_normal_solve_multi", "ipmz_qp_kkt_solve_bk",
+    "ipmz_batch_get_kkt", "ipmz_batch_kkt_solve",
 ]
 SOLVE_MULTI_PANEL = 256  # include/ipmz.h IPMZ_SOLVE_MULTI_PANEL: column panel of the blocked multi-rhs solve
 REDUCTION_AUGMENTED, REDUCTION_NORMAL = 0, 1
@@ -168,6 +169,8 @@ def _load():
         "ipmz_overwriting_solve_bunch_kaufman_multi": ([_VP, _I, _P, ctypes.POINTER(ctypes.c_int), _P, _I], _I),
         "ipmz_normal_solve_multi": ([_VP, _I, _I, _VP, _I64, _VP, _VP, _VP, _I64, _I], _I),
         "ipmz_qp_kkt_solve_bk": ([_VP, _I, _VP, _I64], _I),
+        "ipmz_batch_get_kkt": ([_VP, _I, _P], _I),
+        "ipmz_batch_kkt_solve": ([_VP, _I, _VP, _I64, _I64], _I),
     }
     for name, (args, res) in sig.items():
         fn = getattr(lib, name)
@@ -668,6 +671,19 @@ class Batch(Optimizer):
         FACTOR_PAIR (right-looking, two per QP; needs 2 * batch <= #CU) or
         FACTOR_LEFT (left-looking, one per QP): the small batched LDL^T kernel."""
         _check(lib.ipmz_batch_set_factor_kernel(self.h, int(kernel)), "ipmz_batch_set_factor_kernel")
+
+    def kkt_of(self, index):
+        """kkt() of QP `index`: the (N, N) KKT matrix of its current iterate, lower triangle."""
+        K = np.zeros((self.N, self.N))
+        _check(lib.ipmz_batch_get_kkt(self.h, index, _dp(K)), "ipmz_batch_get_kkt")
+        return K
+
+    def kkt_solve_all(self, B_ptr, nrhs, ldb, sB):
+        """For every QP q: the nrhs rows at B + q * sB (device, Newton order, row stride ldb) <-
+        K_q^{-1} row with the KKT matrix of its current iterate (kkt_of(q)); returns the batched
+        factor's info word.  A contiguous (batch, nrhs, ldb) torch tensor has sB = nrhs * ldb.
+        fp64 LDL^T batches only (not EQ_NONE); the inherited kkt_solve stays for single QPs."""
+        return _check(lib.ipmz_batch_kkt_solve(self.h, nrhs, _VP(B_ptr), ldb, sB), "ipmz_batch_kkt_solve")
 
     def batch_scalars(self):
         out = np.zeros(self.batch * SC_COUNT)
