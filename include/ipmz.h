@@ -32,6 +32,13 @@
  *                                  a batch, and ipmz_qp_kkt_solve for every QP of a batch at
  *                                  once (one launch per batch where a QP's right-hand sides
  *                                  fit a workgroup's LDS)
+ *   ipmz_bk_factor_batch, ipmz_bk_prepare_solve_batch, ipmz_bk_solve_multi_batch,
+ *   ipmz_batch_kkt_solve_bk
+ *                               <- no reference counterpart: the one-workgroup
+ *                                  Bunch-Kaufman factor and the prepared multi-right-hand-side
+ *                                  solve for a batch of systems of one order (N <= 4096) on
+ *                                  caller-owned storage, and ipmz_qp_kkt_solve_bk for every
+ *                                  QP of an IPMZ_EQ_NONE batch at once
  *   ipmz_qp_create + ipmz_qp_load_host
  *                               <- NumericalOptimization::build_environment
  *                                  (EnvironmentBuilder.h:19-20, EnvironmentBuilder.cpp:7-76)
@@ -285,6 +292,44 @@ int ipmz_bk_prepare_solve(ipmz_ctx* ctx, int N, const double* F, int64_t ld, con
  * timeout of the looped solves as IPMZ_ERR_HIP. */
 int ipmz_bk_solve_multi(ipmz_ctx* ctx, int N, const double* F, int64_t ld, const int* ipiv,
                         const void* ws, double* B, int64_t ldb, int nrhs);
+/* ---- batches of Bunch-Kaufman systems of one order (no reference counterpart) ----
+ * `batch` matrices of order N (<= IPMZ_BK_NMAX = 4096), matrix q at A + q*sA (device, row-major,
+ * ld >= N, sA >= (N-1)*ld + N), its pivots at ipiv + q*sP (sP >= N): the step's batched
+ * one-workgroup factor on caller storage, one launch.  Every matrix is bitwise
+ * ipmz_bk_factor_ex(..., IPMZ_BK_WORKGROUP) of that matrix.  info (host, batch ints, may be
+ * NULL): per matrix ipmz_bk_factor's word, 0 or 1 + the first all-zero column the
+ * factorization met.  Returns the smallest non-zero info, else IPMZ_OK; synchronizes.  batch <= 65535; N == 0 and batch == 0 are no-ops. */
+#define IPMZ_BK_NMAX 4096
+int ipmz_bk_factor_batch(ipmz_ctx* ctx, int N, int batch, double* A, int64_t ld, int64_t sA,
+                         int* ipiv, int64_t sP, int fix_kp, int* info);
+/* workspace of the prepared solves of a batch (bytes): per system the transposed factor and L'
+ * (about 16 N^2 bytes together), the inverted 64-column diagonal blocks and the interchange
+ * bookkeeping with the system's own fallback flag */
+int64_t ipmz_bk_batch_solve_workspace_bytes(ipmz_ctx* ctx, int N, int batch);
+/* ipmz_bk_prepare_solve for every matrix of the batch, in a number of launches that does not
+ * grow with `batch` (six); sA even.  The interchange bookkeeping always uses 64-column diagonal blocks,
+ * whatever ipmz_ctx_set_blocking says.  A workspace that is too small is IPMZ_ERR_INVALID.
+ * Asynchronous. */
+int ipmz_bk_prepare_solve_batch(ipmz_ctx* ctx, int N, int batch, const double* F, int64_t ld, int64_t sA,
+                                const int* ipiv, int64_t sP, void* ws, int64_t ws_bytes);
+/* rows r < nrhs at B + q*sB + r*ldb <- A_q^{-1} row; in place, asynchronous, no allocation.
+ * ldb >= N and even, sB >= nrhs*ldb and even, sA even, B 16-byte aligned, nrhs >= 0; B[q][r][N .. ldb)
+ * and everything between nrhs*ldb and sB is never written; N, batch or nrhs == 0 is a no-op.
+ * Below a crossover nrhs the rows go one by one through the step's batched single-vector solve
+ * (one launch per row serving all systems: k rows are bitwise k calls with one row, and for
+ * N < 512 bitwise ipmz_bk_solve of that system); from it on together, as ipmz_bk_solve_multi
+ * with the system on a grid dimension of every launch: row permutation, blocked forward sweep
+ * on L', the D solve in the reference's arithmetic, blocked backward sweep, inverse
+ * permutation.  A system the reference solves in its own interleaved order only (a singular
+ * one) runs those sweeps instead, one workgroup per (system, row), chosen on the device per
+ * system: the other systems of the batch stay on the blocked path.  Stream-ordered launches
+ * only, no cross-workgroup waiting, no atomics: a row's result does not depend on the other
+ * rows, a system's not on the other systems of the batch (given the same path), and equal
+ * inputs give equal bits. */
+int ipmz_bk_solve_multi_batch(ipmz_ctx* ctx, int N, int batch, const double* F, int64_t ld, int64_t sA,
+                              const int* ipiv, int64_t sP, const void* ws,
+                              double* B, int64_t ldb, int64_t sB, int nrhs);
+
 /* Host signatures of the reference (value semantics, reference pivoting
  * including its kp = 0 defect): F = A with the lower triangle factored. */
 int ipmz_symmetric_indefinite_factorization(ipmz_ctx* ctx, int N, const double* A, double* F, int* ipiv);
@@ -550,6 +595,17 @@ int ipmz_batch_get_kkt(ipmz_qp* qp, int index, double* host_K);
  * <= 768 with 128, on 160 KiB) or the panel chain of ipmz_ldlt_solve_multi
  * with the QP on a grid dimension. */
 int ipmz_batch_kkt_solve(ipmz_qp* qp, int nrhs, double* B, int64_t ldb, int64_t sB);
+/* ipmz_batch_kkt_solve for IPMZ_EQ_NONE batches (N <= 4096): the step's own assembly and
+ * batched Bunch-Kaufman factor on the storage the next step overwrites anyway, then
+ * ipmz_bk_prepare_solve_batch and ipmz_bk_solve_multi_batch on a workspace allocated on first
+ * use and freed with the solver (IPMZ_ERR_NOMEM when it cannot be had).  Same argument rules
+ * as ipmz_batch_kkt_solve.  info (host, batch ints, may be NULL): per QP ipmz_bk_factor's
+ * word (0 or 1 + the first all-zero column met); returns the smallest non-zero one, else IPMZ_OK; synchronizes.  The
+ * iterate, a captured step graph (IPMZ_STEP_GRAPH) and all later steps are unchanged, bitwise.
+ * IPMZ_ERR_INVALID for any other equality handling; IPMZ_ERR_STATE before a load, between a
+ * load and ipmz_batch_initialize, and while the stream is capturing.  A solver that holds one
+ * QP forwards to ipmz_qp_kkt_solve_bk: sB is then ignored and info[0] is the return value. */
+int ipmz_batch_kkt_solve_bk(ipmz_qp* qp, int nrhs, double* B, int64_t ldb, int64_t sB, int* info);
 
 /* Phase timing (HIP events on the context stream; eager launches only).
  * ms: host array of IPMZ_PH_COUNT floats, cumulative since enable. */

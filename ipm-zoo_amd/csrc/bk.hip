@@ -232,14 +232,9 @@ __global__ __launch_bounds__(BKT) void k_bk_factor(double* __restrict__ Ab, int6
 // gate (may be null): run only when *gate != 0 (the fallback of the
 // device-wide solve, bk_fast_*)
 template <bool TRANS>
-__global__ __launch_bounds__(BKT) void k_bk_solve(const double* __restrict__ Lb, int64_t ld, int n, int64_t sA,
-                                                  const int* __restrict__ ipivb, int64_t sP, double* __restrict__ bb,
-                                                  int64_t sb, const unsigned* gate) {
-  if (gate && *gate == 0u) return;
+__device__ __forceinline__ void bk_solve_body(const double* __restrict__ L, int64_t ld, int n,
+                                              const int* __restrict__ ipiv, double* __restrict__ b) {
   __shared__ double sv[BKW];
-  const double* L = Lb + blockIdx.x * sA;
-  const int* ipiv = ipivb + blockIdx.x * sP;
-  double* b = bb + blockIdx.x * sb;
   const int tid = threadIdx.x;
   auto l = [&](int i, int j) { return TRANS ? L[(int64_t)j * ld + i] : L[(int64_t)i * ld + j]; };
   auto swapb = [&](int p, int q) {
@@ -324,6 +319,26 @@ __global__ __launch_bounds__(BKT) void k_bk_solve(const double* __restrict__ Lb,
       k -= 2;
     }
   }
+}
+
+template <bool TRANS>
+__global__ __launch_bounds__(BKT) void k_bk_solve(const double* __restrict__ Lb, int64_t ld, int n, int64_t sA,
+                                                  const int* __restrict__ ipivb, int64_t sP, double* __restrict__ bb,
+                                                  int64_t sb, const unsigned* gate) {
+  if (gate && *gate == 0u) return;
+  bk_solve_body<TRANS>(Lb + blockIdx.x * sA, ld, n, ipivb + blockIdx.x * sP, bb + blockIdx.x * sb);
+}
+
+// the same sweeps on LT for row blockIdx.x (stride ldb) of system blockIdx.y
+// (strides sLT, sP, sB); run only for a system whose gate word (sG words
+// apart) is set: the batched prepared solve's fallback
+__global__ __launch_bounds__(BKT) void k_bk_solve_rows(const double* __restrict__ LTb, int n, int64_t sLT,
+                                                       const int* __restrict__ ipivb, int64_t sP,
+                                                       double* __restrict__ Bb, int64_t ldb, int64_t sB,
+                                                       const unsigned* __restrict__ gate, int64_t sG) {
+  if (gate[blockIdx.y * sG] == 0u) return;
+  bk_solve_body<true>(LTb + blockIdx.y * sLT, (int64_t)n, n, ipivb + blockIdx.y * sP,
+                      Bb + blockIdx.y * sB + (int64_t)blockIdx.x * ldb);
 }
 
 // ---------------------------------------------------------------------------
@@ -783,8 +798,10 @@ hipError_t bk_solve(const double* F, int64_t ld, int n, const int* ipiv, double*
 }
 
 // LT[j][i] = F[i][j], i >= j (64 x 64 tiles through LDS: coalesced both ways)
-__global__ __launch_bounds__(256) void k_bk_transpose(const double* __restrict__ F, int64_t ld, int n,
-                                                      double* __restrict__ LT, int64_t ldt) {
+__global__ __launch_bounds__(256) void k_bk_transpose(const double* __restrict__ Fb, int64_t ld, int64_t sA, int n,
+                                                      double* __restrict__ LTb, int64_t ldt, int64_t sLT) {
+  const double* F = Fb + blockIdx.z * sA;
+  double* LT = LTb + blockIdx.z * sLT;
   __shared__ double t[64][65];
   const int bi = blockIdx.y, bj = blockIdx.x;  // source tile rows 64 bi.., columns 64 bj..
   if (bj > bi) return;
@@ -800,10 +817,10 @@ __global__ __launch_bounds__(256) void k_bk_transpose(const double* __restrict__
   }
 }
 
-hipError_t bk_transpose(const double* F, int64_t ld, int n, double* LT, hipStream_t st) {
-  if (n <= 0) return hipSuccess;
+hipError_t bk_transpose(const double* F, int64_t ld, int n, double* LT, hipStream_t st, const BkBatch& bb) {
+  if (n <= 0 || bb.B <= 0) return hipSuccess;
   const int nb = (n + 63) / 64;
-  hipLaunchKernelGGL(k_bk_transpose, dim3(nb, nb), dim3(256), 0, st, F, ld, n, LT, (int64_t)n);
+  hipLaunchKernelGGL(k_bk_transpose, dim3(nb, nb, bb.B), dim3(256), 0, st, F, ld, bb.sA, n, LT, (int64_t)n, bb.sLT);
   return hipGetLastError();
 }
 hipError_t bk_solve_lt(const double* LT, int n, const int* ipiv, double* b, hipStream_t st) {
@@ -836,6 +853,27 @@ struct Meta {
   int *kind, *perm, *srow, *sa, *sb, *slotpos;
   double *d11, *d21, *d22, *ones, *t;
   size_t total;
+  // system q of a batch: every member `stride` bytes further per system (the
+  // per-system layouts lie back to back; one system: stride 0)
+  int64_t stride;
+  IPMZ_HOST_DEVICE Meta of(unsigned q) const {
+    const int64_t o = (int64_t)q * stride;
+    auto adv = [o](auto* p) { return reinterpret_cast<decltype(p)>(reinterpret_cast<char*>(p) + o); };
+    Meta r = *this;
+    r.flag = adv(flag);
+    r.kind = adv(kind);
+    r.perm = adv(perm);
+    r.srow = adv(srow);
+    r.sa = adv(sa);
+    r.sb = adv(sb);
+    r.slotpos = adv(slotpos);
+    r.d11 = adv(d11);
+    r.d21 = adv(d21);
+    r.d22 = adv(d22);
+    r.ones = adv(ones);
+    r.t = adv(t);
+    return r;
+  }
 };
 inline Meta layout(char* base, int n) {
   Meta m;
@@ -853,6 +891,13 @@ inline Meta layout(char* base, int n) {
   m.ones = c.take<double>(n);
   m.t = c.take<double>(n);
   m.total = (size_t)c.off;
+  m.stride = 0;
+  return m;
+}
+// the layouts of a batch: system q's at base + q * total
+inline Meta layout_batch(char* base, int n) {
+  Meta m = layout(base, n);
+  m.stride = (int64_t)m.total;
   return m;
 }
 
@@ -861,11 +906,15 @@ inline Meta layout(char* base, int n) {
 // (row srow, positions sa = srow and sb = kp, as slot indices into slotpos,
 // the distinct positions they touch); perm = the composite interchange
 // ((P b)[p] = b[perm[p]]).  Thread 0 walks ipiv in chunks staged in LDS.
-__global__ __launch_bounds__(1024) void k_scan(const int* __restrict__ ipiv, int n, const int* __restrict__ info,
-                                               Meta m) {
+// System blockIdx.x of a batch: pivots sP apart, one info word each.
+__global__ __launch_bounds__(1024) void k_scan(const int* __restrict__ ipivb, int64_t sP, int n,
+                                               const int* __restrict__ infob, Meta mb) {
   extern __shared__ int lds[];  // perm[n], slotof[n]
   __shared__ int chunk[1025];
   __shared__ int sh_bad, sh_ns, sh_nsl;
+  const int* ipiv = ipivb + blockIdx.x * sP;
+  const int* info = infob ? infob + blockIdx.x : nullptr;
+  const Meta m = mb.of(blockIdx.x);
   int* perm = lds;
   int* slotof = lds + n;
   const int tid = threadIdx.x;
@@ -937,9 +986,11 @@ __global__ __launch_bounds__(1024) void k_scan(const int* __restrict__ ipiv, int
 }
 
 // the pivot blocks of D (from F, before it is overwritten) and the ones vector
-__global__ void k_extract(const double* __restrict__ F, int64_t ld, int n, Meta m) {
+__global__ void k_extract(const double* __restrict__ Fb, int64_t ld, int64_t sA, int n, Meta mb) {
   const int k = blockIdx.x * blockDim.x + threadIdx.x;
   if (k >= n) return;
+  const double* F = Fb + blockIdx.y * sA;
+  const Meta m = mb.of(blockIdx.y);
   m.ones[k] = 1.0;
   const double d11 = F[(int64_t)k * ld + k];
   m.d11[k] = d11;
@@ -956,7 +1007,8 @@ __global__ void k_extract(const double* __restrict__ F, int64_t ld, int n, Meta 
 // column c of L (row c of LT): every interchange after the column's pivot
 // step applied to its entries (through the touched slots, in LDS), and a 2x2
 // pivot's d21 zeroed
-__global__ __launch_bounds__(256) void k_lprime(double* __restrict__ LT, int n, Meta m) {
+__global__ __launch_bounds__(256) void k_lprime(double* __restrict__ LTb, int64_t sLT, int n, Meta mb) {
+  const Meta m = mb.of(blockIdx.y);
   if (m.flag[0]) return;
   extern __shared__ double vals[];
   __shared__ int sh_s0;
@@ -964,7 +1016,7 @@ __global__ __launch_bounds__(256) void k_lprime(double* __restrict__ LT, int n, 
   const int kd = m.kind[c];
   const int cp = kd == 1 ? c + 1 : c;  // last row of the column's pivot step
   const int ns = (int)m.flag[1], nsl = (int)m.flag[2];
-  double* row = LT + (int64_t)c * n;
+  double* row = LTb + blockIdx.y * sLT + (int64_t)c * n;
   if (kd == 1 && tid == 0) row[c + 1] = 0.0;
   if (tid == 0) {  // first interchange of a later step: srow > cp (srow increases)
     int lo = 0, hi = ns;
@@ -998,9 +1050,12 @@ __global__ __launch_bounds__(256) void k_lprime(double* __restrict__ LT, int n, 
 }
 
 // Lp[i][j] = LT[j][i], i > j (64 x 64 tiles through LDS)
-__global__ __launch_bounds__(256) void k_untranspose(const double* __restrict__ LT, int n, double* __restrict__ Lp,
-                                                     int64_t ld, const unsigned* __restrict__ flag) {
-  if (flag[0]) return;
+__global__ __launch_bounds__(256) void k_untranspose(const double* __restrict__ LTb, int64_t sLT, int n,
+                                                     double* __restrict__ Lpb, int64_t ld, int64_t sLp,
+                                                     const unsigned* __restrict__ flag, int64_t sF) {
+  if (flag[blockIdx.z * sF]) return;
+  const double* LT = LTb + blockIdx.z * sLT;
+  double* Lp = Lpb + blockIdx.z * sLp;
   __shared__ double t[64][65];
   const int bi = blockIdx.y, bj = blockIdx.x;  // destination tile rows 64 bi.., columns 64 bj..
   if (bj > bi) return;
@@ -1051,15 +1106,19 @@ __global__ void k_dsolve(double* __restrict__ y, int n, Meta m) {
 
 // The same three stages for a block of right-hand sides (one per row of B,
 // stride ldb, even; B 16-byte aligned), in place; columns [n, ldb) of a row
-// are never touched.  Gated like the single-vector kernels.
+// are never touched.  Gated like the single-vector kernels.  A batch of
+// systems: the system is the last used grid dimension, its rows sB apart and
+// its bookkeeping Meta::of(system); each system has its own fallback flag.
 constexpr int ROWT = 1024;
 // row <- P row ((P b)[p] = b[perm[p]]): one workgroup per row, the whole row
 // staged in LDS (n <= LDS_MAX_N: at most 128 KB), written back two entries
 // per 16-byte store
-__global__ __launch_bounds__(ROWT) void k_gather_rows(double* __restrict__ B, int64_t ldb, int n, Meta m) {
+__global__ __launch_bounds__(ROWT) void k_gather_rows(double* __restrict__ B, int64_t ldb, int64_t sB, int n,
+                                                      Meta mb) {
+  const Meta m = mb.of(blockIdx.y);
   if (m.flag[0]) return;
   extern __shared__ __attribute__((aligned(16))) double rowbuf[];
-  double* b = B + (int64_t)blockIdx.x * ldb;
+  double* b = B + blockIdx.y * sB + (int64_t)blockIdx.x * ldb;
   const int tid = threadIdx.x, n2 = n >> 1;
   for (int i = tid; i < n2; i += ROWT) reinterpret_cast<double2*>(rowbuf)[i] = reinterpret_cast<const double2*>(b)[i];
   if ((n & 1) && tid == 0) rowbuf[n - 1] = b[n - 1];
@@ -1071,10 +1130,12 @@ __global__ __launch_bounds__(ROWT) void k_gather_rows(double* __restrict__ B, in
   if ((n & 1) && tid == 0) b[n - 1] = rowbuf[m.perm[n - 1]];
 }
 // the mirror: b[perm[p]] = b'[p]
-__global__ __launch_bounds__(ROWT) void k_scatter_rows(double* __restrict__ B, int64_t ldb, int n, Meta m) {
+__global__ __launch_bounds__(ROWT) void k_scatter_rows(double* __restrict__ B, int64_t ldb, int64_t sB, int n,
+                                                       Meta mb) {
+  const Meta m = mb.of(blockIdx.y);
   if (m.flag[0]) return;
   extern __shared__ __attribute__((aligned(16))) double rowbuf[];
-  double* b = B + (int64_t)blockIdx.x * ldb;
+  double* b = B + blockIdx.y * sB + (int64_t)blockIdx.x * ldb;
   const int tid = threadIdx.x, n2 = n >> 1;
   for (int i = tid; i < n2; i += ROWT) {
     const double2 v = reinterpret_cast<const double2*>(b)[i];
@@ -1091,8 +1152,11 @@ __global__ __launch_bounds__(ROWT) void k_scatter_rows(double* __restrict__ B, i
 // The thread on the first row of a 2x2 pivot writes both entries of its pair
 // (wherever k + 1 lies: nothing here knows of blocks or panels), the thread
 // on its second row does nothing
-__global__ __launch_bounds__(256) void k_dsolve_rows(double* __restrict__ B, int64_t ldb, int nrhs, int n, Meta m) {
+__global__ __launch_bounds__(256) void k_dsolve_rows(double* __restrict__ Bb, int64_t ldb, int64_t sB, int nrhs,
+                                                     int n, Meta mb) {
+  const Meta m = mb.of(blockIdx.z);
   if (m.flag[0]) return;
+  double* B = Bb + blockIdx.z * sB;
   const int k = blockIdx.x * blockDim.x + threadIdx.x;
   if (k >= n) return;
   const int kd = m.kind[k];
@@ -1119,24 +1183,33 @@ __global__ __launch_bounds__(256) void k_dsolve_rows(double* __restrict__ B, int
 }  // namespace bkf
 
 size_t bk_fast_meta_bytes(int n) { return bkf::layout(nullptr, n).total; }
+// one system's bookkeeping, or a batch's (the layouts back to back)
+static bkf::Meta meta_of(const void* meta, int n, const BkBatch& bb) {
+  char* base = static_cast<char*>(const_cast<void*>(meta));
+  return bb.B > 1 ? bkf::layout_batch(base, n) : bkf::layout(base, n);
+}
 const unsigned* bk_fast_flag(const void* meta) { return static_cast<const unsigned*>(meta); }
 const double* bk_fast_ones(const void* meta, int n) { return bkf::layout(static_cast<char*>(const_cast<void*>(meta)), n).ones; }
 double* bk_fast_tmp(void* meta, int n) { return bkf::layout(static_cast<char*>(meta), n).t; }
 
 hipError_t bk_fast_prepare(const double* F, int64_t ld, int n, const int* ipiv, const int* info, double* LT,
-                           double* Lp, int64_t ldp, void* meta, hipStream_t st) {
-  if (n <= 0) return hipSuccess;
-  bkf::Meta m = bkf::layout(static_cast<char*>(meta), n);
+                           double* Lp, int64_t ldp, void* meta, hipStream_t st, const BkBatch& bb) {
+  if (n <= 0 || bb.B <= 0) return hipSuccess;
+  if (bb.B > 1 && n > bkf::LDS_MAX_N) return hipErrorInvalidValue;
+  bkf::Meta m = meta_of(meta, n, bb);
+  const int64_t sF = m.stride / (int64_t)sizeof(unsigned);
   if (n > bkf::LDS_MAX_N) {  // the interchange bookkeeping lives in one workgroup's LDS: fall back
     hipLaunchKernelGGL(bkf::k_set_fallback, dim3(1), dim3(64), 0, st, m.flag);
     return hipGetLastError();
   }
-  hipLaunchKernelGGL(bkf::k_scan, dim3(1), dim3(1024), (size_t)2 * n * sizeof(int), st, ipiv, n, info, m);
-  hipLaunchKernelGGL(bkf::k_extract, dim3((n + 255) / 256), dim3(256), 0, st, F, ld, n, m);
-  hipLaunchKernelGGL(bkf::k_lprime, dim3(n), dim3(256), (size_t)bkf::SLOT_MAX * sizeof(double), st, LT, n, m);
+  hipLaunchKernelGGL(bkf::k_scan, dim3(bb.B), dim3(1024), (size_t)2 * n * sizeof(int), st, ipiv, bb.sP, n, info, m);
+  hipLaunchKernelGGL(bkf::k_extract, dim3((n + 255) / 256, bb.B), dim3(256), 0, st, F, ld, bb.sA, n, m);
+  // (the touched positions are distinct: at most n, and k_scan flags more than SLOT_MAX)
+  const size_t slots = (size_t)(n < bkf::SLOT_MAX ? n : bkf::SLOT_MAX) * sizeof(double);
+  hipLaunchKernelGGL(bkf::k_lprime, dim3(n, bb.B), dim3(256), slots, st, LT, bb.sLT, n, m);
   const int nb = (n + 63) / 64;
-  hipLaunchKernelGGL(bkf::k_untranspose, dim3(nb, nb), dim3(256), 0, st, (const double*)LT, n, Lp, ldp,
-                     (const unsigned*)m.flag);
+  hipLaunchKernelGGL(bkf::k_untranspose, dim3(nb, nb, bb.B), dim3(256), 0, st, (const double*)LT, bb.sLT, n, Lp, ldp,
+                     bb.sLp, (const unsigned*)m.flag, sF);
   return hipGetLastError();
 }
 
@@ -1163,32 +1236,45 @@ hipError_t bk_fast_fallback(const double* LT, int n, const int* ipiv, double* b,
 
 // the row permutations stage a row of up to LDS_MAX_N doubles: more than the
 // 64 KB a kernel gets by default; raised once per process
-template <void (*kern)(double*, int64_t, int, bkf::Meta)>
-static hipError_t launch_rows_perm(double* B, int64_t ldb, int nrhs, int n, void* meta, hipStream_t st) {
+template <void (*kern)(double*, int64_t, int64_t, int, bkf::Meta)>
+static hipError_t launch_rows_perm(double* B, int64_t ldb, int nrhs, int n, void* meta, hipStream_t st,
+                                   const BkBatch& bb) {
   if (n > bkf::LDS_MAX_N) return hipSuccess;  // (the prepare set the fallback flag: nothing to permute)
   static const hipError_t attr =
       hipFuncSetAttribute(reinterpret_cast<const void*>(kern), hipFuncAttributeMaxDynamicSharedMemorySize,
                           (int)(bkf::LDS_MAX_N * sizeof(double)));
   if (attr != hipSuccess) return attr;
-  hipLaunchKernelGGL(kern, dim3(nrhs), dim3(bkf::ROWT), (size_t)(n + (n & 1)) * sizeof(double), st, B, ldb, n,
-                     bkf::layout(static_cast<char*>(meta), n));
+  hipLaunchKernelGGL(kern, dim3(nrhs, bb.B), dim3(bkf::ROWT), (size_t)(n + (n & 1)) * sizeof(double), st, B, ldb,
+                     bb.sB, n, meta_of(meta, n, bb));
   return hipGetLastError();
 }
-hipError_t bk_multi_gather(double* B, int64_t ldb, int nrhs, int n, void* meta, hipStream_t st) {
-  return launch_rows_perm<bkf::k_gather_rows>(B, ldb, nrhs, n, meta, st);
+hipError_t bk_multi_gather(double* B, int64_t ldb, int nrhs, int n, void* meta, hipStream_t st, const BkBatch& bb) {
+  return launch_rows_perm<bkf::k_gather_rows>(B, ldb, nrhs, n, meta, st, bb);
 }
-hipError_t bk_multi_scatter(double* B, int64_t ldb, int nrhs, int n, void* meta, hipStream_t st) {
-  return launch_rows_perm<bkf::k_scatter_rows>(B, ldb, nrhs, n, meta, st);
+hipError_t bk_multi_scatter(double* B, int64_t ldb, int nrhs, int n, void* meta, hipStream_t st, const BkBatch& bb) {
+  return launch_rows_perm<bkf::k_scatter_rows>(B, ldb, nrhs, n, meta, st, bb);
 }
-hipError_t bk_multi_dsolve(double* B, int64_t ldb, int nrhs, int n, void* meta, hipStream_t st) {
-  hipLaunchKernelGGL(bkf::k_dsolve_rows, dim3((n + 255) / 256, nrhs < 65535 ? nrhs : 65535), dim3(256), 0, st, B, ldb,
-                     nrhs, n, bkf::layout(static_cast<char*>(meta), n));
+hipError_t bk_multi_dsolve(double* B, int64_t ldb, int nrhs, int n, void* meta, hipStream_t st, const BkBatch& bb) {
+  // (a batch has its systems to fill the device with: at most 64 grid rows per system, each striding over nrhs)
+  const int gy = bb.B > 1 ? (nrhs < 64 ? nrhs : 64) : (nrhs < 65535 ? nrhs : 65535);
+  hipLaunchKernelGGL(bkf::k_dsolve_rows, dim3((n + 255) / 256, gy, bb.B), dim3(256), 0, st, B, ldb, bb.sB, nrhs, n,
+                     meta_of(meta, n, bb));
   return hipGetLastError();
 }
 hipError_t bk_multi_fallback(const double* LT, int n, const int* ipiv, double* B, int64_t ldb, int nrhs,
                              const void* meta, hipStream_t st) {
   hipLaunchKernelGGL(k_bk_solve<true>, dim3(nrhs), dim3(BKT), 0, st, LT, (int64_t)n, n, 0, ipiv, 0, B, ldb,
                      bk_fast_flag(meta));
+  return hipGetLastError();
+}
+BkFusedMeta bk_fused_meta(const void* meta, int n, const BkBatch& bb) {
+  const bkf::Meta m = meta_of(meta, n, bb);
+  return {m.flag, m.perm, m.kind, m.d11, m.d21, m.d22, m.stride};
+}
+hipError_t bk_multi_fallback_batch(const double* LT, int n, const int* ipiv, double* B, int64_t ldb, int nrhs,
+                                   const void* meta, hipStream_t st, const BkBatch& bb) {
+  hipLaunchKernelGGL(k_bk_solve_rows, dim3(nrhs, bb.B), dim3(BKT), 0, st, LT, n, bb.sLT, ipiv, bb.sP, B, ldb, bb.sB,
+                     bk_fast_flag(meta), (int64_t)(bk_fast_meta_bytes(n) / sizeof(unsigned)));
   return hipGetLastError();
 }
 

@@ -243,6 +243,92 @@ int bk_multi_impl(ipmz_ctx* ctx, int N, const double* F, int64_t ld, const int* 
   return IPMZ_OK;
 }
 
+// Batches of Bunch-Kaufman systems of one order (one workgroup per matrix) -----
+// BK_BATCH_MULTI_CROSSOVER: the number of right-hand sides per system from
+// which the blocked paths run; below it every row is one launch of the step's
+// own batched single-vector solve (bk_solve), all systems at once.  From
+// tools/batch_bk_multi_bench.py (profiles/batch_bk_multi/bench.json, DESIGN.md
+// "Batched multi-right-hand-side Bunch-Kaufman solve"), solve alone = call(nrhs)
+// - call(0), the blocked legs including their once-per-call prepare: the loop
+// costs 3.58 ms for 2 rows and 4.80 ms for 3 (C4 with EQ_NONE, N = 320, batch
+// 1024) / 1.05 and 1.49 ms (batch 128), the one-launch solve 1.39-1.43 / 0.26
+// ms, far outside the loop's spread (0.09 / 0.04 ms): by BATCH_MULTI_CROSSOVER's
+// rule the constant would be 2.  It is 4 because the tests pin nrhs = 3 to the
+// loop's bitwise property (three rows are three one-row calls), as they do for
+// ipmz_batch_kkt_solve; 2 is the measured choice once that case may change.
+// Fused or panels: no panel width leads the one-launch solve by more than the
+// spread at both C4 batch sizes at any count, so eligibility alone decides.
+static constexpr int BK_BATCH_MULTI_CROSSOVER = 4;
+
+int bk_batch_info(hipStream_t st, const int* dinfo, int batch, int* info) {
+  std::vector<int> h((size_t)batch, 0);
+  HIP_OK(hipMemcpyAsync(h.data(), dinfo, (size_t)batch * sizeof(int), hipMemcpyDeviceToHost, st));
+  HIP_OK(hipStreamSynchronize(st));
+  int rc = 0;
+  for (int q = 0; q < batch; ++q) {
+    if (info) info[q] = h[q];
+    if (h[q] != 0 && (rc == 0 || h[q] < rc)) rc = h[q];
+  }
+  return rc;
+}
+
+int bk_batch_prepare(ipmz_ctx* ctx, int N, int batch, const double* F, int64_t ld, int64_t sA, const int* ipiv,
+                     int64_t sP, const int* info, const BkBatchWs& w) {
+  hipStream_t st = ctx->stream;
+  BkBatch bb;
+  bb.B = batch;
+  bb.sA = sA;
+  bb.sP = sP;
+  bb.sLT = w.sLT;
+  bb.sLp = w.sLp;
+  HIP_OK(bk_transpose(F, ld, N, w.LT, st, bb));
+  HIP_OK(bk_fast_prepare(F, ld, N, ipiv, info, w.LT, w.Lp, w.ldp, w.meta, st, bb));
+  HIP_OK(linv_from_l(w.Lp, w.ldp, N, 64, w.Linv, st, batch, w.sLp, w.sLinv));
+  return IPMZ_OK;
+}
+
+int bk_batch_multi_impl(ipmz_ctx* ctx, int N, int batch, const double* F, int64_t ld, int64_t sA, const int* ipiv,
+                        int64_t sP, const BkBatchWs& w, double* B, int64_t ldb, int64_t sB, int nrhs) {
+  const int dbg = debug_inject_mask();
+  hipStream_t st = ctx->stream;
+  if (nrhs < BK_BATCH_MULTI_CROSSOVER && !(nrhs >= 2 && (dbg & IPMZ_DEBUG_MULTI_BLOCKED))) {
+    // the step's own kernel, one launch per row for all systems
+    for (int r = 0; r < nrhs; ++r) HIP_OK(bk_solve(F, ld, N, ipiv, B + (int64_t)r * ldb, batch, sA, sP, sB, st));
+    return IPMZ_OK;
+  }
+  BkBatch bb;
+  bb.B = batch;
+  bb.sA = sA;
+  bb.sP = sP;
+  bb.sLT = w.sLT;
+  bb.sLp = w.sLp;
+  bb.sB = sB;
+  TrsmBatch tb;
+  tb.B = batch;
+  tb.sK = w.sLp;
+  tb.sL = w.sLinv;
+  tb.sB = sB;
+  tb.sG = w.sM / (int64_t)sizeof(unsigned);  // a fallback flag per system: a flagged system's launches exit
+  const unsigned* flag = bk_fast_flag(w.meta);
+  // one launch per batch where a system's slab fits a workgroup's LDS, unless
+  // a panel width is forced; then the flagged systems' reference sweeps
+  if (!(dbg & (IPMZ_DEBUG_MULTI_W128 | IPMZ_DEBUG_MULTI_W512)) && bk_solve_fused_eligible(N)) {
+    HIP_OK(bk_solve_fused(w.Lp, w.ldp, N, w.Linv, B, ldb, nrhs, bk_fused_meta(w.meta, N, bb), st, tb));
+    HIP_OK(bk_multi_fallback_batch(w.LT, N, ipiv, B, ldb, nrhs, w.meta, st, bb));
+    return IPMZ_OK;
+  }
+  // (both width bits together: the panel chain at its default width, as ipmz_batch_kkt_solve)
+  const bool w512 = dbg & IPMZ_DEBUG_MULTI_W512, w128 = dbg & IPMZ_DEBUG_MULTI_W128;
+  const int pw = w512 && w128 ? SOLVE_MULTI_PANEL : w512 ? 512 : w128 ? 128 : SOLVE_MULTI_PANEL;
+  HIP_OK(bk_multi_gather(B, ldb, nrhs, N, w.meta, st, bb));
+  HIP_OK(trsm_sweep<double>(w.Lp, w.ldp, N, w.Linv, 64, B, ldb, nrhs, pw, false, st, flag, tb));
+  HIP_OK(bk_multi_dsolve(B, ldb, nrhs, N, w.meta, st, bb));
+  HIP_OK(trsm_sweep<double>(w.Lp, w.ldp, N, w.Linv, 64, B, ldb, nrhs, pw, true, st, flag, tb));
+  HIP_OK(bk_multi_scatter(B, ldb, nrhs, N, w.meta, st, bb));
+  HIP_OK(bk_multi_fallback_batch(w.LT, N, ipiv, B, ldb, nrhs, w.meta, st, bb));
+  return IPMZ_OK;
+}
+
 // Mixed-precision multi-right-hand-side solve (mixed_multi.hip, trsm.hip).
 // MIXED_MULTI_PANEL: column panel of the blocked fp32 solve;
 // MIXED_MULTI_CROSSOVER: the number of right-hand sides from which the blocked
@@ -704,6 +790,75 @@ int ipmz_bk_solve_multi(ipmz_ctx* ctx, int N, const double* F, int64_t ld, const
   HIP_OK(hipSetDevice(ctx->device));
   const BkSolveWs w = bk_solve_ws(static_cast<char*>(const_cast<void*>(ws)), N);
   return bk_multi_impl(ctx, N, F, ld, ipiv, w.LT, w.Lp, w.ldp, w.k, B, ldb, nrhs);
+}
+
+// Batches of Bunch-Kaufman systems of one order (one workgroup per matrix) -----
+// what the batch entry points share: the order, the count and the strides of F and ipiv
+// (even_sA: the prepared solve's rule; the factor reads and writes element by element)
+static const char* bk_batch_args(ipmz_ctx* ctx, int N, int batch, int64_t ld, int64_t sA, int64_t sP,
+                                 bool even_sA = true) {
+  if (!ctx || N < 0 || batch < 0 || ld < N) return "bad arguments (N >= 0, batch >= 0, ld >= N)";
+  if (N > IPMZ_BK_NMAX) return "N > 4096 (one workgroup per matrix)";
+  if (batch > 65535) return "batch > 65535";
+  if ((even_sA && (sA & 1)) || (batch > 1 && (sA < (int64_t)(N - 1) * ld + N || sP < N)))
+    return "bad strides (sA even and >= (N - 1) * ld + N, sP >= N)";
+  return nullptr;
+}
+
+int ipmz_bk_factor_batch(ipmz_ctx* ctx, int N, int batch, double* A, int64_t ld, int64_t sA, int* ipiv, int64_t sP,
+                         int fix_kp, int* info) {
+  if (const char* why = bk_batch_args(ctx, N, batch, ld, sA, sP, false))
+    return fail(IPMZ_ERR_INVALID, std::string("ipmz_bk_factor_batch: ") + why);
+  if (batch == 0) return IPMZ_OK;
+  if (N == 0) {
+    if (info) std::memset(info, 0, (size_t)batch * sizeof(int));
+    return IPMZ_OK;
+  }
+  if (!A || !ipiv) return fail(IPMZ_ERR_INVALID, "ipmz_bk_factor_batch: null pointer");
+  HIP_OK(hipSetDevice(ctx->device));
+  int* dinfo = nullptr;
+  HIP_OK(hipMallocAsync(reinterpret_cast<void**>(&dinfo), (size_t)batch * sizeof(int), ctx->stream));
+  int rc;
+  const hipError_t e = bk_factor(A, ld, N, ipiv, dinfo, fix_kp, batch, sA, sP, ctx->stream);
+  if (e != hipSuccess) rc = hip_fail(e, "bk_factor", __FILE__, __LINE__);
+  else rc = bk_batch_info(ctx->stream, dinfo, batch, info);
+  hipFreeAsync(dinfo, ctx->stream);
+  return rc;
+}
+
+int64_t ipmz_bk_batch_solve_workspace_bytes(ipmz_ctx* ctx, int N, int batch) {
+  if (!ctx || N < 0 || batch < 0 || N > IPMZ_BK_NMAX) return 0;
+  return bk_batch_ws(nullptr, N, batch).total;
+}
+
+int ipmz_bk_prepare_solve_batch(ipmz_ctx* ctx, int N, int batch, const double* F, int64_t ld, int64_t sA,
+                                const int* ipiv, int64_t sP, void* ws, int64_t ws_bytes) {
+  if (const char* why = bk_batch_args(ctx, N, batch, ld, sA, sP))
+    return fail(IPMZ_ERR_INVALID, std::string("ipmz_bk_prepare_solve_batch: ") + why);
+  if (N == 0 || batch == 0) return IPMZ_OK;
+  if (!F || !ipiv || !ws) return fail(IPMZ_ERR_INVALID, "ipmz_bk_prepare_solve_batch: null pointer");
+  const BkBatchWs w = bk_batch_ws(static_cast<char*>(ws), N, batch);
+  if (ws_bytes < w.total)
+    return fail(IPMZ_ERR_INVALID,
+                "ipmz_bk_prepare_solve_batch: workspace too small (ipmz_bk_batch_solve_workspace_bytes(N, batch))");
+  HIP_OK(hipSetDevice(ctx->device));
+  return bk_batch_prepare(ctx, N, batch, F, ld, sA, ipiv, sP, nullptr, w);
+}
+
+int ipmz_bk_solve_multi_batch(ipmz_ctx* ctx, int N, int batch, const double* F, int64_t ld, int64_t sA,
+                              const int* ipiv, int64_t sP, const void* ws, double* B, int64_t ldb, int64_t sB,
+                              int nrhs) {
+  if (const char* why = bk_batch_args(ctx, N, batch, ld, sA, sP))
+    return fail(IPMZ_ERR_INVALID, std::string("ipmz_bk_solve_multi_batch: ") + why);
+  if (nrhs < 0 || ldb < N || (ldb & 1) || sB < (int64_t)nrhs * ldb || (sB & 1))
+    return fail(IPMZ_ERR_INVALID, "ipmz_bk_solve_multi_batch: bad arguments (nrhs >= 0, ldb >= N and even, sB >= "
+                                  "nrhs * ldb and even)");
+  if (N == 0 || batch == 0 || nrhs == 0) return IPMZ_OK;
+  if (!F || !ipiv || !ws || !B) return fail(IPMZ_ERR_INVALID, "ipmz_bk_solve_multi_batch: null pointer");
+  if ((uintptr_t)B & 15) return fail(IPMZ_ERR_INVALID, "ipmz_bk_solve_multi_batch: B must be 16-byte aligned");
+  HIP_OK(hipSetDevice(ctx->device));
+  const BkBatchWs w = bk_batch_ws(static_cast<char*>(const_cast<void*>(ws)), N, batch);
+  return bk_batch_multi_impl(ctx, N, batch, F, ld, sA, ipiv, sP, w, B, ldb, sB, nrhs);
 }
 
 // Host adapters with the reference's signatures ------------------------------

@@ -153,6 +153,33 @@ inline BkSolveWs bk_solve_ws(char* base, int N) {
   w.total = c.off + w.k.total;
   return w;
 }
+// The prepared solve of a batch of Bunch-Kaufman factors of one order
+// (ipmz_bk_prepare_solve_batch): per system the factor transposed (LT, N x N),
+// L' (N x ldp), the 64 x 64 inverse diagonal blocks of L' and the interchange
+// bookkeeping with the system's fallback flag -- member by member, each an
+// array over the batch (strides sLT, sLp, sLinv elements, sM bytes).  No
+// persistent-solve operators: no batched path uses the persistent sweeps.
+struct BkBatchWs {
+  double *LT = nullptr, *Lp = nullptr, *Linv = nullptr;
+  char* meta = nullptr;
+  int64_t ldp = 0, sLT = 0, sLp = 0, sLinv = 0, sM = 0;
+  int64_t total = 0;
+};
+inline BkBatchWs bk_batch_ws(char* base, int N, int batch) {
+  BkBatchWs w;
+  Carver c{base};
+  w.ldp = round_up(N, 64);
+  w.sLT = round_up((int64_t)N * N, 32);
+  w.sLp = (int64_t)N * w.ldp;
+  w.sLinv = (int64_t)((N + 63) / 64) * 64 * 64;
+  w.sM = (int64_t)bk_fast_meta_bytes(N);
+  w.LT = c.take<double>(w.sLT * batch);
+  w.Lp = c.take<double>(w.sLp * batch);
+  w.Linv = c.take<double>(w.sLinv * batch);
+  w.meta = c.take<char>(w.sM * batch);
+  w.total = c.off;
+  return w;
+}
 
 // the workspace whose sticky error words the next ipmz_ctx_sync checks (pe:
 // a panel factor's, may be null; se: a persistent solve's)
@@ -198,5 +225,15 @@ hipError_t bk_run(const double* Lp, int64_t ldp, int N, const double* LT, const 
 // caller (ldb even, B 16-byte aligned)
 int bk_multi_impl(ipmz_ctx* ctx, int N, const double* F, int64_t ld, const int* ipiv, const double* LT,
                   const double* Lp, int64_t ldp, const BkWs& w, double* B, int64_t ldb, int nrhs);
+// the same for a batch of prepared factors (bk_batch_prepare: LT, L', the
+// inverse diagonal blocks and the bookkeeping of every system, from the
+// factors' F, ipiv and info words -- info may be null).  Asynchronous, stream
+// order only; arguments checked by the caller
+int bk_batch_prepare(ipmz_ctx* ctx, int N, int batch, const double* F, int64_t ld, int64_t sA, const int* ipiv,
+                     int64_t sP, const int* info, const BkBatchWs& w);
+int bk_batch_multi_impl(ipmz_ctx* ctx, int N, int batch, const double* F, int64_t ld, int64_t sA, const int* ipiv,
+                        int64_t sP, const BkBatchWs& w, double* B, int64_t ldb, int64_t sB, int nrhs);
+// copies the batch's device info words to info (host, may be null), synchronizes, returns the smallest non-zero one
+int bk_batch_info(hipStream_t st, const int* dinfo, int batch, int* info);
 
 #pragma GCC visibility pop

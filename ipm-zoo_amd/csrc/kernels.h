@@ -177,7 +177,9 @@ hipError_t panel_factor(float* K, int64_t ld, int N, int k0, int bo, float* D, f
 // look-ahead update the panel's columns needed last (instead of a
 // cross-stream wait before that launch), then acquire (agent scope)
 hipError_t panel_ready(unsigned* area, hipStream_t st);
-hipError_t linv_from_l(const double* L, int64_t ld, int N, int nbi, double* Linv, hipStream_t st);
+// batch systems behind one launch: L and Linv of consecutive systems sL and sLinv elements apart
+hipError_t linv_from_l(const double* L, int64_t ld, int N, int nbi, double* Linv, hipStream_t st, int batch = 1,
+                       int64_t sL = 0, int64_t sLinv = 0);
 hipError_t gemm_nt_sub(int M, int N, int Kd, const double* A, int64_t lda, const double* B, int64_t ldb,
                        double* C, int64_t ldc, int64_t row0, int64_t col0, bool square_lower, hipStream_t st,
                        const BatchStrides* bs = nullptr);
@@ -204,6 +206,7 @@ hipError_t ldlt_solve(const double* K, int64_t ld, int N, const double* D, const
 struct TrsmBatch {
   int B = 1;
   int64_t sK = 0, sD = 0, sL = 0, sB = 0;
+  int64_t sG = 0;  // trsm_sweep's gate: words between consecutive systems' gate words (0: one word for all)
 };
 template <typename T>
 hipError_t ldlt_solve_multi(const T* K, int64_t ld, int N, const T* D, const T* Linv, int nbi, T* B, int64_t ldb,
@@ -211,7 +214,8 @@ hipError_t ldlt_solve_multi(const T* K, int64_t ld, int N, const T* D, const T* 
 
 // one of its sweeps alone: forward B <- B L^{-T}, backward B <- B L^{-1} (the
 // middle stage is the caller's; same argument rules).  gate (device word, may
-// be null): when set, every launch ends at once if *gate != 0
+// be null): when set, every launch ends at once if *gate != 0 -- per system of
+// a batch when tb.sG != 0 (system q reads gate[q * tb.sG])
 template <typename T>
 hipError_t trsm_sweep(const T* K, int64_t ld, int N, const T* Linv, int nbi, T* B, int64_t ldb, int nrhs, int w,
                       bool backward, hipStream_t st, const unsigned* gate, const TrsmBatch& tb = TrsmBatch());
@@ -313,7 +317,9 @@ hipError_t ne_check_sign(const double* D, int N, int offset, double sign, int* i
 
 
 // bk.hip: Bunch-Kaufman factor / solve (one workgroup per matrix) -----------
+#ifndef IPMZ_BK_NMAX  // (include/ipmz.h publishes the same limit for the batch entry points)
 #define IPMZ_BK_NMAX 4096
+#endif
 hipError_t bk_factor(double* A, int64_t ld, int n, int* ipiv, int* info, int fix_kp, int batch, int64_t sA,
                      int64_t sP, hipStream_t st);
 hipError_t bk_solve(const double* F, int64_t ld, int n, const int* ipiv, double* b, int batch, int64_t sA, int64_t sP,
@@ -328,7 +334,17 @@ const unsigned* bk_grid_err_word(const void* ws, int n);
 // one system's solve through a transposed copy of the factor's lower
 // triangle (LT: n x n doubles, row j = column j of L; bk_transpose once per
 // factor): coalesced sweeps, the same arithmetic as bk_solve
-hipError_t bk_transpose(const double* F, int64_t ld, int n, double* LT, hipStream_t st);
+// A batch of B systems of one order behind the prepared solve's launches (the
+// system is a grid dimension): the factors, pivots, LT, L' and right-hand
+// sides of consecutive systems lie sA, sP, sLT, sLp and sB elements apart;
+// the bookkeeping (meta) of system q starts bk_fast_meta_bytes(n) * q bytes
+// into meta, with a fallback flag of its own.  The default is one system.
+struct BkBatch {
+  int B = 1;
+  int64_t sA = 0, sP = 0, sLT = 0, sLp = 0, sB = 0;
+};
+hipError_t bk_transpose(const double* F, int64_t ld, int n, double* LT, hipStream_t st,
+                        const BkBatch& bb = BkBatch());
 hipError_t bk_solve_lt(const double* LT, int n, const int* ipiv, double* b, hipStream_t st);
 // Device-wide solve: A^{-1} b = P^T L'^{-T} D^{-1} L'^{-1} P b, L' = L with every
 // later interchange folded into its columns (once per factor, bk_fast_prepare:
@@ -345,7 +361,7 @@ const unsigned* bk_fast_flag(const void* meta);
 const double* bk_fast_ones(const void* meta, int n);
 double* bk_fast_tmp(void* meta, int n);
 hipError_t bk_fast_prepare(const double* F, int64_t ld, int n, const int* ipiv, const int* info, double* LT,
-                           double* Lp, int64_t ldp, void* meta, hipStream_t st);
+                           double* Lp, int64_t ldp, void* meta, hipStream_t st, const BkBatch& bb = BkBatch());
 hipError_t bk_fast_gather(const double* b, int n, void* meta, hipStream_t st);
 hipError_t bk_fast_dsolve(double* y, int n, void* meta, hipStream_t st);
 hipError_t bk_fast_scatter(double* b, int n, void* meta, hipStream_t st);
@@ -356,11 +372,42 @@ hipError_t bk_fast_fallback(const double* LT, int n, const int* ipiv, double* b,
 // bk_multi_fallback (one launch, a workgroup per row, run only when the flag
 // is set).  Stream-ordered, nothing waits across workgroups; columns
 // [n, ldb) of B are never written.
-hipError_t bk_multi_gather(double* B, int64_t ldb, int nrhs, int n, void* meta, hipStream_t st);
-hipError_t bk_multi_dsolve(double* B, int64_t ldb, int nrhs, int n, void* meta, hipStream_t st);
-hipError_t bk_multi_scatter(double* B, int64_t ldb, int nrhs, int n, void* meta, hipStream_t st);
+hipError_t bk_multi_gather(double* B, int64_t ldb, int nrhs, int n, void* meta, hipStream_t st,
+                           const BkBatch& bb = BkBatch());
+hipError_t bk_multi_dsolve(double* B, int64_t ldb, int nrhs, int n, void* meta, hipStream_t st,
+                           const BkBatch& bb = BkBatch());
+hipError_t bk_multi_scatter(double* B, int64_t ldb, int nrhs, int n, void* meta, hipStream_t st,
+                            const BkBatch& bb = BkBatch());
 hipError_t bk_multi_fallback(const double* LT, int n, const int* ipiv, double* B, int64_t ldb, int nrhs,
                              const void* meta, hipStream_t st);
+// What the one-launch solve of trsm.hip reads of the bookkeeping (system 0's;
+// system q's lies sM bytes x q further): the fallback flag, the composite
+// interchange, the pivot kinds (0 = 1x1, 1 / 2 = first / second row of a 2x2)
+// and the pivot blocks of D
+struct BkFusedMeta {
+  const unsigned* flag;
+  const int *perm, *kind;
+  const double *d11, *d21, *d22;
+  int64_t sM;
+  __host__ __device__ BkFusedMeta of(unsigned q) const {
+    const int64_t o = (int64_t)q * sM;
+    auto adv = [o](auto* p) { return reinterpret_cast<decltype(p)>(reinterpret_cast<const char*>(p) + o); };
+    return {adv(flag), adv(perm), adv(kind), adv(d11), adv(d21), adv(d22), sM};
+  }
+};
+BkFusedMeta bk_fused_meta(const void* meta, int n, const BkBatch& bb);
+// The whole prepared solve of small systems in ONE launch per batch
+// (trsm_bk_fused_kernel: gather, forward sweep, D solve, backward sweep and
+// scatter on a slab that stays in LDS), eligible as ldlt_solve_fused is with
+// inner block 64; Lp, Linv as trsm_sweep's K, Linv (tb.sK, tb.sL), tb.sB the
+// systems' right-hand sides.  Flagged systems are skipped (bk_multi_fallback_batch).
+bool bk_solve_fused_eligible(int N);
+hipError_t bk_solve_fused(const double* Lp, int64_t ldp, int N, const double* Linv, double* B, int64_t ldb, int nrhs,
+                          const BkFusedMeta& m, hipStream_t st, const TrsmBatch& tb);
+// the batch's fallback: one workgroup per (system, row), the reference's
+// interleaved sweeps on that system's LT, run only where the system's flag is set
+hipError_t bk_multi_fallback_batch(const double* LT, int n, const int* ipiv, double* B, int64_t ldb, int nrhs,
+                                   const void* meta, hipStream_t st, const BkBatch& bb);
 
 // newton.hip -----------------------------------------------------------------
 enum Slot { X = 0, LA, LC, S, P, LG, LH, LY, LZ, G, H, Y, Z, NSLOT };

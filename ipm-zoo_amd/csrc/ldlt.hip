@@ -236,8 +236,10 @@ __global__ __launch_bounds__(256) void ldlt_diag64_blk_kernel(double* __restrict
 // was not produced by ldlt_factor (ipmz_overwriting_solve_ldlt).
 template <int NB, int NT>
 __global__ __launch_bounds__(NT) void linv_from_l_kernel(const double* __restrict__ L, int64_t ld, int N,
-                                                         double* __restrict__ Linv) {
+                                                         double* __restrict__ Linv, int64_t sL, int64_t sLinv) {
   __shared__ double M[NB][NB + 1];
+  L += blockIdx.y * sL;  // system blockIdx.y of a batch
+  Linv += blockIdx.y * sLinv;
   const int k0 = blockIdx.x * NB;
   const int b = N - k0 < NB ? N - k0 : NB;
   const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
@@ -261,13 +263,14 @@ __global__ __launch_bounds__(NT) void linv_from_l_kernel(const double* __restric
   }
 }
 
-hipError_t linv_from_l(const double* L, int64_t ld, int N, int nbi, double* Linv, hipStream_t st) {
+hipError_t linv_from_l(const double* L, int64_t ld, int N, int nbi, double* Linv, hipStream_t st, int batch,
+                       int64_t sL, int64_t sLinv) {
   const int nblk = (N + nbi - 1) / nbi;
-  if (nblk == 0) return hipSuccess;
+  if (nblk == 0 || batch <= 0) return hipSuccess;
   if (nbi == 128)
-    hipLaunchKernelGGL((linv_from_l_kernel<128, 512>), dim3(nblk), dim3(512), 0, st, L, ld, N, Linv);
+    hipLaunchKernelGGL((linv_from_l_kernel<128, 512>), dim3(nblk, batch), dim3(512), 0, st, L, ld, N, Linv, sL, sLinv);
   else if (nbi == 64)
-    hipLaunchKernelGGL((linv_from_l_kernel<64, 256>), dim3(nblk), dim3(256), 0, st, L, ld, N, Linv);
+    hipLaunchKernelGGL((linv_from_l_kernel<64, 256>), dim3(nblk, batch), dim3(256), 0, st, L, ld, N, Linv, sL, sLinv);
   else
     return hipErrorInvalidValue;
   return hipGetLastError();

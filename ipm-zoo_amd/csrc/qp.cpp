@@ -50,6 +50,7 @@ struct ipmz_qp {
   double* bklt = nullptr;  // its factor transposed (N x N): the interchange folding's input, the fallback's factor
   char* bkfws = nullptr;   // the device-wide solve's workspace (bk_ws), L' in K
   char* bkmws = nullptr;   // ipmz_qp_kkt_solve_bk below that order: its prepared solve (bk_solve_ws), on first use
+  char* bkbws = nullptr;   // ipmz_batch_kkt_solve_bk: the batch's prepared solves (bk_batch_ws), on first use
   unsigned* pflags = nullptr;  // B > 1: the two-workgroup small factor's flags + sticky error word
   int small_kernel = IPMZ_BATCH_FACTOR_AUTO;  // ipmz_batch_set_factor_kernel
   bool eqpen = false;  // EqualityHandling::PenaltyFunction (LDL^T)
@@ -1010,6 +1011,52 @@ int ipmz_batch_kkt_solve(ipmz_qp* s, int nrhs, double* B, int64_t ldb, int64_t s
   return ws_result(st, s->binfo, pair ? s->pflags + (size_t)s->B * IPMZ_PAIR_FLAGS : nullptr, nullptr,
                    "ipmz_batch_kkt_solve",
                    ": a hand-off of the two-workgroup batched factor timed out; the factor is invalid");
+}
+
+int ipmz_batch_kkt_solve_bk(ipmz_qp* s, int nrhs, double* B, int64_t ldb, int64_t sB, int* info) {
+  if (!s) return fail(IPMZ_ERR_INVALID, "null qp");
+  if (s->B == 1) {
+    const int rc = ipmz_qp_kkt_solve_bk(s, nrhs, B, ldb);
+    if (info) info[0] = rc;
+    return rc;
+  }
+  if (!s->eqnone || s->normal || s->mixed)
+    return fail(IPMZ_ERR_INVALID, "ipmz_batch_kkt_solve_bk: EqualityHandling::None batches only (the Bunch-Kaufman "
+                                  "factor); the LDL^T handlings solve with ipmz_batch_kkt_solve");
+  if (!s->loaded) return fail(IPMZ_ERR_STATE, "ipmz_batch_kkt_solve_bk: load and initialize the batch first");
+  if (nrhs < 0 || ldb < s->N || (ldb & 1) || sB < (int64_t)nrhs * ldb || (sB & 1) || (nrhs > 0 && !B))
+    return fail(IPMZ_ERR_INVALID, "ipmz_batch_kkt_solve_bk: bad arguments (nrhs >= 0, ldb >= N and even, sB >= nrhs "
+                                  "* ldb and even)");
+  if (nrhs > 0 && ((uintptr_t)B & 15))
+    return fail(IPMZ_ERR_INVALID, "ipmz_batch_kkt_solve_bk: B must be 16-byte aligned");
+  if (s->N > IPMZ_BK_NMAX || s->B > 65535)
+    return fail(IPMZ_ERR_INVALID, "ipmz_batch_kkt_solve_bk: N <= 4096 and batch <= 65535");
+  HIP_OK(hipSetDevice(s->ctx->device));
+  int rc = not_capturing(s->ctx, "ipmz_batch_kkt_solve_bk");
+  if (rc) return rc;
+  hipStream_t st = s->ctx->stream;
+  // the prepared solves' workspace is this call's own, allocated on first use and kept
+  if (!s->bkbws) {
+    void* w = nullptr;
+    if (hipMalloc(&w, (size_t)bk_batch_ws(nullptr, s->N, s->B).total) != hipSuccess) {
+      (void)hipGetLastError();
+      return fail(IPMZ_ERR_NOMEM, "device allocation failed");
+    }
+    s->allocs.push_back(w);
+    s->bkbws = static_cast<char*>(w);
+  }
+  // the step's own assembly and batched factor, on the storage the next step
+  // overwrites anyway (it assembles and factors again): the iterate is only
+  // read.  (No forked step to wait for: step_forks is false for batches.)
+  HIP_OK(qp_assemble(s->qb, st));
+  if ((rc = factor_batch(s, nullptr, false))) return rc;
+  if (nrhs > 0) {
+    const BkBatchWs w = bk_batch_ws(s->bkbws, s->N, s->B);
+    if ((rc = bk_batch_prepare(s->ctx, s->N, s->B, s->K, s->ldk, s->sK, s->ipiv, s->sP, s->binfo, w))) return rc;
+    if ((rc = bk_batch_multi_impl(s->ctx, s->N, s->B, s->K, s->ldk, s->sK, s->ipiv, s->sP, w, B, ldb, sB, nrhs)))
+      return rc;
+  }
+  return bk_batch_info(st, s->binfo, s->B, info);  // synchronizes
 }
 
 int ipmz_qp_kkt_solve(ipmz_qp* s, int nrhs, double* B, int64_t ldb) {

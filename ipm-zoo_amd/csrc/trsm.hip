@@ -31,8 +31,8 @@
 //
 // Every panel-solve and update launch takes a gate (a device word, may be
 // null): a non-null gate whose word is not 0 ends the kernel before any load
-// (the Bunch-Kaufman solve's fallback flag, bk.hip); the LDL^T callers pass
-// null.
+// (the Bunch-Kaufman solve's fallback flag, bk.hip; a batch's systems have a
+// flag each, TrsmBatch::sG words apart); the LDL^T callers pass null.
 //
 // No kernel here waits for another workgroup: right-hand sides are
 // independent, a panel-solve workgroup owns 16 of them, an update workgroup
@@ -342,8 +342,8 @@ template <typename T, int NBI, bool BWD>
 __global__ __launch_bounds__(TM_NT) void trsm_panel_kernel(const T* __restrict__ K, int64_t ld, int N,
                                                            const T* __restrict__ Linv, int nbi_rt, T* B, int64_t ldb,
                                                            int nrhs, int p0, int w, const unsigned* gate, int64_t sK,
-                                                           int64_t sL, int64_t sB) {
-  if (gate && *gate != 0u) return;
+                                                           int64_t sL, int64_t sB, int64_t sG) {
+  if (gate && gate[blockIdx.y * sG] != 0u) return;
   K += blockIdx.y * sK;
   Linv += blockIdx.y * sL;
   B += blockIdx.y * sB;
@@ -481,6 +481,71 @@ __global__ __launch_bounds__(TM_NT) void trsm_fused_kernel(const double* __restr
   slab_store<double>(B, ldb, nrhs, r0, 0, N, w, slab, SP);
 }
 
+// The whole prepared Bunch-Kaufman solve of one small system in one workgroup
+// (bk.hip "Device-wide solve": A^{-1} = P^T L'^{-T} D^{-1} L'^{-1} P): right-hand
+// sides [16 * blockIdx.x, +16) of system blockIdx.y.  trsm_fused_kernel's
+// design on L' (K = L', unit lower, inner block 64): the slab is loaded
+// through perm (the row permutation fused into the load, 8-byte loads), goes
+// through the forward stream, the D solve in the reference's arithmetic
+// (bkf::k_dsolve_rows' expressions; a 2x2 pivot's two entries are both in the
+// slab, wherever the pair lies against the 64-column blocks), the backward
+// stream, and is stored through perm.  It shares panel_stream with
+// trsm_fused_kernel -- the panel kernels keep their inline copy, so their
+// registers do not change.  A system whose fallback flag is set is left to
+// the fallback launch: its workgroups exit before any load.
+__global__ __launch_bounds__(TM_NT) void trsm_bk_fused_kernel(const double* __restrict__ K, int64_t ld, int N,
+                                                              const double* __restrict__ Linv, double* B, int64_t ldb,
+                                                              int nrhs, BkFusedMeta m, int64_t sK, int64_t sL,
+                                                              int64_t sB) {
+  constexpr int V = Mfma<double>::V;
+  m = m.of(blockIdx.y);
+  if (m.flag[0] != 0u) return;
+  extern __shared__ __attribute__((aligned(16))) unsigned char trsm_sm[];
+  K += blockIdx.y * sK;
+  Linv += blockIdx.y * sL;
+  B += blockIdx.y * sB;
+  const int w = (N + TM_SB - 1) / TM_SB * TM_SB;
+  const int SP = w + V, TP = TM_SB + V;
+  double* slab = reinterpret_cast<double*>(trsm_sm);
+  double* Ts = slab + TM_G * SP;
+  double* Ls = Ts + TM_G * TP;
+  const int r0 = blockIdx.x * TM_G;
+  const PanelGeom<double> g = {K, ld, N, Linv, TM_SB, 0, N, SP, TP};
+  // slab[r][p] = b_r[perm[p]]; rows >= nrhs and columns >= N are zero and never stored
+  panel_stream<double, TM_SB, false>(g, slab, Ts, Ls, [&] {
+    for (int idx = threadIdx.x; idx < TM_G * w; idx += TM_NT) {
+      const int r = idx / w, c = idx % w;
+      slab[r * SP + c] = (r0 + r < nrhs && c < N) ? B[(int64_t)(r0 + r) * ldb + m.perm[c]] : 0.0;
+    }
+  });
+  // Z = D^{-1} Y: the thread on the first row of a 2x2 pivot writes both entries of its pair
+  for (int k = threadIdx.x; k < N; k += TM_NT) {
+    const int kd = m.kind[k];
+    if (kd == 0) {
+      const double d = m.d11[k];
+#pragma unroll 4
+      for (int r = 0; r < TM_G; ++r) slab[r * SP + k] = slab[r * SP + k] / d;
+    } else if (kd == 1 && k + 1 < N) {
+      const double akm1k = m.d21[k];
+      const double akm1 = m.d11[k] / akm1k;
+      const double ak = m.d22[k] / akm1k;
+      const double denom = akm1 * ak - 1.0;
+#pragma unroll 2
+      for (int r = 0; r < TM_G; ++r) {
+        const double bkm1 = slab[r * SP + k] / akm1k;
+        const double bk = slab[r * SP + k + 1] / akm1k;
+        slab[r * SP + k] = (ak * bkm1 - bk) / denom;
+        slab[r * SP + k + 1] = (akm1 * bk - bkm1) / denom;
+      }
+    }
+  }
+  panel_stream<double, TM_SB, true>(g, slab, Ts, Ls, [] {});  // (its first barrier orders the D solve before T)
+  for (int idx = threadIdx.x; idx < TM_G * w; idx += TM_NT) {
+    const int r = idx / w, c = idx % w;
+    if (r0 + r < nrhs && c < N) B[(int64_t)(r0 + r) * ldb + m.perm[c]] = slab[r * SP + c];
+  }
+}
+
 // between the sweeps: B[r][j] /= D[j] (a division, LinearSolvers.cpp:62-64);
 // system blockIdx.z (strides sB, sD)
 template <typename T>
@@ -518,8 +583,9 @@ struct UpdStage {
 template <typename T, bool NN>
 __global__ __launch_bounds__(UN_NT) void trsm_update_kernel(const T* X, int64_t ldx, const T* __restrict__ L,
                                                             int64_t ldl, T* C, int64_t ldc, int M, int Nc, int Kd,
-                                                            int ntm, const unsigned* gate, int64_t sX, int64_t sL) {
-  if (gate && *gate != 0u) return;
+                                                            int ntm, const unsigned* gate, int64_t sX, int64_t sL,
+                                                            int64_t sG) {
+  if (gate && gate[blockIdx.y * sG] != 0u) return;
   typedef typename Mfma<T>::vec16_t vec_t;
   typedef typename Mfma<T>::acc_t acc_t;
   constexpr int V = Mfma<T>::V, BK = 8 * V, PADA = BK + V, BSTAGE = BK * UN_PADB;
@@ -600,7 +666,7 @@ hipError_t launch_update(const T* X, int64_t ldx, const T* L, int64_t ldl, T* C,
                          hipStream_t st, const unsigned* gate, const TrsmBatch& tb) {
   const int ntm = (M + UN_BM - 1) / UN_BM, ntn = (Nc + UN_BN - 1) / UN_BN;
   hipLaunchKernelGGL((trsm_update_kernel<T, NN>), dim3((unsigned)(ntm * ntn), (unsigned)tb.B), dim3(UN_NT), 0, st, X,
-                     ldx, L, ldl, C, ldc, M, Nc, Kd, ntm, gate, tb.sB, tb.sK);
+                     ldx, L, ldl, C, ldc, M, Nc, Kd, ntm, gate, tb.sB, tb.sK, tb.sG);
   return hipGetLastError();
 }
 
@@ -615,7 +681,7 @@ hipError_t launch_panel(const T* K, int64_t ld, int N, const T* Linv, int nbi, T
   if (attr != hipSuccess) return attr;
   hipLaunchKernelGGL((trsm_panel_kernel<T, NBI, BWD>), dim3((nrhs + TM_G - 1) / TM_G, (unsigned)tb.B), dim3(TM_NT),
                      panel_lds_bytes<T>(w, nbi), st, K, ld, N, Linv, nbi, B, ldb, nrhs, p0, w, gate, tb.sK, tb.sL,
-                     tb.sB);
+                     tb.sB, tb.sG);
   return hipGetLastError();
 }
 
@@ -722,6 +788,25 @@ hipError_t ldlt_solve_fused(const double* K, int64_t ld, int N, const double* D,
   else
     hipLaunchKernelGGL(trsm_fused_kernel<0>, grid, dim3(TM_NT), lds, st, K, ld, N, D, Linv, nbi, B, ldb, nrhs, tb.sK,
                        tb.sD, tb.sL, tb.sB);
+  return hipGetLastError();
+}
+
+bool bk_solve_fused_eligible(int N) { return ldlt_solve_fused_eligible(N, TM_SB); }
+
+hipError_t bk_solve_fused(const double* Lp, int64_t ldp, int N, const double* Linv, double* B, int64_t ldb, int nrhs,
+                          const BkFusedMeta& m, hipStream_t st, const TrsmBatch& tb) {
+  if (N <= 0 || nrhs <= 0) return hipSuccess;
+  if (!bk_solve_fused_eligible(N) || (ldp & 1) || ldp < N || ldb < N || ((uintptr_t)Lp & 15) ||
+      ((uintptr_t)Linv & 15) || !batch_ok(tb))
+    return hipErrorInvalidValue;
+  // all the LDS a workgroup may have; raised once per process
+  static const hipError_t attr =
+      hipFuncSetAttribute(reinterpret_cast<const void*>(&trsm_bk_fused_kernel),
+                          hipFuncAttributeMaxDynamicSharedMemorySize, (int)device_lds_per_workgroup());
+  if (attr != hipSuccess) return attr;
+  const int w = (N + TM_SB - 1) / TM_SB * TM_SB;
+  hipLaunchKernelGGL(trsm_bk_fused_kernel, dim3((nrhs + TM_G - 1) / TM_G, (unsigned)tb.B), dim3(TM_NT),
+                     panel_lds_bytes<double>(w, TM_SB), st, Lp, ldp, N, Linv, B, ldb, nrhs, m, tb.sK, tb.sL, tb.sB);
   return hipGetLastError();
 }
 

@@ -51,6 +51,8 @@ EXPORTS = [
     "ipmz_bk_solve_workspace_bytes", "ipmz_bk_prepare_solve", "ipmz_bk_solve_multi",
     "ipmz_overwriting_solve_bunch_kaufman_multi", "ipmz_normal_solve_multi", "ipmz_qp_kkt_solve_bk",
     "ipmz_batch_get_kkt", "ipmz_batch_kkt_solve",
+    "ipmz_bk_factor_batch", "ipmz_bk_batch_solve_workspace_bytes", "ipmz_bk_prepare_solve_batch",
+    "ipmz_bk_solve_multi_batch", "ipmz_batch_kkt_solve_bk",
 ]
 SOLVE_MULTI_PANEL = 256  # include/ipmz.h IPMZ_SOLVE_MULTI_PANEL: column panel of the blocked multi-rhs solve
 REDUCTION_AUGMENTED, REDUCTION_NORMAL = 0, 1
@@ -171,6 +173,11 @@ def _load():
         "ipmz_qp_kkt_solve_bk": ([_VP, _I, _VP, _I64], _I),
         "ipmz_batch_get_kkt": ([_VP, _I, _P], _I),
         "ipmz_batch_kkt_solve": ([_VP, _I, _VP, _I64, _I64], _I),
+        "ipmz_bk_factor_batch": ([_VP, _I, _I, _VP, _I64, _I64, _VP, _I64, _I, ctypes.POINTER(_I)], _I),
+        "ipmz_bk_batch_solve_workspace_bytes": ([_VP, _I, _I], _I64),
+        "ipmz_bk_prepare_solve_batch": ([_VP, _I, _I, _VP, _I64, _I64, _VP, _I64, _VP, _I64], _I),
+        "ipmz_bk_solve_multi_batch": ([_VP, _I, _I, _VP, _I64, _I64, _VP, _I64, _VP, _VP, _I64, _I64, _I], _I),
+        "ipmz_batch_kkt_solve_bk": ([_VP, _I, _VP, _I64, _I64, ctypes.POINTER(_I)], _I),
     }
     for name, (args, res) in sig.items():
         fn = getattr(lib, name)
@@ -319,6 +326,30 @@ class Context:
         """Every row of B (device, nrhs rows, stride ldb) <- A^{-1} row, from the prepared solve in ws."""
         return _check(lib.ipmz_bk_solve_multi(self.h, N, _VP(F_ptr), ld, _VP(ipiv_ptr), _VP(ws_ptr), _VP(B_ptr), ldb,
                                               nrhs), "ipmz_bk_solve_multi")
+
+    # -- batches of Bunch-Kaufman systems of one order (N <= 4096, one workgroup per matrix) --
+    def bk_factor_batch(self, N, batch, A_ptr, ld, sA, ipiv_ptr, sP, fix_kp=False):
+        """bk_factor(algo=BK_WORKGROUP) of every matrix A + q * sA (pivots at ipiv + q * sP) in one
+        launch; returns (the smallest non-zero info word or 0, the per-matrix info words)."""
+        info = np.zeros(max(batch, 0), dtype=np.int32)
+        rc = _check(lib.ipmz_bk_factor_batch(self.h, N, batch, _VP(A_ptr), ld, sA, _VP(ipiv_ptr), sP, int(fix_kp),
+                                             info.ctypes.data_as(ctypes.POINTER(_I))), "ipmz_bk_factor_batch")
+        return rc, info
+
+    def bk_batch_solve_workspace_bytes(self, N, batch):
+        return lib.ipmz_bk_batch_solve_workspace_bytes(self.h, N, batch)
+
+    def bk_prepare_solve_batch(self, N, batch, F_ptr, ld, sA, ipiv_ptr, sP, ws_ptr, ws_bytes):
+        """Once per batch of factors: the prepared solves of bk_solve_multi_batch, built in ws."""
+        return _check(lib.ipmz_bk_prepare_solve_batch(self.h, N, batch, _VP(F_ptr), ld, sA, _VP(ipiv_ptr), sP,
+                                                      _VP(ws_ptr), ws_bytes), "ipmz_bk_prepare_solve_batch")
+
+    def bk_solve_multi_batch(self, N, batch, F_ptr, ld, sA, ipiv_ptr, sP, ws_ptr, B_ptr, ldb, sB, nrhs):
+        """For every system q: the nrhs rows at B + q * sB (device, row stride ldb) <- A_q^{-1} row,
+        from the prepared solves in ws; in place, asynchronous."""
+        return _check(lib.ipmz_bk_solve_multi_batch(self.h, N, batch, _VP(F_ptr), ld, sA, _VP(ipiv_ptr), sP,
+                                                    _VP(ws_ptr), _VP(B_ptr), ldb, sB, nrhs),
+                      "ipmz_bk_solve_multi_batch")
 
     # -- normal equations (C2) --
     def normal_workspace_bytes(self, n, mp):
@@ -684,6 +715,15 @@ class Batch(Optimizer):
         factor's info word.  A contiguous (batch, nrhs, ldb) torch tensor has sB = nrhs * ldb.
         fp64 LDL^T batches only (not EQ_NONE); the inherited kkt_solve stays for single QPs."""
         return _check(lib.ipmz_batch_kkt_solve(self.h, nrhs, _VP(B_ptr), ldb, sB), "ipmz_batch_kkt_solve")
+
+    def kkt_solve_all_bk(self, B_ptr, nrhs, ldb, sB):
+        """kkt_solve_all for EQ_NONE batches: the step's batched Bunch-Kaufman factor, then
+        bk_solve_multi_batch on the rows of every QP; returns (the smallest non-zero per-QP
+        info word or 0, the per-QP info words)."""
+        info = np.zeros(self.batch, dtype=np.int32)
+        rc = _check(lib.ipmz_batch_kkt_solve_bk(self.h, nrhs, _VP(B_ptr), ldb, sB,
+                                                info.ctypes.data_as(ctypes.POINTER(_I))), "ipmz_batch_kkt_solve_bk")
+        return rc, info
 
     def batch_scalars(self):
         out = np.zeros(self.batch * SC_COUNT)
