@@ -49,6 +49,12 @@
  *                                  compute_search_direction_ (:344-380), two
  *                                  get_max_step_ (:270-342), update (:222-231)
  *   ipmz_qp_solve               <- Optimizer::solve (Optimizer.h:20, Optimizer.cpp:63-73)
+ *   ipmz_qp_newton_solve_multi, ipmz_batch_newton_solve_multi
+ *                               <- the multi-row form of Optimizer::compute_search_direction_
+ *                                  (:344-380) with get_max_step_ (:270-342): full residual
+ *                                  vectors r_v of the Newton system in, full Newton
+ *                                  directions and their maximum steps out, any number of
+ *                                  rows from one factor, for a QP or every QP of a batch
  *
  * Conventions
  *   - Plain pointers and sizes only.  "device" pointers are HIP device
@@ -606,6 +612,78 @@ int ipmz_batch_kkt_solve(ipmz_qp* qp, int nrhs, double* B, int64_t ldb, int64_t 
  * load and ipmz_batch_initialize, and while the stream is capturing.  A solver that holds one
  * QP forwards to ipmz_qp_kkt_solve_bk: sB is then ignored and info[0] is the return value. */
 int ipmz_batch_kkt_solve_bk(ipmz_qp* qp, int nrhs, double* B, int64_t ldb, int64_t sB, int* info);
+
+/* compute_search_direction_ (Optimizer.cpp:344-380) for a block of residual
+ * vectors, plus get_max_step_ (Optimizer.cpp:270-342) of every direction: for
+ * every QP q of the solver and every row r < nrhs, the full Newton direction d
+ * of J d = -r at the current iterate, J the Jacobian of the formulation's
+ * Newton system (tests/golden/formulations.txt, "newton system / lhs").
+ *
+ * Rows: with L = ipmz_qp_state_len(qp), row r of QP q of R is at R + q * sR +
+ * r * ldr (device) and holds L doubles: the residual vectors r_v in Newton
+ * order, the layout of ipmz_qp_get_state(.., IPMZ_STATE_RES, ..) ("shorthand
+ * definitions" of formulations.txt).  Dir has the same shape (q * sD + r *
+ * ldd) and receives the full direction in the layout of IPMZ_STATE_DAFF.  Per
+ * row: the augmented right-hand side from the row's r_v and the iterate (the
+ * step's own expressions), K^{-1} of it, then the delta_definitions in reverse
+ * (the step's own back-substitution).  mu does not enter: the caller has put
+ * whatever mu and corrector terms it wants into R.  The row
+ * ipmz_qp_get_state(IPMZ_STATE_RES) of a fresh iterate gives the affine
+ * direction the next step computes (IPMZ_STATE_DAFF after it).
+ *
+ * alpha (device, batch * nrhs doubles, QP-major, may be NULL): alpha[q * nrhs
+ * + r] = get_max_step_ of (the iterate, row r's direction) before the 0.995
+ * factor -- what a step stores in IPMZ_SC_ALPHA_AFF / IPMZ_SC_ALPHA -- by the
+ * step's rules, the explicit l_x, u_x, l_A, u_A bounds of box-only and
+ * IPMZ_INEQ_SLACKS forms included.
+ *
+ * Factor, by the solver's formulation: the fp64 augmented LDL^T for every
+ * equality handling but IPMZ_EQ_NONE, Bunch-Kaufman for IPMZ_EQ_NONE (any N for
+ * a single QP, N <= 4096 for batches): the step's own assembly and factor on
+ * the storage the next step overwrites anyway, then the blocked solves of
+ * ipmz_qp_kkt_solve / _bk and ipmz_batch_kkt_solve / _bk with their crossovers
+ * and kernels.  The reduced right-hand sides live in a workspace of the solver
+ * (batch * nrhs * round_up(N, 2) doubles, allocated on first use, grown for
+ * the largest nrhs seen, freed with the solver; IPMZ_ERR_NOMEM when it cannot
+ * be had), not in Dir: the solves see rows of stride round_up(N, 2) whatever
+ * ldd is, and nothing relies on the head of a Newton-order row being the KKT
+ * order.
+ *
+ * Arguments: nrhs >= 0 (nrhs == 0 still assembles, factors and returns the
+ * info word); ldr >= L, ldd >= L, both even; sR >= nrhs * ldr, sD >= nrhs *
+ * ldd, both even; R and Dir 16-byte aligned.  Dir[q][r][L .. ldd) and
+ * everything between nrhs * ldd and sD keep their bits.  R is never written
+ * unless it is Dir: Dir == R with ldd == ldr and sD == sR is allowed (in place
+ * -- every element of a row is read and written by exactly one thread of the
+ * back-substitution); any other overlap is the caller's error and is not
+ * detected.
+ *
+ * Returns what the matching *_kkt_solve* call returns: the factor's info word,
+ * after the sticky error words were checked; synchronizes once, at the end.
+ * info (host, batch ints, may be NULL): per QP for IPMZ_EQ_NONE batches, as in
+ * ipmz_batch_kkt_solve_bk; otherwise every entry is the return value.  A
+ * solver that holds one QP forwards from the batch call to the single one (sR
+ * and sD ignored).
+ *
+ * The iterate, the step's own right-hand side, direction and residual slots,
+ * the scalar block, the matrix the fused steps keep across steps, a captured
+ * step graph (IPMZ_STEP_GRAPH) and all later steps are unchanged, bitwise.
+ * Stream-ordered launches only, no cross-workgroup waiting, no atomics: a
+ * row's result does not depend on the other rows of the call, a QP's not on
+ * the other QPs (given the same kernel selection), equal inputs give equal
+ * bits.
+ *
+ * IPMZ_ERR_INVALID: an enabled normal-equations reduction or mixed precision;
+ * IPMZ_EQ_SLACKED_SLACKS / IPMZ_EQ_NAIVE_SLACKS (their public state is a
+ * permuted, merged view of the step's slots; the device permutation this call
+ * would need is a follow-up); bad strides or alignment; IPMZ_EQ_NONE batches
+ * with N > 4096.  IPMZ_ERR_STATE before a load, between a load and
+ * ipmz_batch_initialize, and while the context's stream is capturing. */
+int ipmz_qp_newton_solve_multi(ipmz_qp* qp, int nrhs, const double* R, int64_t ldr, double* Dir, int64_t ldd,
+                               double* alpha /* device, nrhs, may be NULL */);
+int ipmz_batch_newton_solve_multi(ipmz_qp* qp, int nrhs, const double* R, int64_t ldr, int64_t sR, double* Dir,
+                                  int64_t ldd, int64_t sD, double* alpha /* device, batch*nrhs, QP-major, may be NULL */,
+                                  int* info /* host, batch ints, may be NULL */);
 
 /* Phase timing (HIP events on the context stream; eager launches only).
  * ms: host array of IPMZ_PH_COUNT floats, cumulative since enable. */

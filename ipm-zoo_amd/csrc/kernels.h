@@ -48,14 +48,17 @@ namespace ipmz {
 //         eligible, and both together the panel chain at IPMZ_SOLVE_MULTI_PANEL,
 // 524288 / 1048576 = the persistent solve splits every 128-row block over 2 / 4 workgroups, whatever
 //         its table says; both bits = the unsplit solve (all three bitwise alike,
-//         tests/test_gpu_solve_split.py)
+//         tests/test_gpu_solve_split.py),
+// 2097152 / 4194304 = ipmz_*_newton_solve_multi's element-wise kernels take 1 / 8 rows per thread instead
+//         of IPMZ_NEWTON_MULTI_RPG; both bits = 2 (A/B, tools/newton_multi_bench.py; the same bits in every row)
 enum { IPMZ_INJECT_SOLVE = 1, IPMZ_INJECT_PANEL = 2, IPMZ_INJECT_GRAPH_FORKS = 4, IPMZ_DEBUG_CONVERT_ONLY = 16,
        IPMZ_DEBUG_ONE_STREAM = 32, IPMZ_DEBUG_TRACE = 64, IPMZ_DEBUG_F32_ENGINE = 128,
        IPMZ_DEBUG_NO_FOURTH = 256, IPMZ_DEBUG_IR_FULL = 512,
        IPMZ_DEBUG_F64_ENGINE = 1024, IPMZ_DEBUG_GIVEBACK = 2048, IPMZ_DEBUG_ROWS_CHAIN = 4096,
        IPMZ_DEBUG_NO_K0 = 8192, IPMZ_DEBUG_NO_FUSED_SOLVES = 16384, IPMZ_DEBUG_READY_LATE = 32768,
        IPMZ_DEBUG_MULTI_BLOCKED = 65536, IPMZ_DEBUG_MULTI_W512 = 131072,
-       IPMZ_DEBUG_MULTI_W128 = 262144, IPMZ_DEBUG_SOLVE_H2 = 524288, IPMZ_DEBUG_SOLVE_H4 = 1048576 };
+       IPMZ_DEBUG_MULTI_W128 = 262144, IPMZ_DEBUG_SOLVE_H2 = 524288, IPMZ_DEBUG_SOLVE_H4 = 1048576,
+       IPMZ_DEBUG_NEWTON_RPG1 = 2097152, IPMZ_DEBUG_NEWTON_RPG8 = 4194304 };
 #define IPMZ_TRACE(...)                                                  \
   do {                                                                   \
     if (::ipmz::debug_inject_mask() & ::ipmz::IPMZ_DEBUG_TRACE) {        \
@@ -481,6 +484,18 @@ hipError_t qp_assemble(const QPBatch& qb, hipStream_t st);
 hipError_t qp_rhs(const QPBatch& qb, hipStream_t st);
 hipError_t qp_backsub(const QPBatch& qb, int which, hipStream_t st);
 hipError_t qp_ratio(const QPBatch& qb, int which, int out_index, hipStream_t st);
+// The same three for a block of residual vectors per QP (ipmz_*_newton_solve_multi):
+// row r of QP z of R (at R + z sR + r ldr, Newton order) -> its augmented rhs
+// in row r of W; the solved W and R -> the full direction in row r of D (may
+// be R, same strides); get_max_step_ of every row -> alpha[z nrhs + r].
+// IPMZ_NEWTON_MULTI_RPG: rows one thread takes at once (one row group of the grid).
+#define IPMZ_NEWTON_MULTI_RPG 4
+hipError_t qp_rhs_multi(const QPBatch& qb, const double* R, int64_t ldr, int64_t sR, double* W, int64_t ldw, int64_t sW,
+                        int nrhs, hipStream_t st);
+hipError_t qp_backsub_multi(const QPBatch& qb, const double* R, int64_t ldr, int64_t sR, const double* W, int64_t ldw,
+                            int64_t sW, double* D, int64_t ldd, int64_t sD, int nrhs, hipStream_t st);
+hipError_t qp_ratio_multi(const QPBatch& qb, const double* D, int64_t ldd, int64_t sD, double* alpha, int nrhs,
+                          hipStream_t st);
 hipError_t qp_mu_aff(const QPBatch& qb, hipStream_t st);
 hipError_t qp_corrector_residuals(const QPBatch& qb, hipStream_t st);
 hipError_t qp_update(const QPBatch& qb, int freeze, hipStream_t st);

@@ -1,7 +1,9 @@
 // Newton-step kernels around the factorization: synthetic QP generation,
 // build_environment's initial iterate, residual (shorthand) vectors,
 // KKT assembly, augmented rhs, eliminated-variable back-substitution, ratio
-// tests, mu / sigma, corrector residuals and the iterate update.
+// tests, mu / sigma, corrector residuals and the iterate update; and the rhs,
+// back-substitution and ratio test of a caller's block of residual vectors
+// (ipmz_*_newton_solve_multi), the same formulas over another accessor.
 //
 // Formulations (tests/golden/formulations.txt is the reference's own
 // symbolic output these formulas restate): InequalityHandling::SlackedSlacks
@@ -522,55 +524,172 @@ hipError_t qp_assemble(const QPBatch& qb, hipStream_t st) {
   return hipGetLastError();
 }
 
+// Where the residual vectors r_v, the augmented vector b and the directions of
+// rhs_elem / backsub_elem / ratio_elem live -- the formulas themselves are
+// written once, over an accessor IO: r(slot, i) reads r_v, b(t) is where the
+// augmented rhs goes, x(t) reads the solved vector, d(slot, i) is a direction
+// element, val_t the value type and zero() its zero.
+//   DSel    the step's own slots of the QPDev: q.r, q.b and q.daff (which = 0)
+//           or q.dir (1); val_t = double.
+//   RowsIO  RP rows of a caller's block at once (newton_solve_multi below):
+//           val_t = RowVec<RP>, one double per row, with the element-wise
+//           operators the formulas use.  r_v lives in R and the directions in
+//           D, both in Newton order -- the device slot layout itself, so
+//           element i of slot s is at q.r[s] - q.r[0] + i -- and b in rows of
+//           the workspace W.  What depends on the iterate alone (the ipmz_inv
+//           reciprocals, ds_inv, the bounds) stays a double: it is evaluated
+//           once per element for all RP rows.  D may be R (in place): an
+//           element of a row is read and written by one thread only, so
+//           neither pointer is __restrict__.  cnt <= RP rows are valid; the
+//           others read the last valid row again and store nothing.
+//   RowD    one row of D, for ratio_elem.
+// The library is built with -ffp-contract=off: the same expression rounds the
+// same way in every instantiation.
+struct DSel {
+  typedef double val_t;
+  const QPDev& q;
+  double* const* dd;
+  __device__ __forceinline__ double r(int slot, int i) const { return q.r[slot][i]; }
+  __device__ __forceinline__ double& b(int t) const { return q.b[t]; }
+  __device__ __forceinline__ double x(int t) const { return q.b[t]; }
+  __device__ __forceinline__ double& d(int slot, int i) const { return dd[slot][i]; }
+  __device__ __forceinline__ double zero() const { return 0.0; }
+};
+__device__ __forceinline__ DSel dsel(const QPDev& q, int which) { return DSel{q, which ? q.dir : q.daff}; }
+
+template <int RP>
+struct RowVec {
+  double v[RP];
+};
+#define IPMZ_ROWVEC_OP(OP)                                                                                \
+  template <int RP>                                                                                       \
+  __device__ __forceinline__ RowVec<RP> operator OP(const RowVec<RP>& a, const RowVec<RP>& b) {            \
+    RowVec<RP> c;                                                                                         \
+    _Pragma("unroll") for (int k = 0; k < RP; ++k) c.v[k] = a.v[k] OP b.v[k];                              \
+    return c;                                                                                             \
+  }                                                                                                       \
+  template <int RP>                                                                                       \
+  __device__ __forceinline__ RowVec<RP> operator OP(const RowVec<RP>& a, double b) {                       \
+    RowVec<RP> c;                                                                                         \
+    _Pragma("unroll") for (int k = 0; k < RP; ++k) c.v[k] = a.v[k] OP b;                                   \
+    return c;                                                                                             \
+  }                                                                                                       \
+  template <int RP>                                                                                       \
+  __device__ __forceinline__ RowVec<RP> operator OP(double a, const RowVec<RP>& b) {                       \
+    RowVec<RP> c;                                                                                         \
+    _Pragma("unroll") for (int k = 0; k < RP; ++k) c.v[k] = a OP b.v[k];                                   \
+    return c;                                                                                             \
+  }
+IPMZ_ROWVEC_OP(+)
+IPMZ_ROWVEC_OP(*)
+#undef IPMZ_ROWVEC_OP
+template <int RP>
+__device__ __forceinline__ RowVec<RP> operator-(const RowVec<RP>& a) {
+  RowVec<RP> c;
+#pragma unroll
+  for (int k = 0; k < RP; ++k) c.v[k] = -a.v[k];
+  return c;
+}
+// element e of cnt rows, ld apart: assignment stores the valid rows
+template <int RP>
+struct RowRef {
+  double* p;
+  int64_t ld;
+  int cnt;
+  __device__ __forceinline__ void operator=(const RowVec<RP>& a) const {
+#pragma unroll
+    for (int k = 0; k < RP; ++k)
+      if (k < cnt) p[k * ld] = a.v[k];
+  }
+};
+template <int RP>
+struct RowsIO {
+  typedef RowVec<RP> val_t;
+  const QPDev& q;
+  const double* R;
+  int64_t ldr;
+  double* W;
+  int64_t ldw;
+  double* D;
+  int64_t ldd;
+  int cnt;
+  __device__ __forceinline__ val_t load(const double* p, int64_t ld) const {
+    val_t a;
+#pragma unroll
+    for (int k = 0; k < RP; ++k) a.v[k] = p[(k < cnt ? k : cnt - 1) * ld];
+    return a;
+  }
+  __device__ __forceinline__ val_t r(int slot, int i) const { return load(R + (q.r[slot] - q.r[0]) + i, ldr); }
+  __device__ __forceinline__ RowRef<RP> b(int t) const { return RowRef<RP>{W + t, ldw, cnt}; }
+  __device__ __forceinline__ val_t x(int t) const { return load(W + t, ldw); }
+  __device__ __forceinline__ RowRef<RP> d(int slot, int i) const {
+    return RowRef<RP>{D + (q.r[slot] - q.r[0]) + i, ldd, cnt};
+  }
+  __device__ __forceinline__ val_t zero() const {
+    val_t a;
+#pragma unroll
+    for (int k = 0; k < RP; ++k) a.v[k] = 0.0;
+    return a;
+  }
+};
+struct RowD {
+  const QPDev& q;
+  const double* D;
+  __device__ __forceinline__ double d(int slot, int i) const { return D[(q.r[slot] - q.r[0]) + i]; }
+};
+
 // ---------------------------------------------------------------------------
 // Augmented rhs (formulations.txt, augmented system rhs rows 0..2).
 // element t (< N) of the augmented rhs
-__device__ __forceinline__ void rhs_elem(const QPDev& q, int t) {
+template <class IO>
+__device__ __forceinline__ void rhs_elem(const QPDev& q, const IO& io, int t) {
   const int n = q.n, m = q.m;
   if (t < n) {
     const int i = t;
-    const double rx = q.r[X][i];
+    const auto rx = io.r(X, i);
     if (q.slacks) {  // (((U_x - X)^{-1}*r_lz) - r_x - ((X - L_x)^{-1}*r_ly)), absent terms dropped
-      double b = q.vup ? ipmz_inv(q.ux[i] + (-q.v[X][i])) * q.r[LZ][i] + (-rx) : -rx;
-      if (q.vlo) b = b + (-(ipmz_inv(q.v[X][i] + (-q.lx[i])) * q.r[LY][i]));
-      q.b[i] = b;
+      auto b = q.vup ? ipmz_inv(q.ux[i] + (-q.v[X][i])) * io.r(LZ, i) + (-rx) : -rx;
+      if (q.vlo) b = b + (-(ipmz_inv(q.v[X][i] + (-q.lx[i])) * io.r(LY, i)));
+      io.b(i) = b;
       return;
     }
-    const double tz = q.vup ? ipmz_inv(q.v[Z][i]) * (q.r[Z][i] + (-(q.v[LZ][i] * q.r[LZ][i]))) : 0.0;
-    const double ty = q.vlo ? ipmz_inv(q.v[Y][i]) * (q.r[Y][i] + (-(q.v[LY][i] * q.r[LY][i]))) : 0.0;
-    if (q.vlo && q.vup) q.b[i] = (tz + (-rx)) + (-ty);
-    else if (q.vup) q.b[i] = tz + (-rx);  // ((Z^{-1}*(r_z - (L_z*r_lz))) - r_x)
-    else if (q.vlo) q.b[i] = -(rx + ty);  // -(r_x + (Y^{-1}*(r_y - (L_y*r_ly))))
-    else q.b[i] = -rx;
+    const auto tz = q.vup ? ipmz_inv(q.v[Z][i]) * (io.r(Z, i) + (-(q.v[LZ][i] * io.r(LZ, i)))) : io.zero();
+    const auto ty = q.vlo ? ipmz_inv(q.v[Y][i]) * (io.r(Y, i) + (-(q.v[LY][i] * io.r(LY, i)))) : io.zero();
+    if (q.vlo && q.vup) io.b(i) = (tz + (-rx)) + (-ty);
+    else if (q.vup) io.b(i) = tz + (-rx);  // ((Z^{-1}*(r_z - (L_z*r_lz))) - r_x)
+    else if (q.vlo) io.b(i) = -(rx + ty);  // -(r_x + (Y^{-1}*(r_y - (L_y*r_ly))))
+    else io.b(i) = -rx;
   } else if (t < n + q.mk && q.naive) {
     if (t < n + m) {  // ((L_g^{-1}*r_g) - r_lg)
       const int i = t - n;
-      q.b[t] = ipmz_inv(q.v[LG][i]) * q.r[G][i] + (-q.r[LG][i]);
+      io.b(t) = ipmz_inv(q.v[LG][i]) * io.r(G, i) + (-io.r(LG, i));
     } else {  // ((L_h^{-1}*r_h) - r_lh)
       const int i = t - n - m;
-      q.b[t] = ipmz_inv(q.v[LH][i]) * q.r[H][i] + (-q.r[LH][i]);
+      io.b(t) = ipmz_inv(q.v[LH][i]) * io.r(H, i) + (-io.r(LH, i));
     }
   } else if (t < n + m) {
     const int i = t - n;
-    const double rla = q.r[LA][i], rs = q.r[S][i];
+    const auto rla = io.r(LA, i), rs = io.r(S, i);
     if (q.slacks) {
-      const double a = ipmz_inv(q.uA[i] + (-q.v[S][i])) * q.r[LH][i];
-      const double c = ipmz_inv(q.v[S][i] + (-q.lA[i])) * q.r[LG][i];
-      q.b[t] = ds_inv_sl(q, i) * ((a + (-rs)) + (-c)) + (-rla);
+      const auto a = ipmz_inv(q.uA[i] + (-q.v[S][i])) * io.r(LH, i);
+      const auto c = ipmz_inv(q.v[S][i] + (-q.lA[i])) * io.r(LG, i);
+      io.b(t) = ds_inv_sl(q, i) * ((a + (-rs)) + (-c)) + (-rla);
     } else if (q.alo && q.aup) {
-      const double th = ipmz_inv(q.v[H][i]) * (q.r[H][i] + (-(q.v[LH][i] * q.r[LH][i])));
-      const double tg = ipmz_inv(q.v[G][i]) * (q.r[G][i] + (-(q.v[LG][i] * q.r[LG][i])));
-      q.b[t] = ds_inv(q, i) * ((th + (-rs)) + (-tg)) + (-rla);
+      const auto th = ipmz_inv(q.v[H][i]) * (io.r(H, i) + (-(q.v[LH][i] * io.r(LH, i))));
+      const auto tg = ipmz_inv(q.v[G][i]) * (io.r(G, i) + (-(q.v[LG][i] * io.r(LG, i))));
+      io.b(t) = ds_inv(q, i) * ((th + (-rs)) + (-tg)) + (-rla);
     } else if (q.alo) {  // -(r_lA + (L_g^{-1}*(r_g + (G*r_s))) - r_lg)
-      q.b[t] = -((rla + ipmz_inv(q.v[LG][i]) * (q.r[G][i] + q.v[G][i] * rs)) + (-q.r[LG][i]));
+      io.b(t) = -((rla + ipmz_inv(q.v[LG][i]) * (io.r(G, i) + q.v[G][i] * rs)) + (-io.r(LG, i)));
     } else {  // ((L_h^{-1}*(r_h - (H*r_s))) - r_lA - r_lh)
-      q.b[t] = ((ipmz_inv(q.v[LH][i]) * (q.r[H][i] + (-(q.v[H][i] * rs)))) + (-rla)) + (-q.r[LH][i]);
+      io.b(t) = ((ipmz_inv(q.v[LH][i]) * (io.r(H, i) + (-(q.v[H][i] * rs)))) + (-rla)) + (-io.r(LH, i));
     }
   } else if (t < q.N) {
     const int i = t - n - q.mk;
-    q.b[t] = (q.eqnone || q.eqpen) ? -q.r[LC][i] : q.delta * q.r[P][i] + (-q.r[LC][i]);
+    io.b(t) = (q.eqnone || q.eqpen) ? -io.r(LC, i) : q.delta * io.r(P, i) + (-io.r(LC, i));
   }
 }
+
+__device__ __forceinline__ void rhs_elem(const QPDev& q, int t) { rhs_elem(q, dsel(q, 0), t); }
 
 __global__ void k_rhs(const QPDev* __restrict__ qs) { rhs_elem(qs[blockIdx.y], blockIdx.x * NT + threadIdx.x); }
 
@@ -580,91 +699,90 @@ hipError_t qp_rhs(const QPBatch& qb, hipStream_t st) {
 }
 
 // Back-substitution of the eliminated variables (delta_definitions,
-// Optimizer.cpp:373-378) into the affine (which = 0) or corrector (1) slots.
-struct DSel {
-  double* const* d;
-};
-__device__ __forceinline__ DSel dsel(const QPDev& q, int which) { return DSel{which ? q.dir : q.daff}; }
+// Optimizer.cpp:373-378) into the directions io.d.
 
 // element t (< N): the solution b -> the Newton directions D
-__device__ __forceinline__ void backsub_elem(const QPDev& q, const DSel& D, int t) {
+template <class IO>
+__device__ __forceinline__ void backsub_elem(const QPDev& q, const IO& io, int t) {
   const int n = q.n, m = q.m;
   if (t < n) {
     const int i = t;
-    const double dx = q.b[i];
-    D.d[X][i] = dx;
+    const auto dx = io.x(i);
+    io.d(X, i) = dx;
     if (q.slacks) {
       if (q.vlo)  // -((X - L_x)^{-1}*(r_ly + (L_y*dx)))
-        D.d[LY][i] = -(ipmz_inv(q.v[X][i] + (-q.lx[i])) * (q.r[LY][i] + q.v[LY][i] * dx));
+        io.d(LY, i) = -(ipmz_inv(q.v[X][i] + (-q.lx[i])) * (io.r(LY, i) + q.v[LY][i] * dx));
       if (q.vup)  // ((U_x - X)^{-1}*((L_z*dx) - r_lz))
-        D.d[LZ][i] = ipmz_inv(q.ux[i] + (-q.v[X][i])) * (q.v[LZ][i] * dx + (-q.r[LZ][i]));
+        io.d(LZ, i) = ipmz_inv(q.ux[i] + (-q.v[X][i])) * (q.v[LZ][i] * dx + (-io.r(LZ, i)));
       return;
     }
     if (q.vlo) {
-      D.d[LY][i] = -((ipmz_inv(q.v[Y][i]) * q.v[LY][i]) *
-                     ((dx + ipmz_inv(q.v[LY][i]) * q.r[Y][i]) + (-q.r[LY][i])));
-      D.d[Y][i] = -(ipmz_inv(q.v[LY][i]) * (q.r[Y][i] + q.v[Y][i] * D.d[LY][i]));
+      const auto dly = -((ipmz_inv(q.v[Y][i]) * q.v[LY][i]) *
+                         ((dx + ipmz_inv(q.v[LY][i]) * io.r(Y, i)) + (-io.r(LY, i))));
+      io.d(LY, i) = dly;
+      io.d(Y, i) = -(ipmz_inv(q.v[LY][i]) * (io.r(Y, i) + q.v[Y][i] * dly));
     }
     if (q.vup) {
-      D.d[LZ][i] = -((ipmz_inv(q.v[Z][i]) * q.v[LZ][i]) *
-                     ((ipmz_inv(q.v[LZ][i]) * q.r[Z][i] + (-q.r[LZ][i])) + (-dx)));
-      D.d[Z][i] = -(ipmz_inv(q.v[LZ][i]) * (q.r[Z][i] + q.v[Z][i] * D.d[LZ][i]));
+      const auto dlz = -((ipmz_inv(q.v[Z][i]) * q.v[LZ][i]) *
+                         ((ipmz_inv(q.v[LZ][i]) * io.r(Z, i) + (-io.r(LZ, i))) + (-dx)));
+      io.d(LZ, i) = dlz;
+      io.d(Z, i) = -(ipmz_inv(q.v[LZ][i]) * (io.r(Z, i) + q.v[Z][i] * dlz));
     }
   } else if (t < n + q.mk && q.naive) {
     if (t < n + m) {  // -(L_g^{-1}*(r_g + (G*dl_g)))
       const int i = t - n;
-      const double dlg = q.b[t];
-      D.d[LG][i] = dlg;
-      D.d[G][i] = -(ipmz_inv(q.v[LG][i]) * (q.r[G][i] + q.v[G][i] * dlg));
+      const auto dlg = io.x(t);
+      io.d(LG, i) = dlg;
+      io.d(G, i) = -(ipmz_inv(q.v[LG][i]) * (io.r(G, i) + q.v[G][i] * dlg));
     } else {
       const int i = t - n - m;
-      const double dlh = q.b[t];
-      D.d[LH][i] = dlh;
-      D.d[H][i] = -(ipmz_inv(q.v[LH][i]) * (q.r[H][i] + q.v[H][i] * dlh));
+      const auto dlh = io.x(t);
+      io.d(LH, i) = dlh;
+      io.d(H, i) = -(ipmz_inv(q.v[LH][i]) * (io.r(H, i) + q.v[H][i] * dlh));
     }
   } else if (t < n + m) {
     const int i = t - n;
-    const double dla = q.b[t], rs = q.r[S][i];
-    D.d[LA][i] = dla;
+    const auto dla = io.x(t), rs = io.r(S, i);
+    io.d(LA, i) = dla;
     if (q.slacks) {
-      const double a = ipmz_inv(q.uA[i] + (-q.v[S][i])) * q.r[LH][i];
-      const double c = ipmz_inv(q.v[S][i] + (-q.lA[i])) * q.r[LG][i];
-      const double ds = ds_inv_sl(q, i) * (((dla + a) + (-rs)) + (-c));
-      D.d[S][i] = ds;
-      D.d[LG][i] = -(ipmz_inv(q.v[S][i] + (-q.lA[i])) * (q.r[LG][i] + q.v[LG][i] * ds));
-      D.d[LH][i] = ipmz_inv(q.uA[i] + (-q.v[S][i])) * (q.v[LH][i] * ds + (-q.r[LH][i]));
+      const auto a = ipmz_inv(q.uA[i] + (-q.v[S][i])) * io.r(LH, i);
+      const auto c = ipmz_inv(q.v[S][i] + (-q.lA[i])) * io.r(LG, i);
+      const auto ds = ds_inv_sl(q, i) * (((dla + a) + (-rs)) + (-c));
+      io.d(S, i) = ds;
+      io.d(LG, i) = -(ipmz_inv(q.v[S][i] + (-q.lA[i])) * (io.r(LG, i) + q.v[LG][i] * ds));
+      io.d(LH, i) = ipmz_inv(q.uA[i] + (-q.v[S][i])) * (q.v[LH][i] * ds + (-io.r(LH, i)));
       return;
     }
-    double ds;
+    typename IO::val_t ds;
     if (q.alo && q.aup) {
-      const double th = ipmz_inv(q.v[H][i]) * (q.r[H][i] + (-(q.v[LH][i] * q.r[LH][i])));
-      const double tg = ipmz_inv(q.v[G][i]) * (q.r[G][i] + (-(q.v[LG][i] * q.r[LG][i])));
+      const auto th = ipmz_inv(q.v[H][i]) * (io.r(H, i) + (-(q.v[LH][i] * io.r(LH, i))));
+      const auto tg = ipmz_inv(q.v[G][i]) * (io.r(G, i) + (-(q.v[LG][i] * io.r(LG, i))));
       ds = ds_inv(q, i) * (((dla + th) + (-rs)) + (-tg));
     } else if (q.alo) {  // (L_g^{-1}*G*(dla - r_s - (G^{-1}*(r_g - (L_g*r_lg)))))
       ds = (ipmz_inv(q.v[LG][i]) * q.v[G][i]) *
-           ((dla + (-rs)) + (-(ipmz_inv(q.v[G][i]) * (q.r[G][i] + (-(q.v[LG][i] * q.r[LG][i]))))));
+           ((dla + (-rs)) + (-(ipmz_inv(q.v[G][i]) * (io.r(G, i) + (-(q.v[LG][i] * io.r(LG, i)))))));
     } else {  // (L_h^{-1}*H*(dla + (H^{-1}*(r_h - (L_h*r_lh))) - r_s))
       ds = (ipmz_inv(q.v[LH][i]) * q.v[H][i]) *
-           ((dla + ipmz_inv(q.v[H][i]) * (q.r[H][i] + (-(q.v[LH][i] * q.r[LH][i])))) + (-rs));
+           ((dla + ipmz_inv(q.v[H][i]) * (io.r(H, i) + (-(q.v[LH][i] * io.r(LH, i))))) + (-rs));
     }
-    D.d[S][i] = ds;
+    io.d(S, i) = ds;
     if (q.alo) {
-      const double dlg =
-          -((ipmz_inv(q.v[G][i]) * q.v[LG][i]) * ((ds + ipmz_inv(q.v[LG][i]) * q.r[G][i]) + (-q.r[LG][i])));
-      D.d[LG][i] = dlg;
-      D.d[G][i] = -(ipmz_inv(q.v[LG][i]) * (q.r[G][i] + q.v[G][i] * dlg));
+      const auto dlg =
+          -((ipmz_inv(q.v[G][i]) * q.v[LG][i]) * ((ds + ipmz_inv(q.v[LG][i]) * io.r(G, i)) + (-io.r(LG, i))));
+      io.d(LG, i) = dlg;
+      io.d(G, i) = -(ipmz_inv(q.v[LG][i]) * (io.r(G, i) + q.v[G][i] * dlg));
     }
     if (q.aup) {
-      const double dlh =
-          -((ipmz_inv(q.v[H][i]) * q.v[LH][i]) * ((ipmz_inv(q.v[LH][i]) * q.r[H][i] + (-q.r[LH][i])) + (-ds)));
-      D.d[LH][i] = dlh;
-      D.d[H][i] = -(ipmz_inv(q.v[LH][i]) * (q.r[H][i] + q.v[H][i] * dlh));
+      const auto dlh =
+          -((ipmz_inv(q.v[H][i]) * q.v[LH][i]) * ((ipmz_inv(q.v[LH][i]) * io.r(H, i) + (-io.r(LH, i))) + (-ds)));
+      io.d(LH, i) = dlh;
+      io.d(H, i) = -(ipmz_inv(q.v[LH][i]) * (io.r(H, i) + q.v[H][i] * dlh));
     }
   } else if (t < q.N) {
     const int i = t - n - q.mk;
-    const double dlc = q.b[t];
-    D.d[LC][i] = dlc;
-    if (!q.eqnone && !q.eqpen) D.d[P][i] = -(q.r[P][i] + q.delta * dlc);
+    const auto dlc = io.x(t);
+    io.d(LC, i) = dlc;
+    if (!q.eqnone && !q.eqpen) io.d(P, i) = -(io.r(P, i) + q.delta * dlc);
   }
 }
 
@@ -684,11 +802,12 @@ hipError_t qp_backsub(const QPBatch& qb, int which, hipStream_t st) {
 // variable (box-only SlackedSlacks, or Slacks) -- explicit bounds on x
 // (l_x, u_x) and s (l_A, u_A), both always (the environment holds both).
 // Element t (< n + m), folded into a.
-__device__ __forceinline__ void ratio_elem(const QPDev& q, const DSel& D, int t, double& a) {
+template <class IO>
+__device__ __forceinline__ void ratio_elem(const QPDev& q, const IO& io, int t, double& a) {
   const int n = q.n, m = q.m;
   const bool explicit_bounds = q.slacks || m == 0;
   auto nonneg = [&](int slot, int i) {
-    const double d = D.d[slot][i];
+    const double d = io.d(slot, i);
     if (d < 0.0) a = fmin(a, -q.v[slot][i] / d);
   };
   auto bounded = [&](double v, double d, double lo, double up) {
@@ -703,7 +822,7 @@ __device__ __forceinline__ void ratio_elem(const QPDev& q, const DSel& D, int t,
       if (q.vlo) nonneg(Y, i);
       if (q.vup) nonneg(Z, i);
     }
-    if (explicit_bounds) bounded(q.v[X][i], D.d[X][i], q.lx[i], q.ux[i]);
+    if (explicit_bounds) bounded(q.v[X][i], io.d(X, i), q.lx[i], q.ux[i]);
   } else {
     const int i = t - n;
     if (q.alo) nonneg(LG, i);
@@ -712,7 +831,7 @@ __device__ __forceinline__ void ratio_elem(const QPDev& q, const DSel& D, int t,
       if (q.alo) nonneg(G, i);
       if (q.aup) nonneg(H, i);
     }
-    if (explicit_bounds) bounded(q.v[S][i], D.d[S][i], q.lA[i], q.uA[i]);
+    if (explicit_bounds) bounded(q.v[S][i], io.d(S, i), q.lA[i], q.uA[i]);
   }
 }
 
@@ -738,6 +857,110 @@ hipError_t qp_ratio(const QPBatch& qb, int which, int out_index, hipStream_t st)
   const int nb = red_blocks(qb.h.n + qb.h.m);
   hipLaunchKernelGGL(k_ratio_part, grid2(nb, qb.B), dim3(NT), 0, st, qb.d, which);
   hipLaunchKernelGGL(k_min_final, grid2(1, qb.B), dim3(NT), 0, st, qb.d, nb, out_index);
+  return hipGetLastError();
+}
+
+// ---------------------------------------------------------------------------
+// compute_search_direction_ (Optimizer.cpp:344-380) for a block of residual
+// vectors (ipmz_*_newton_solve_multi): row r of QP z of R holds r_v in Newton
+// order; k_rhs_multi writes its augmented rhs to row r of the workspace W, the
+// blocked solves overwrite W with K^{-1} W, k_backsub_multi writes the full
+// direction to row r of D and k_ratio_multi get_max_step_ of (iterate, row).
+// Grid (N / NT, row groups, QP): a thread owns KKT element t of one QP and
+// the RP rows of its group at once (RowsIO) -- a row's loads are coalesced
+// across t, and what depends on the iterate alone is evaluated once for the
+// group.  Stream order only, no atomics; a row's result depends on no other
+// row (the rows of a group share only those iterate factors).
+template <int RP>
+__global__ __launch_bounds__(NT) void k_rhs_multi(const QPDev* __restrict__ qs, const double* __restrict__ R,
+                                                  int64_t ldr, int64_t sR, double* __restrict__ W, int64_t ldw,
+                                                  int64_t sW, int row0, int nrhs) {
+  const QPDev& q = qs[blockIdx.z];
+  const int t = blockIdx.x * NT + threadIdx.x;
+  const int r0 = row0 + blockIdx.y * RP;
+  if (t >= q.N || r0 >= nrhs) return;
+  R += blockIdx.z * sR + (int64_t)r0 * ldr;
+  W += blockIdx.z * sW + (int64_t)r0 * ldw;
+  rhs_elem(q, RowsIO<RP>{q, R, ldr, W, ldw, nullptr, 0, nrhs - r0 < RP ? nrhs - r0 : RP}, t);
+}
+// (R and D without __restrict__: D may be R)
+template <int RP>
+__global__ __launch_bounds__(NT) void k_backsub_multi(const QPDev* __restrict__ qs, const double* R, int64_t ldr,
+                                                      int64_t sR, const double* __restrict__ W, int64_t ldw,
+                                                      int64_t sW, double* D, int64_t ldd, int64_t sD, int row0,
+                                                      int nrhs) {
+  const QPDev& q = qs[blockIdx.z];
+  const int t = blockIdx.x * NT + threadIdx.x;
+  const int r0 = row0 + blockIdx.y * RP;
+  if (t >= q.N || r0 >= nrhs) return;
+  R += blockIdx.z * sR + (int64_t)r0 * ldr;
+  W += blockIdx.z * sW + (int64_t)r0 * ldw;
+  D += blockIdx.z * sD + (int64_t)r0 * ldd;
+  backsub_elem(q, RowsIO<RP>{q, R, ldr, const_cast<double*>(W), ldw, D, ldd, nrhs - r0 < RP ? nrhs - r0 : RP}, t);
+}
+// one workgroup of NTH threads per (row, QP): ratio_elem over t < n + m in a
+// fixed order (and fmin over finite values does not depend on it)
+template <int NTH>
+__global__ __launch_bounds__(NTH) void k_ratio_multi(const QPDev* __restrict__ qs, const double* __restrict__ D,
+                                                     int64_t ldd, int64_t sD, double* __restrict__ alpha, int row0,
+                                                     int nrhs) {
+  const QPDev& q = qs[blockIdx.y];
+  const int r = row0 + blockIdx.x;
+  const RowD io{q, D + blockIdx.y * sD + (int64_t)r * ldd};
+  __shared__ double sh[NTH / 64];
+  double a = 1.0;
+  for (int t = threadIdx.x; t < q.n + q.m; t += NTH) ratio_elem(q, io, t, a);
+  a = block_allmin<NTH>(a, sh);
+  if (threadIdx.x == 0) alpha[(int64_t)blockIdx.y * nrhs + r] = a;
+}
+
+// rows per group of the two element-wise kernels (tools/newton_multi_bench.py,
+// DESIGN.md "Newton directions for a block of residuals"); the debug bits
+// select 1, 2 or 8 for the A/B
+static int newton_multi_rpg() {
+  const int dbg = debug_inject_mask();
+  const bool r1 = dbg & IPMZ_DEBUG_NEWTON_RPG1, r8 = dbg & IPMZ_DEBUG_NEWTON_RPG8;
+  return r1 && r8 ? 2 : r1 ? 1 : r8 ? 8 : IPMZ_NEWTON_MULTI_RPG;
+}
+// f(rows per group as a constant, first row, grid): grid y <= 65535, further launches for more groups
+template <typename F>
+static void newton_multi_launches(const QPBatch& qb, int nrhs, F&& f) {
+  const int rpg = newton_multi_rpg();
+  const int64_t groups = ((int64_t)nrhs + rpg - 1) / rpg;
+  for (int64_t g0 = 0; g0 < groups; g0 += 65535) {
+    const dim3 grid((qb.h.N + NT - 1) / NT, (unsigned)(groups - g0 < 65535 ? groups - g0 : 65535), qb.B);
+    const int row0 = (int)(g0 * rpg);
+    if (rpg == 1) f(std::integral_constant<int, 1>{}, row0, grid);
+    else if (rpg == 2) f(std::integral_constant<int, 2>{}, row0, grid);
+    else if (rpg == 8) f(std::integral_constant<int, 8>{}, row0, grid);
+    else f(std::integral_constant<int, IPMZ_NEWTON_MULTI_RPG>{}, row0, grid);
+  }
+}
+
+hipError_t qp_rhs_multi(const QPBatch& qb, const double* R, int64_t ldr, int64_t sR, double* W, int64_t ldw, int64_t sW,
+                        int nrhs, hipStream_t st) {
+  newton_multi_launches(qb, nrhs, [&](auto rp, int row0, dim3 grid) {
+    hipLaunchKernelGGL((k_rhs_multi<decltype(rp)::value>), grid, dim3(NT), 0, st, qb.d, R, ldr, sR, W, ldw, sW, row0,
+                       nrhs);
+  });
+  return hipGetLastError();
+}
+hipError_t qp_backsub_multi(const QPBatch& qb, const double* R, int64_t ldr, int64_t sR, const double* W, int64_t ldw,
+                            int64_t sW, double* D, int64_t ldd, int64_t sD, int nrhs, hipStream_t st) {
+  newton_multi_launches(qb, nrhs, [&](auto rp, int row0, dim3 grid) {
+    hipLaunchKernelGGL((k_backsub_multi<decltype(rp)::value>), grid, dim3(NT), 0, st, qb.d, R, ldr, sR, W, ldw, sW, D,
+                       ldd, sD, row0, nrhs);
+  });
+  return hipGetLastError();
+}
+hipError_t qp_ratio_multi(const QPBatch& qb, const double* D, int64_t ldd, int64_t sD, double* alpha, int nrhs,
+                          hipStream_t st) {
+  if (nrhs <= 0) return hipSuccess;
+  // 1024 threads where a row keeps them busy (a single large QP: one workgroup walks n + m elements)
+  if (qb.h.n + qb.h.m > 2048)
+    hipLaunchKernelGGL(k_ratio_multi<1024>, dim3(nrhs, qb.B), dim3(1024), 0, st, qb.d, D, ldd, sD, alpha, 0, nrhs);
+  else
+    hipLaunchKernelGGL(k_ratio_multi<NT>, dim3(nrhs, qb.B), dim3(NT), 0, st, qb.d, D, ldd, sD, alpha, 0, nrhs);
   return hipGetLastError();
 }
 

@@ -42,6 +42,9 @@ struct ipmz_qp {
   // ipmz_qp_kkt_solve_mixed: the multi-right-hand-side workspace, for the largest nrhs seen
   char* mmws = nullptr;
   int mmws_nrhs = 0;
+  // ipmz_*_newton_solve_multi: the reduced right-hand sides, B x nrhs x round_up(N, 2) doubles, for the largest nrhs seen
+  double* nmws = nullptr;
+  int nmws_nrhs = 0;
   // normal-equations reduction (C2)
   bool normal = false;
   // EqualityHandling::None: Bunch-Kaufman factor (pivots per QP)
@@ -794,6 +797,7 @@ int ipmz_qp_destroy(ipmz_qp* s) {
   }
   for (void* p : s->allocs) hipFree(p);
   if (s->mmws) hipFree(s->mmws);
+  if (s->nmws) hipFree(s->nmws);
   if (s->mw.hev) hipEventDestroy(s->mw.hev);
   if (s->mw.hst) hipHostFree(s->mw.hst);
   ipmz_ctx* ctx = s->ctx;
@@ -978,6 +982,94 @@ static int batch_multi_impl(ipmz_qp* s, double* B, int64_t ldb, int64_t sB, int 
   return IPMZ_OK;
 }
 
+// What the four *_kkt_solve* calls and the two *_newton_solve_multi calls
+// share, by the solver's kind (single or batch, LDL^T or Bunch-Kaufman):
+// kkt_ws_ensure  the Bunch-Kaufman prepared solves' workspace, on first use;
+// kkt_enqueue    the step's own assembly and factor on the storage the next
+//                step overwrites anyway (it assembles and factors again: the
+//                iterate is only read), then the nrhs rows of B <- K^{-1} row;
+//                asynchronous;
+// kkt_finish     the one synchronize: the sticky error words, then the info
+//                word(s).  info (host, batch ints, may be null) is filled per
+//                QP for Bunch-Kaufman batches only.
+static int kkt_ws_ensure(ipmz_qp* s) {
+  if (!s->eqnone) return IPMZ_OK;
+  // single QPs below IPMZ_BK_GRID_MIN: the steps solve on F itself; batches:
+  // no step uses prepared solves.  Allocated on first use and kept
+  char** slot = s->B == 1 ? &s->bkmws : &s->bkbws;
+  if (*slot || (s->B == 1 && s->bkfws)) return IPMZ_OK;
+  const size_t bytes = s->B == 1 ? (size_t)bk_solve_ws(nullptr, s->N).total : (size_t)bk_batch_ws(nullptr, s->N, s->B).total;
+  void* w = nullptr;
+  if (hipMalloc(&w, bytes) != hipSuccess) {
+    (void)hipGetLastError();
+    return fail(IPMZ_ERR_NOMEM, "device allocation failed");
+  }
+  s->allocs.push_back(w);
+  *slot = static_cast<char*>(w);
+  return IPMZ_OK;
+}
+
+// the persistent solve's sticky error word of a single QP's Bunch-Kaufman path
+static const unsigned* bk_single_se(const ipmz_qp* s) {
+  return (s->bkfws ? bk_ws(s->bkfws, s->N) : bk_solve_ws(s->bkmws, s->N).k).ctrl + SOLVE_ERR_WORD;
+}
+
+static int kkt_enqueue(ipmz_qp* s, double* B, int64_t ldb, int64_t sB, int nrhs) {
+  hipStream_t st = s->ctx->stream;
+  int rc;
+  if (s->B == 1 && !s->eqnone) {
+    HIP_OK(qp_assemble(s->qb, st));
+    rc = factor_impl(s->ctx, s->N, s->K, s->ldk, s->D, ldlt_ws_of(s), nbo_for(s->ctx, s->N), nullptr);
+    if (!rc) rc = ipmz_ldlt_solve_multi(s->ctx, s->N, s->K, s->ldk, s->D, s->ws, B, ldb, nrhs);
+    unwatch(s->ctx);  // s->ws is the solver's: checked in kkt_finish, not at a later sync
+    return rc;
+  }
+  if (s->B == 1) {
+    HIP_OK(qp_assemble(s->qb, st));
+    if ((rc = factor_batch(s, nullptr, false))) return rc;
+    if (s->bkfws) {  // factor_batch left LT in bklt, L' in K and the operators in bkfws
+      rc = bk_multi_impl(s->ctx, s->N, s->K, s->ldk, s->ipiv, s->bklt, s->K, s->ldk, bk_ws(s->bkfws, s->N), B, ldb, nrhs);
+    } else {
+      const BkSolveWs w = bk_solve_ws(s->bkmws, s->N);
+      HIP_OK(bk_transpose(s->K, s->ldk, s->N, w.LT, st));
+      HIP_OK(bk_setup(s->K, s->ldk, s->N, s->ipiv, s->binfo, w.LT, w.Lp, w.ldp, w.k, st));
+      rc = bk_multi_impl(s->ctx, s->N, s->K, s->ldk, s->ipiv, w.LT, w.Lp, w.ldp, w.k, B, ldb, nrhs);
+    }
+    unwatch(s->ctx);  // the workspace is the solver's: checked in kkt_finish, not at a later sync
+    return rc;
+  }
+  // batches (no forked step to wait for: step_forks is false for them).  The
+  // whole matrix of every QP goes into K and is factored there in place
+  // (factor_batch without K0), as the non-fused step does.  The fused step's
+  // kept matrix K0 -- its off-diagonal part written once per load -- is
+  // neither read nor written; that step rewrites K0's diagonal and all of L in
+  // K itself.
+  HIP_OK(qp_assemble(s->qb, st));
+  if ((rc = factor_batch(s, nullptr, false))) return rc;
+  if (!s->eqnone) return batch_multi_impl(s, B, ldb, sB, nrhs);
+  if (nrhs > 0) {
+    const BkBatchWs w = bk_batch_ws(s->bkbws, s->N, s->B);
+    if ((rc = bk_batch_prepare(s->ctx, s->N, s->B, s->K, s->ldk, s->sK, s->ipiv, s->sP, s->binfo, w))) return rc;
+    if ((rc = bk_batch_multi_impl(s->ctx, s->N, s->B, s->K, s->ldk, s->sK, s->ipiv, s->sP, w, B, ldb, sB, nrhs)))
+      return rc;
+  }
+  return IPMZ_OK;
+}
+
+static int kkt_finish(ipmz_qp* s, const char* what, int* info) {
+  hipStream_t st = s->ctx->stream;
+  if (s->B == 1 && !s->eqnone) return read_info(s->ctx, ldlt_ws_of(s));  // checks the error words of s->ws itself
+  if (s->B == 1)
+    return ws_result(st, s->binfo, s->bkws ? bk_grid_err_word(s->bkws, s->N) : nullptr, bk_single_se(s), what,
+                     ": a grid barrier of the whole-device Bunch-Kaufman factor timed out; the factor is invalid");
+  if (s->eqnone) return bk_batch_info(st, s->binfo, s->B, info);
+  // the info word, and the sticky error word of the two-workgroup factor where
+  // it ran (qp_status's rule)
+  const bool pair = s->ctx->nbi == 64 && small_pair_used(s->small_kernel, s->pflags != nullptr, s->B, s->N);
+  return ws_result(st, s->binfo, pair ? s->pflags + (size_t)s->B * IPMZ_PAIR_FLAGS : nullptr, nullptr, what,
+                   ": a hand-off of the two-workgroup batched factor timed out; the factor is invalid");
+}
+
 int ipmz_batch_kkt_solve(ipmz_qp* s, int nrhs, double* B, int64_t ldb, int64_t sB) {
   if (!s) return fail(IPMZ_ERR_INVALID, "null qp");
   if (s->B == 1) return ipmz_qp_kkt_solve(s, nrhs, B, ldb);
@@ -994,23 +1086,8 @@ int ipmz_batch_kkt_solve(ipmz_qp* s, int nrhs, double* B, int64_t ldb, int64_t s
   HIP_OK(hipSetDevice(s->ctx->device));
   int rc = not_capturing(s->ctx, "ipmz_batch_kkt_solve");
   if (rc) return rc;
-  hipStream_t st = s->ctx->stream;
-  // (no forked step to wait for: step_forks is false for batches)
-  // The step's own assembly and factor, on the storage the next step
-  // overwrites anyway: the whole matrix of every QP goes into K and is
-  // factored there in place (factor_batch without K0), as the non-fused step
-  // does.  The fused step's kept matrix K0 -- its off-diagonal part written
-  // once per load -- is neither read nor written; that step rewrites K0's
-  // diagonal and all of L in K itself.  The iterate is only read.
-  HIP_OK(qp_assemble(s->qb, st));
-  if ((rc = factor_batch(s, nullptr, false))) return rc;
-  if ((rc = batch_multi_impl(s, B, ldb, sB, nrhs))) return rc;
-  // the info word, and the sticky error word of the two-workgroup factor where
-  // it ran (qp_status's rule); synchronizes
-  const bool pair = s->ctx->nbi == 64 && small_pair_used(s->small_kernel, s->pflags != nullptr, s->B, s->N);
-  return ws_result(st, s->binfo, pair ? s->pflags + (size_t)s->B * IPMZ_PAIR_FLAGS : nullptr, nullptr,
-                   "ipmz_batch_kkt_solve",
-                   ": a hand-off of the two-workgroup batched factor timed out; the factor is invalid");
+  if ((rc = kkt_enqueue(s, B, ldb, sB, nrhs))) return rc;
+  return kkt_finish(s, "ipmz_batch_kkt_solve", nullptr);  // synchronizes
 }
 
 int ipmz_batch_kkt_solve_bk(ipmz_qp* s, int nrhs, double* B, int64_t ldb, int64_t sB, int* info) {
@@ -1034,29 +1111,9 @@ int ipmz_batch_kkt_solve_bk(ipmz_qp* s, int nrhs, double* B, int64_t ldb, int64_
   HIP_OK(hipSetDevice(s->ctx->device));
   int rc = not_capturing(s->ctx, "ipmz_batch_kkt_solve_bk");
   if (rc) return rc;
-  hipStream_t st = s->ctx->stream;
-  // the prepared solves' workspace is this call's own, allocated on first use and kept
-  if (!s->bkbws) {
-    void* w = nullptr;
-    if (hipMalloc(&w, (size_t)bk_batch_ws(nullptr, s->N, s->B).total) != hipSuccess) {
-      (void)hipGetLastError();
-      return fail(IPMZ_ERR_NOMEM, "device allocation failed");
-    }
-    s->allocs.push_back(w);
-    s->bkbws = static_cast<char*>(w);
-  }
-  // the step's own assembly and batched factor, on the storage the next step
-  // overwrites anyway (it assembles and factors again): the iterate is only
-  // read.  (No forked step to wait for: step_forks is false for batches.)
-  HIP_OK(qp_assemble(s->qb, st));
-  if ((rc = factor_batch(s, nullptr, false))) return rc;
-  if (nrhs > 0) {
-    const BkBatchWs w = bk_batch_ws(s->bkbws, s->N, s->B);
-    if ((rc = bk_batch_prepare(s->ctx, s->N, s->B, s->K, s->ldk, s->sK, s->ipiv, s->sP, s->binfo, w))) return rc;
-    if ((rc = bk_batch_multi_impl(s->ctx, s->N, s->B, s->K, s->ldk, s->sK, s->ipiv, s->sP, w, B, ldb, sB, nrhs)))
-      return rc;
-  }
-  return bk_batch_info(st, s->binfo, s->B, info);  // synchronizes
+  if ((rc = kkt_ws_ensure(s))) return rc;
+  if ((rc = kkt_enqueue(s, B, ldb, sB, nrhs))) return rc;
+  return kkt_finish(s, "ipmz_batch_kkt_solve_bk", info);  // synchronizes
 }
 
 int ipmz_qp_kkt_solve(ipmz_qp* s, int nrhs, double* B, int64_t ldb) {
@@ -1074,15 +1131,9 @@ int ipmz_qp_kkt_solve(ipmz_qp* s, int nrhs, double* B, int64_t ldb) {
   if (nrhs < 0 || ldb < s->N || (ldb & 1) || (nrhs > 0 && !B))
     return fail(IPMZ_ERR_INVALID, "ipmz_qp_kkt_solve: bad arguments (nrhs >= 0, ldb >= N and even)");
   HIP_OK(hipSetDevice(s->ctx->device));
-  // the step's own assembly and factor, on the storage the next step
-  // overwrites anyway (it assembles and factors again): the iterate is only read
-  HIP_OK(qp_assemble(s->qb, s->ctx->stream));
-  const LdltWs w = ldlt_ws_of(s);
-  int rc = factor_impl(s->ctx, s->N, s->K, s->ldk, s->D, w, nbo_for(s->ctx, s->N), nullptr);
-  if (!rc) rc = ipmz_ldlt_solve_multi(s->ctx, s->N, s->K, s->ldk, s->D, s->ws, B, ldb, nrhs);
-  unwatch(s->ctx);  // s->ws is the solver's: checked here, not at a later sync
+  const int rc = kkt_enqueue(s, B, ldb, 0, nrhs);
   if (rc) return rc;
-  return read_info(s->ctx, w);  // synchronizes; checks the error words of s->ws itself
+  return kkt_finish(s, "ipmz_qp_kkt_solve", nullptr);  // synchronizes
 }
 
 int ipmz_qp_kkt_solve_bk(ipmz_qp* s, int nrhs, double* B, int64_t ldb) {
@@ -1098,41 +1149,95 @@ int ipmz_qp_kkt_solve_bk(ipmz_qp* s, int nrhs, double* B, int64_t ldb) {
     return fail(IPMZ_ERR_INVALID, "ipmz_qp_kkt_solve_bk: bad arguments (nrhs >= 0, ldb >= N and even)");
   if (nrhs > 0 && ((uintptr_t)B & 15)) return fail(IPMZ_ERR_INVALID, "ipmz_qp_kkt_solve_bk: B must be 16-byte aligned");
   HIP_OK(hipSetDevice(s->ctx->device));
-  hipStream_t st = s->ctx->stream;
   if (s->step_pending) {  // a forked step still in flight reads the storage factored below
     HIP_OK(hipEventSynchronize(s->step_done));
     s->step_pending = false;
   }
-  // below IPMZ_BK_GRID_MIN the steps solve on F itself: the prepared solve's
-  // workspace is this call's own, allocated on first use and kept
-  if (!s->bkfws && !s->bkmws) {
-    void* w = nullptr;
-    if (hipMalloc(&w, (size_t)bk_solve_ws(nullptr, s->N).total) != hipSuccess)
+  int rc = kkt_ws_ensure(s);
+  if (rc) return rc;
+  if ((rc = kkt_enqueue(s, B, ldb, 0, nrhs))) return rc;
+  return kkt_finish(s, "ipmz_qp_kkt_solve_bk", nullptr);  // synchronizes
+}
+
+// compute_search_direction_ for a block of residual vectors: rhs_elem's
+// reduction of every row into the solver's workspace, the formulation's own
+// factor and blocked solve there (kkt_enqueue), backsub_elem's
+// back-substitution into Dir and ratio_elem's step length per row.
+static int newton_multi(ipmz_qp* s, const char* who, int nrhs, const double* R, int64_t ldr, int64_t sR, double* Dir,
+                        int64_t ldd, int64_t sD, double* alpha, int* info) {
+  const std::string w(who);
+  if (s->normal) return fail(IPMZ_ERR_INVALID, w + ": the normal-equations reduction is enabled (augmented system only)");
+  if (s->mixed) return fail(IPMZ_ERR_INVALID, w + ": mixed precision is enabled (fp64 factors only)");
+  if (s->eqss)
+    return fail(IPMZ_ERR_INVALID, w + ": EqualityHandling::SlackedSlacks / NaiveSlacks keep a permuted, merged view of "
+                                      "the Newton order on the device; not served");
+  if (!s->loaded) return fail(IPMZ_ERR_STATE, w + ": load (and initialize) the QP first");
+  const int64_t L = s->state_len;
+  if (nrhs < 0 || ldr < L || ldd < L || (ldr & 1) || (ldd & 1) || (nrhs > 0 && (!R || !Dir)))
+    return fail(IPMZ_ERR_INVALID, w + ": bad arguments (nrhs >= 0, ldr >= state_len, ldd >= state_len, both even)");
+  if (s->B > 1 && (sR < (int64_t)nrhs * ldr || sD < (int64_t)nrhs * ldd || (sR & 1) || (sD & 1)))
+    return fail(IPMZ_ERR_INVALID, w + ": bad arguments (sR >= nrhs * ldr, sD >= nrhs * ldd, both even)");
+  if (nrhs > 0 && (((uintptr_t)R & 15) || ((uintptr_t)Dir & 15)))
+    return fail(IPMZ_ERR_INVALID, w + ": R and Dir must be 16-byte aligned");
+  if (s->eqnone && s->B > 1 && (s->N > IPMZ_BK_NMAX || s->B > 65535))
+    return fail(IPMZ_ERR_INVALID, w + ": EqualityHandling::None batches: N <= 4096 and batch <= 65535");
+  HIP_OK(hipSetDevice(s->ctx->device));
+  int rc = not_capturing(s->ctx, who);
+  if (rc) return rc;
+  if (s->step_pending) {  // a forked step still in flight reads the storage factored below
+    HIP_OK(hipEventSynchronize(s->step_done));
+    s->step_pending = false;
+  }
+  if ((rc = kkt_ws_ensure(s))) return rc;
+  // the reduced right-hand sides: not Dir itself (the solves see rows of this
+  // stride whatever ldd is, and nothing relies on the head of a Newton-order
+  // row being the KKT order).  Every call ends synchronized, so growing it
+  // here is safe
+  const int64_t ldw = round_up(s->N, 2), sW = (int64_t)nrhs * ldw;
+  if (nrhs > s->nmws_nrhs) {
+    if (s->nmws) hipFree(s->nmws);
+    s->nmws = nullptr;
+    s->nmws_nrhs = 0;
+    void* p = nullptr;
+    if (hipMalloc(&p, (size_t)(sW * s->B) * sizeof(double)) != hipSuccess) {
+      (void)hipGetLastError();
       return fail(IPMZ_ERR_NOMEM, "device allocation failed");
-    s->allocs.push_back(w);
-    s->bkmws = static_cast<char*>(w);
+    }
+    s->nmws = static_cast<double*>(p);
+    s->nmws_nrhs = nrhs;
   }
-  // the step's own assembly and factor, on the storage the next step
-  // overwrites anyway (it assembles and factors again): the iterate is only read
-  HIP_OK(qp_assemble(s->qb, st));
-  int rc = factor_batch(s, nullptr, false);
-  if (rc) return rc;
-  const unsigned* se = nullptr;
-  if (s->bkfws) {  // factor_batch left LT in bklt, L' in K and the operators in bkfws
-    const BkWs w = bk_ws(s->bkfws, s->N);
-    rc = bk_multi_impl(s->ctx, s->N, s->K, s->ldk, s->ipiv, s->bklt, s->K, s->ldk, w, B, ldb, nrhs);
-    se = w.ctrl + SOLVE_ERR_WORD;
-  } else {
-    const BkSolveWs w = bk_solve_ws(s->bkmws, s->N);
-    HIP_OK(bk_transpose(s->K, s->ldk, s->N, w.LT, st));
-    HIP_OK(bk_setup(s->K, s->ldk, s->N, s->ipiv, s->binfo, w.LT, w.Lp, w.ldp, w.k, st));
-    rc = bk_multi_impl(s->ctx, s->N, s->K, s->ldk, s->ipiv, w.LT, w.Lp, w.ldp, w.k, B, ldb, nrhs);
-    se = w.k.ctrl + SOLVE_ERR_WORD;
+  hipStream_t st = s->ctx->stream;
+  double* W = s->nmws;
+  if (nrhs > 0) HIP_OK(qp_rhs_multi(s->qb, R, ldr, sR, W, ldw, sW, nrhs, st));
+  if ((rc = kkt_enqueue(s, W, ldw, sW, nrhs))) return rc;
+  if (nrhs > 0) {
+    HIP_OK(qp_backsub_multi(s->qb, R, ldr, sR, W, ldw, sW, Dir, ldd, sD, nrhs, st));
+    if (alpha) HIP_OK(qp_ratio_multi(s->qb, Dir, ldd, sD, alpha, nrhs, st));
   }
-  unwatch(s->ctx);  // the workspace is the solver's: checked here, not at a later sync
-  if (rc) return rc;
-  return ws_result(st, s->binfo, s->bkws ? bk_grid_err_word(s->bkws, s->N) : nullptr, se, "ipmz_qp_kkt_solve_bk",
-                   ": a grid barrier of the whole-device Bunch-Kaufman factor timed out; the factor is invalid");
+  rc = kkt_finish(s, who, info);  // synchronizes
+  if (info && !(s->eqnone && s->B > 1))
+    for (int q = 0; q < s->B; ++q) info[q] = rc;
+  return rc;
+}
+
+int ipmz_qp_newton_solve_multi(ipmz_qp* s, int nrhs, const double* R, int64_t ldr, double* Dir, int64_t ldd,
+                               double* alpha) {
+  if (!s) return fail(IPMZ_ERR_INVALID, "null qp");
+  if (s->B != 1)
+    return fail(IPMZ_ERR_INVALID, "ipmz_qp_newton_solve_multi: single QPs only, this is a batch "
+                                  "(ipmz_batch_newton_solve_multi)");
+  return newton_multi(s, "ipmz_qp_newton_solve_multi", nrhs, R, ldr, 0, Dir, ldd, 0, alpha, nullptr);
+}
+
+int ipmz_batch_newton_solve_multi(ipmz_qp* s, int nrhs, const double* R, int64_t ldr, int64_t sR, double* Dir,
+                                  int64_t ldd, int64_t sD, double* alpha, int* info) {
+  if (!s) return fail(IPMZ_ERR_INVALID, "null qp");
+  if (s->B == 1) {
+    const int rc = ipmz_qp_newton_solve_multi(s, nrhs, R, ldr, Dir, ldd, alpha);
+    if (info) info[0] = rc;
+    return rc;
+  }
+  return newton_multi(s, "ipmz_batch_newton_solve_multi", nrhs, R, ldr, sR, Dir, ldd, sD, alpha, info);
 }
 
 // the QP's mixed-precision workspace, allocated once (a captured step keeps its addresses)

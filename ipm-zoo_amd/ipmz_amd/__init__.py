@@ -53,6 +53,7 @@ EXPORTS = [
     "ipmz_batch_get_kkt", "ipmz_batch_kkt_solve",
     "ipmz_bk_factor_batch", "ipmz_bk_batch_solve_workspace_bytes", "ipmz_bk_prepare_solve_batch",
     "ipmz_bk_solve_multi_batch", "ipmz_batch_kkt_solve_bk",
+    "ipmz_qp_newton_solve_multi", "ipmz_batch_newton_solve_multi",
 ]
 SOLVE_MULTI_PANEL = 256  # include/ipmz.h IPMZ_SOLVE_MULTI_PANEL: column panel of the blocked multi-rhs solve
 REDUCTION_AUGMENTED, REDUCTION_NORMAL = 0, 1
@@ -178,6 +179,8 @@ def _load():
         "ipmz_bk_prepare_solve_batch": ([_VP, _I, _I, _VP, _I64, _I64, _VP, _I64, _VP, _I64], _I),
         "ipmz_bk_solve_multi_batch": ([_VP, _I, _I, _VP, _I64, _I64, _VP, _I64, _VP, _VP, _I64, _I64, _I], _I),
         "ipmz_batch_kkt_solve_bk": ([_VP, _I, _VP, _I64, _I64, ctypes.POINTER(_I)], _I),
+        "ipmz_qp_newton_solve_multi": ([_VP, _I, _VP, _I64, _VP, _I64, _VP], _I),
+        "ipmz_batch_newton_solve_multi": ([_VP, _I, _VP, _I64, _I64, _VP, _I64, _I64, _VP, ctypes.POINTER(_I)], _I),
     }
     for name, (args, res) in sig.items():
         fn = getattr(lib, name)
@@ -622,6 +625,15 @@ class Optimizer:
                       "ipmz_qp_kkt_solve_mixed")
         return info, stat
 
+    def newton_solve(self, R_ptr, D_ptr, nrhs, ldr, ldd, alpha_ptr=None):
+        """compute_search_direction_ for a block of residual vectors: row r of R (device, nrhs rows
+        of state_len doubles in the order of residuals(), stride ldr) -> the full Newton direction
+        of J d = -r at the current iterate in row r of D (the order of daff(), stride ldd; D may
+        be R), and get_max_step_ of it in alpha[r] (device, optional).  One factor for all rows;
+        returns the factor's info.  fp64 LDL^T or Bunch-Kaufman (EQ_NONE) by the formulation."""
+        return _check(lib.ipmz_qp_newton_solve_multi(self.h, nrhs, _VP(R_ptr), ldr, _VP(D_ptr), ldd, _VP(alpha_ptr)),
+                      "ipmz_qp_newton_solve_multi")
+
     def set_timing(self, on=True):
         _check(lib.ipmz_qp_set_timing(self.h, 1 if on else 0), "ipmz_qp_set_timing")
 
@@ -724,6 +736,17 @@ class Batch(Optimizer):
         rc = _check(lib.ipmz_batch_kkt_solve_bk(self.h, nrhs, _VP(B_ptr), ldb, sB,
                                                 info.ctypes.data_as(ctypes.POINTER(_I))), "ipmz_batch_kkt_solve_bk")
         return rc, info
+
+    def newton_solve_all(self, R_ptr, D_ptr, nrhs, ldr, sR, ldd, sD, alpha_ptr=None):
+        """newton_solve for every QP of the batch at once: QP q's rows at R + q * sR and D + q * sD,
+        its step lengths at alpha[q * nrhs ..].  Returns the batched factor's info word, or for
+        EQ_NONE batches (Bunch-Kaufman) (the smallest non-zero per-QP info word or 0, the per-QP
+        words), like kkt_solve_all_bk."""
+        info = np.zeros(self.batch, dtype=np.int32)
+        rc = _check(lib.ipmz_batch_newton_solve_multi(self.h, nrhs, _VP(R_ptr), ldr, sR, _VP(D_ptr), ldd, sD,
+                                                      _VP(alpha_ptr), info.ctypes.data_as(ctypes.POINTER(_I))),
+                    "ipmz_batch_newton_solve_multi")
+        return (rc, info) if self.equality_handling == EQ_NONE else rc
 
     def batch_scalars(self):
         out = np.zeros(self.batch * SC_COUNT)

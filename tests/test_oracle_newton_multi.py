@@ -1,0 +1,73 @@
+"""What tests/test_gpu_newton_multi.py relies on, checked without a GPU: the
+independent reference of tests/newton_multi_cases.py -- the dense Jacobian of
+the full Newton system, numpy.linalg.solve, get_max_step_ in numpy -- against
+the oracle's own Newton step.  For every shape, Regularization and None
+equalities, at iterates 0-3:
+
+  * numpy.linalg.solve(J, -residuals_numpy) equals oracle.daff() within 1e-13
+    in the tests' measure (measured: <= 2.3e-15; the device bound is 1e-10);
+  * max_step_numpy(vars, daff) equals the oracle record's alpha_aff exactly.
+"""
+import numpy as np
+import pytest
+
+import newton_multi_cases as nc
+import oracle
+
+REF_TOL = 1e-13
+SHAPES = nc.SHAPES + [c[:3] for c in nc.BATCHES[1:]]
+# (without equality rows the two handlings are the same system)
+CASES = [(c, e) for c in SHAPES for e in (False, True) if c[2] or not e]
+
+
+@pytest.mark.parametrize("c,eq_none", CASES, ids=[nc.case_id(c) + ("_none" if e else "_reg") for c, e in CASES])
+def test_jacobian_solve_is_the_oracles_direction(c, eq_none):
+    n, m, p = c
+    q = nc.qp(n, m, p)
+    o = oracle.OracleQP(q, eq_none=eq_none)
+    order, sz, off, L = nc.offsets(q, eq_none)
+    assert list(order) == list(o.order) and L == o.L
+    worst = worst_cond = 0.0
+    for it in range(4):
+        v = o.vars()
+        r = nc.residuals_numpy(q, v, eq_none)
+        J = nc.full_jacobian(q, v, o.order, eq_none)
+        d = np.linalg.solve(J, -r)
+        done, rec = o.iterate()
+        assert not done, it
+        worst = max(worst, nc.row_err(d[None], o.daff()[None]))
+        worst_cond = max(worst_cond, np.linalg.cond(J))
+        assert nc.max_step_numpy(q, v, o.daff(), eq_none) == rec["alpha_aff"], it
+        assert nc.max_step_numpy(q, v, o.dir(), eq_none) == rec["alpha"], it
+    print(f"{nc.case_id(c)} eq_none={eq_none}: J-solve vs oracle.daff {worst:.3e} (bound {REF_TOL:.1e}), "
+          f"cond(J) <= {worst_cond:.1f}", flush=True)
+    assert worst < REF_TOL
+
+
+def test_shapes_reach_what_they_name():
+    N = [sum(c) for c in nc.SHAPES]
+    assert N == [20, 72, 321, 40]
+    q = nc.qp(*nc.SHAPES[2])
+    L = nc.offsets(q, True)[3]  # EqualityHandling::None: 5 n + 6 m + p
+    assert N[2] % 2 == 1 and L == 1585 and nc.even(L) == L + 1 and nc.offsets(q, False)[3] == 1602
+    assert len(set(nc.offsets(nc.qp(*nc.SHAPES[0]), False)[1].values())) == 3  # n, m, p all differ
+    assert "s" not in nc.offsets(nc.qp(*nc.SHAPES[3]), False)[2]  # box-only: no g / h
+    # right-hand-side counts against the kernels' row group
+    import os
+    import re
+    with open(os.path.join(os.path.dirname(os.path.dirname(os.path.abspath(__file__))), "ipm-zoo_amd", "csrc",
+                           "kernels.h")) as f:
+        rpg = int(re.search(r"#define IPMZ_NEWTON_MULTI_RPG (\d+)", f.read()).group(1))
+    with open(os.path.join(os.path.dirname(os.path.dirname(os.path.abspath(__file__))), "ipm-zoo_amd", "csrc",
+                           "newton.hip")) as f:
+        assert f"if (qb.h.n + qb.h.m > {nc.RATIO_WIDE})" in f.read()
+    assert [c[0] + c[1] > nc.RATIO_WIDE for c in nc.RATIO_SHAPES] == [False, True]
+    assert nc.RATIO_SHAPES[0][0] + nc.RATIO_SHAPES[0][1] == nc.RATIO_WIDE
+    assert rpg == nc.RPG and any(r % rpg for r in nc.RHS_COUNTS if r > rpg) and any(r < rpg for r in nc.RHS_COUNTS)
+
+
+def test_random_rows_stay_moderate():
+    q = nc.qp(*nc.SHAPES[1])
+    o = oracle.OracleQP(q)
+    D = nc.reference(q, o.vars(), nc.rows(o.L)[0])
+    assert 1.0 < np.abs(D).max() < 1e3
