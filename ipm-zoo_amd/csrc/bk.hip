@@ -823,11 +823,6 @@ hipError_t bk_transpose(const double* F, int64_t ld, int n, double* LT, hipStrea
   hipLaunchKernelGGL(k_bk_transpose, dim3(nb, nb, bb.B), dim3(256), 0, st, F, ld, bb.sA, n, LT, (int64_t)n, bb.sLT);
   return hipGetLastError();
 }
-hipError_t bk_solve_lt(const double* LT, int n, const int* ipiv, double* b, hipStream_t st) {
-  if (n <= 0) return hipSuccess;
-  hipLaunchKernelGGL(k_bk_solve<true>, dim3(1), dim3(BKT), 0, st, LT, (int64_t)n, n, 0, ipiv, 0, b, 0, nullptr);
-  return hipGetLastError();
-}
 
 
 // ---------------------------------------------------------------------------

@@ -183,21 +183,17 @@ int mixed_factor_impl(ipmz_ctx* ctx, const double* K, int64_t ld, MixedWs& w, Tr
 static constexpr int SOLVE_MULTI_PANEL = IPMZ_SOLVE_MULTI_PANEL;
 static constexpr int SOLVE_MULTI_CROSSOVER = 10;
 static_assert(SOLVE_MULTI_PANEL % 128 == 0 && SOLVE_MULTI_PANEL <= IPMZ_TRSM_PANEL_MAX, "panel width");
-// panel width of a blocked solve (fp64 here, fp32 in mixed_multi_impl): the debug bits', else the default
-static int multi_panel_width(int dbg, int dflt) {
-  return (dbg & IPMZ_DEBUG_MULTI_W512) ? 512 : (dbg & IPMZ_DEBUG_MULTI_W128) ? 128 : dflt;
-}
 
 // nrhs >= 2 rows through the LDL^T factor in w: looped single-vector solves
 // below the crossover, the blocked solve from it on
 static int ldlt_multi_impl(ipmz_ctx* ctx, int N, const double* K, int64_t ld, const double* D, const LdltWs& w,
                            double* B, int64_t ldb, int nrhs) {
-  const int dbg = debug_inject_mask();
-  if (nrhs < SOLVE_MULTI_CROSSOVER && !(dbg & IPMZ_DEBUG_MULTI_BLOCKED)) {
+  const MultiPlan plan =
+      multi_plan(nrhs, SOLVE_MULTI_CROSSOVER, SOLVE_MULTI_PANEL, debug_inject_mask(), MultiKind::Ldlt);
+  if (!plan.blocked) {
     for (int r = 0; r < nrhs; ++r) HIP_OK(solve_ws(K, ld, N, D, w, ctx->nbi, B + (int64_t)r * ldb, ctx->stream));
   } else {
-    const int pw = multi_panel_width(dbg, SOLVE_MULTI_PANEL);
-    HIP_OK(ldlt_solve_multi<double>(K, ld, N, D, w.Linv, ctx->nbi, B, ldb, nrhs, pw, ctx->stream));
+    HIP_OK(ldlt_solve_multi<double>(K, ld, N, D, w.Linv, ctx->nbi, B, ldb, nrhs, plan.width, ctx->stream));
   }
   watch(ctx, w);  // as ipmz_ldlt_solve: the workspace's error words are checked by ipmz_ctx_sync
   return IPMZ_OK;
@@ -218,9 +214,9 @@ static constexpr int BK_MULTI_CROSSOVER = 12;
 
 int bk_multi_impl(ipmz_ctx* ctx, int N, const double* F, int64_t ld, const int* ipiv, const double* LT,
                   const double* Lp, int64_t ldp, const BkWs& w, double* B, int64_t ldb, int nrhs) {
-  const int dbg = debug_inject_mask();
+  const MultiPlan plan = multi_plan(nrhs, BK_MULTI_CROSSOVER, SOLVE_MULTI_PANEL, debug_inject_mask(), MultiKind::Bk);
   hipStream_t st = ctx->stream;
-  if (nrhs < BK_MULTI_CROSSOVER && !(nrhs >= 2 && (dbg & IPMZ_DEBUG_MULTI_BLOCKED))) {
+  if (!plan.blocked) {
     // exactly ipmz_bk_solve's launches for this order, row by row
     for (int r = 0; r < nrhs; ++r) {
       double* b = B + (int64_t)r * ldb;
@@ -231,11 +227,10 @@ int bk_multi_impl(ipmz_ctx* ctx, int N, const double* F, int64_t ld, const int* 
     // every stage exits on the fallback flag, read on the device; the
     // fallback launch is gated the other way
     const unsigned* flag = bk_fast_flag(w.meta);
-    const int pw = multi_panel_width(dbg, SOLVE_MULTI_PANEL);
     HIP_OK(bk_multi_gather(B, ldb, nrhs, N, w.meta, st));
-    HIP_OK(trsm_sweep<double>(Lp, ldp, N, w.Linv, 64, B, ldb, nrhs, pw, false, st, flag));
+    HIP_OK(trsm_sweep<double>(Lp, ldp, N, w.Linv, 64, B, ldb, nrhs, plan.width, false, st, flag));
     HIP_OK(bk_multi_dsolve(B, ldb, nrhs, N, w.meta, st));
-    HIP_OK(trsm_sweep<double>(Lp, ldp, N, w.Linv, 64, B, ldb, nrhs, pw, true, st, flag));
+    HIP_OK(trsm_sweep<double>(Lp, ldp, N, w.Linv, 64, B, ldb, nrhs, plan.width, true, st, flag));
     HIP_OK(bk_multi_scatter(B, ldb, nrhs, N, w.meta, st));
     HIP_OK(bk_multi_fallback(LT, N, ipiv, B, ldb, nrhs, w.meta, st));
   }
@@ -272,15 +267,19 @@ int bk_batch_info(hipStream_t st, const int* dinfo, int batch, int* info) {
   return rc;
 }
 
+// the batch's strides as the kernels take them: the prepared workspace's, and the caller's for F, ipiv and B
+static BkBatch bk_batch(const BkBatchWs& w, int batch, int64_t sA, int64_t sP, int64_t sB) {
+  return BkBatch{batch, sA, sP, w.sLT, w.sLp, sB};
+}
+// ... and as the blocked sweeps take them (K = L', no D; the gate: a flagged system's launches exit)
+static TrsmBatch trsm_batch(const BkBatchWs& w, int batch, int64_t sB) {
+  return TrsmBatch{batch, w.sLp, 0, w.sLinv, sB, w.sM / (int64_t)sizeof(unsigned)};
+}
+
 int bk_batch_prepare(ipmz_ctx* ctx, int N, int batch, const double* F, int64_t ld, int64_t sA, const int* ipiv,
                      int64_t sP, const int* info, const BkBatchWs& w) {
   hipStream_t st = ctx->stream;
-  BkBatch bb;
-  bb.B = batch;
-  bb.sA = sA;
-  bb.sP = sP;
-  bb.sLT = w.sLT;
-  bb.sLp = w.sLp;
+  const BkBatch bb = bk_batch(w, batch, sA, sP, 0);
   HIP_OK(bk_transpose(F, ld, N, w.LT, st, bb));
   HIP_OK(bk_fast_prepare(F, ld, N, ipiv, info, w.LT, w.Lp, w.ldp, w.meta, st, bb));
   HIP_OK(linv_from_l(w.Lp, w.ldp, N, 64, w.Linv, st, batch, w.sLp, w.sLinv));
@@ -289,41 +288,28 @@ int bk_batch_prepare(ipmz_ctx* ctx, int N, int batch, const double* F, int64_t l
 
 int bk_batch_multi_impl(ipmz_ctx* ctx, int N, int batch, const double* F, int64_t ld, int64_t sA, const int* ipiv,
                         int64_t sP, const BkBatchWs& w, double* B, int64_t ldb, int64_t sB, int nrhs) {
-  const int dbg = debug_inject_mask();
+  const MultiPlan plan =
+      multi_plan(nrhs, BK_BATCH_MULTI_CROSSOVER, SOLVE_MULTI_PANEL, debug_inject_mask(), MultiKind::Batch);
   hipStream_t st = ctx->stream;
-  if (nrhs < BK_BATCH_MULTI_CROSSOVER && !(nrhs >= 2 && (dbg & IPMZ_DEBUG_MULTI_BLOCKED))) {
+  if (!plan.blocked) {
     // the step's own kernel, one launch per row for all systems
     for (int r = 0; r < nrhs; ++r) HIP_OK(bk_solve(F, ld, N, ipiv, B + (int64_t)r * ldb, batch, sA, sP, sB, st));
     return IPMZ_OK;
   }
-  BkBatch bb;
-  bb.B = batch;
-  bb.sA = sA;
-  bb.sP = sP;
-  bb.sLT = w.sLT;
-  bb.sLp = w.sLp;
-  bb.sB = sB;
-  TrsmBatch tb;
-  tb.B = batch;
-  tb.sK = w.sLp;
-  tb.sL = w.sLinv;
-  tb.sB = sB;
-  tb.sG = w.sM / (int64_t)sizeof(unsigned);  // a fallback flag per system: a flagged system's launches exit
+  const BkBatch bb = bk_batch(w, batch, sA, sP, sB);
+  const TrsmBatch tb = trsm_batch(w, batch, sB);
   const unsigned* flag = bk_fast_flag(w.meta);
   // one launch per batch where a system's slab fits a workgroup's LDS, unless
   // a panel width is forced; then the flagged systems' reference sweeps
-  if (!(dbg & (IPMZ_DEBUG_MULTI_W128 | IPMZ_DEBUG_MULTI_W512)) && bk_solve_fused_eligible(N)) {
+  if (plan.fused && bk_solve_fused_eligible(N)) {
     HIP_OK(bk_solve_fused(w.Lp, w.ldp, N, w.Linv, B, ldb, nrhs, bk_fused_meta(w.meta, N, bb), st, tb));
     HIP_OK(bk_multi_fallback_batch(w.LT, N, ipiv, B, ldb, nrhs, w.meta, st, bb));
     return IPMZ_OK;
   }
-  // (both width bits together: the panel chain at its default width, as ipmz_batch_kkt_solve)
-  const bool w512 = dbg & IPMZ_DEBUG_MULTI_W512, w128 = dbg & IPMZ_DEBUG_MULTI_W128;
-  const int pw = w512 && w128 ? SOLVE_MULTI_PANEL : w512 ? 512 : w128 ? 128 : SOLVE_MULTI_PANEL;
   HIP_OK(bk_multi_gather(B, ldb, nrhs, N, w.meta, st, bb));
-  HIP_OK(trsm_sweep<double>(w.Lp, w.ldp, N, w.Linv, 64, B, ldb, nrhs, pw, false, st, flag, tb));
+  HIP_OK(trsm_sweep<double>(w.Lp, w.ldp, N, w.Linv, 64, B, ldb, nrhs, plan.width, false, st, flag, tb));
   HIP_OK(bk_multi_dsolve(B, ldb, nrhs, N, w.meta, st, bb));
-  HIP_OK(trsm_sweep<double>(w.Lp, w.ldp, N, w.Linv, 64, B, ldb, nrhs, pw, true, st, flag, tb));
+  HIP_OK(trsm_sweep<double>(w.Lp, w.ldp, N, w.Linv, 64, B, ldb, nrhs, plan.width, true, st, flag, tb));
   HIP_OK(bk_multi_scatter(B, ldb, nrhs, N, w.meta, st, bb));
   HIP_OK(bk_multi_fallback_batch(w.LT, N, ipiv, B, ldb, nrhs, w.meta, st, bb));
   return IPMZ_OK;
@@ -352,16 +338,16 @@ static_assert(MIXED_MULTI_PANEL % 128 == 0 && MIXED_MULTI_PANEL <= IPMZ_TRSM_PAN
 // null); synchronizes
 int mixed_multi_impl(ipmz_ctx* ctx, const double* K, int64_t ld, MixedWs& w, const MixedMultiWs& m, double* B,
                      int64_t ldb, int nrhs, double tol, int max_refine, double* stat) {
-  const int dbg = debug_inject_mask();
+  const MultiPlan plan =
+      multi_plan(nrhs, MIXED_MULTI_CROSSOVER, MIXED_MULTI_PANEL, debug_inject_mask(), MultiKind::Ldlt);
   hipStream_t st = ctx->stream;
-  if (nrhs < MIXED_MULTI_CROSSOVER && !(dbg & IPMZ_DEBUG_MULTI_BLOCKED)) {
+  if (!plan.blocked) {
     for (int r = 0; r < nrhs; ++r) {
       HIP_OK(mixed_solve(K, ld, w, B + (int64_t)r * ldb, tol, max_refine, st));
       HIP_OK(hipMemcpyAsync(m.stat + 2 * r, w.stat, 2 * sizeof(double), hipMemcpyDeviceToDevice, st));
     }
   } else {
-    const int pw = multi_panel_width(dbg, MIXED_MULTI_PANEL);
-    HIP_OK(mixed_solve_multi(K, ld, w, m, B, ldb, nrhs, tol, max_refine, pw, st));
+    HIP_OK(mixed_solve_multi(K, ld, w, m, B, ldb, nrhs, tol, max_refine, plan.width, st));
   }
   if (stat) HIP_OK(hipMemcpyAsync(stat, m.stat, (size_t)nrhs * 2 * sizeof(double), hipMemcpyDeviceToHost, st));
   HIP_OK(hipStreamSynchronize(st));

@@ -191,6 +191,45 @@ inline void watch(ipmz_ctx* ctx, const LdltWs& w) { watch(ctx, w.pctrl + PANEL_E
 inline void watch(ipmz_ctx* ctx, const BkWs& w) { watch(ctx, nullptr, w.ctrl + SOLVE_ERR_WORD); }
 inline void unwatch(ipmz_ctx* ctx) { ctx->check_pe = ctx->check_se = nullptr; }
 
+// How a multi-right-hand-side solve serves nrhs rows: looped single-vector solves below the path's crossover, from
+// it on the blocked solve in column panels of the path's default width.  Debug bits (kernels.h) force the blocked
+// solve (IPMZ_DEBUG_MULTI_BLOCKED) or a panel width (_W512, _W128).  The kinds differ on purpose:
+//   Ldlt   one system, LDL^T (fp64, normal equations, mixed): MULTI_BLOCKED at any row count; both width bits: 512
+//   Bk     one system, Bunch-Kaufman: MULTI_BLOCKED from 2 rows on (one row stays ipmz_bk_solve's launches); both: 512
+//   Batch  a batch, either factor: MULTI_BLOCKED from 2 rows on; the one-launch solve where it is eligible and no
+//          width is forced; both width bits: the panel chain at the default width (tools/batch_multi_bench.py)
+enum class MultiKind { Ldlt, Bk, Batch };
+struct MultiPlan {
+  bool blocked;  // false: nrhs looped single-vector solves
+  int width;     // the blocked solve's panel width
+  bool fused;    // blocked, and the one-launch solve may be taken where eligible
+};
+constexpr MultiPlan multi_plan(int nrhs, int crossover, int panel, int dbg, MultiKind kind) {
+  const bool w512 = dbg & IPMZ_DEBUG_MULTI_W512, w128 = dbg & IPMZ_DEBUG_MULTI_W128;
+  const bool batch = kind == MultiKind::Batch;
+  const bool blocked =
+      nrhs >= crossover || ((dbg & IPMZ_DEBUG_MULTI_BLOCKED) && (kind == MultiKind::Ldlt || nrhs >= 2));
+  return {blocked, batch && w512 && w128 ? panel : w512 ? 512 : w128 ? 128 : panel, blocked && batch && !w512 && !w128};
+}
+// Pinned for all eight combinations of the three bits at 1, 2, crossover - 1 and crossover rows (crossover 10,
+// default panel 256).  forced: the counts that MULTI_BLOCKED runs blocked (a bit per count, lowest: 1 row); the
+// widths with no width bit, W512, W128 and both; fused: the one-launch solve where blocked and no width bit is set
+constexpr bool multi_plan_pins(MultiKind kind, int forced, int w0, int w512, int w128, int wboth, bool fused) {
+  const int rows[4] = {1, 2, 9, 10}, width[4] = {w0, w512, w128, wboth};
+  for (int m = 0; m < 8; ++m)
+    for (int i = 0; i < 4; ++i) {
+      const int dbg = (m & 1 ? IPMZ_DEBUG_MULTI_W512 : 0) | (m & 2 ? IPMZ_DEBUG_MULTI_W128 : 0) |
+                      (m & 4 ? IPMZ_DEBUG_MULTI_BLOCKED : 0);
+      const bool blocked = i == 3 || ((m & 4) && (forced >> i & 1));
+      const MultiPlan p = multi_plan(rows[i], 10, 256, dbg, kind);
+      if (p.blocked != blocked || p.width != width[m & 3] || p.fused != (blocked && fused && !(m & 3))) return false;
+    }
+  return true;
+}
+static_assert(multi_plan_pins(MultiKind::Ldlt, 0b1111, 256, 512, 128, 512, false), "Ldlt: blocked at any count, 512 wins");
+static_assert(multi_plan_pins(MultiKind::Bk, 0b1110, 256, 512, 128, 512, false), "Bk: blocked from 2 rows, 512 wins");
+static_assert(multi_plan_pins(MultiKind::Batch, 0b1110, 256, 512, 128, 256, true), "Batch: from 2 rows, both = default");
+
 // capi.cpp --------------------------------------------------------------------
 // One batch of copies and one synchronize: the sticky error words pe (panel
 // factor) and se (persistent solve), then the info word; each may be null.

@@ -38,14 +38,10 @@ namespace ipmz {
 //        (what a serialized dispatch order can produce; the forms must factor bitwise alike),
 // 8192 = batches assemble the whole KKT into K every step (not the kept K0) (A/B),
 // 16384 = batches run the two solves and the phases between them as separate launches (A/B),
-// 65536 = ipmz_ldlt_solve_multi runs its blocked path from 2 right-hand sides on (no looped single-vector
-//         solves below the crossover) (A/B, tools/solve_multi_bench.py); ipmz_mixed_solve_multi and
-//         ipmz_qp_kkt_solve_mixed likewise (tools/mixed_multi_bench.py), and ipmz_normal_solve_multi,
-//         ipmz_bk_solve_multi and ipmz_qp_kkt_solve_bk (tools/bk_multi_bench.py),
-//         and ipmz_batch_kkt_solve (tools/batch_multi_bench.py),
-// 131072 / 262144 = ... with 512- / 128-column panels instead of IPMZ_SOLVE_MULTI_PANEL (A/B); in
-//         ipmz_batch_kkt_solve either bit also selects the panel chain where the one-launch solve is
-//         eligible, and both together the panel chain at IPMZ_SOLVE_MULTI_PANEL,
+// 65536 = every multi-right-hand-side solve runs its blocked path from 2 right-hand sides on (no looped
+//         single-vector solves below the crossover) (A/B, tools/*_multi_bench.py),
+// 131072 / 262144 = ... with 512- / 128-column panels instead of its default width (A/B); the batched solves
+//         then take the panel chain where the one-launch solve is eligible (capi.h multi_plan: the rule per path),
 // 524288 / 1048576 = the persistent solve splits every 128-row block over 2 / 4 workgroups, whatever
 //         its table says; both bits = the unsplit solve (all three bitwise alike,
 //         tests/test_gpu_solve_split.py),
@@ -334,9 +330,9 @@ hipError_t bk_solve(const double* F, int64_t ld, int n, const int* ipiv, double*
 size_t bk_grid_ws_bytes(int n);
 hipError_t bk_factor_grid(double* A, int64_t ld, int n, int* ipiv, int* info, int fix_kp, void* ws, hipStream_t st);
 const unsigned* bk_grid_err_word(const void* ws, int n);
-// one system's solve through a transposed copy of the factor's lower
-// triangle (LT: n x n doubles, row j = column j of L; bk_transpose once per
-// factor): coalesced sweeps, the same arithmetic as bk_solve
+// A transposed copy of the factor's lower triangle (LT: n x n doubles, row j =
+// column j of L; bk_transpose once per factor): the device-wide solve's input
+// and its fallbacks' factor (coalesced sweeps, the same arithmetic as bk_solve).
 // A batch of B systems of one order behind the prepared solve's launches (the
 // system is a grid dimension): the factors, pivots, LT, L' and right-hand
 // sides of consecutive systems lie sA, sP, sLT, sLp and sB elements apart;
@@ -348,7 +344,6 @@ struct BkBatch {
 };
 hipError_t bk_transpose(const double* F, int64_t ld, int n, double* LT, hipStream_t st,
                         const BkBatch& bb = BkBatch());
-hipError_t bk_solve_lt(const double* LT, int n, const int* ipiv, double* b, hipStream_t st);
 // Device-wide solve: A^{-1} b = P^T L'^{-T} D^{-1} L'^{-1} P b, L' = L with every
 // later interchange folded into its columns (once per factor, bk_fast_prepare:
 // from F, ipiv, the factor's info word and LT = bk_transpose(F); LT is

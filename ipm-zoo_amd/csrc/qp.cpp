@@ -10,6 +10,12 @@
 
 #include "capi.h"
 
+// a device buffer kept for the largest size asked of it so far (grow)
+struct GrowBuf {
+  char* p = nullptr;
+  size_t bytes = 0;
+};
+
 struct ipmz_qp {
   ipmz_ctx* ctx = nullptr;
   int n = 0, m = 0, p = 0, N = 0, B = 1;
@@ -28,7 +34,6 @@ struct ipmz_qp {
   // every step); the small factor reads it and writes L to K (strides sK)
   double* K0 = nullptr;
   char* ws = nullptr;      // B == 1: ldlt_ws(N); B > 1: bLinv, bW, binfo below
-  int64_t ws_bytes = 0;
   double *bLinv = nullptr, *bW = nullptr;  // batched factor workspace (B > 1)
   int* binfo = nullptr;
   int64_t sL = 0, sW = 0;
@@ -38,22 +43,23 @@ struct ipmz_qp {
   double ir_tol = 1e-12;
   int ir_max = 10;
   MixedWs mw;
-  char* mws = nullptr;
+  GrowBuf mws;
   // ipmz_qp_kkt_solve_mixed: the multi-right-hand-side workspace, for the largest nrhs seen
-  char* mmws = nullptr;
-  int mmws_nrhs = 0;
+  GrowBuf mmws;
   // ipmz_*_newton_solve_multi: the reduced right-hand sides, B x nrhs x round_up(N, 2) doubles, for the largest nrhs seen
-  double* nmws = nullptr;
-  int nmws_nrhs = 0;
+  GrowBuf nmws;
   // normal-equations reduction (C2)
   bool normal = false;
   // EqualityHandling::None: Bunch-Kaufman factor (pivots per QP)
   bool eqnone = false;
-  char* bkws = nullptr;  // the whole-device Bunch-Kaufman factor's workspace (B == 1, N >= IPMZ_BK_GRID_MIN)
-  double* bklt = nullptr;  // its factor transposed (N x N): the interchange folding's input, the fallback's factor
-  char* bkfws = nullptr;   // the device-wide solve's workspace (bk_ws), L' in K
-  char* bkmws = nullptr;   // ipmz_qp_kkt_solve_bk below that order: its prepared solve (bk_solve_ws), on first use
-  char* bkbws = nullptr;   // ipmz_batch_kkt_solve_bk: the batch's prepared solves (bk_batch_ws), on first use
+  // Path::BkGrid only, allocated together: the whole-device factor's workspace, the factor transposed (N x N: the
+  // interchange folding's input, the fallback's factor), the device-wide solve's workspace (bk_ws; L' in K)
+  char* bkws = nullptr;
+  double* bklt = nullptr;
+  char* bkfws = nullptr;
+  // ipmz_*_kkt_solve_bk on the other two Bunch-Kaufman paths, on first use: the prepared solve (Path::BkSmall,
+  // bk_solve_ws), the batch's prepared solves (Path::BkBatch, bk_batch_ws)
+  GrowBuf bkpws;
   unsigned* pflags = nullptr;  // B > 1: the two-workgroup small factor's flags + sticky error word
   int small_kernel = IPMZ_BATCH_FACTOR_AUTO;  // ipmz_batch_set_factor_kernel
   bool eqpen = false;  // EqualityHandling::PenaltyFunction (LDL^T)
@@ -66,7 +72,7 @@ struct ipmz_qp {
   bool vlo = true, vup = true, alo = true, aup = true;
   int* ipiv = nullptr;
   int64_t sP = 0;
-  char* nws = nullptr;
+  GrowBuf nws;  // the normal equations' workspace (normal_ws), when the reduction is first enabled
   hipGraph_t graph = nullptr;
   hipGraphExec_t gexec = nullptr;
   int graph_flags = -1;
@@ -126,6 +132,22 @@ double* dev_array(ipmz_qp* s, int64_t count, int64_t* stride_out = nullptr, bool
   return dev_alloc<double>(s, (size_t)(stride * s->B), zero);
 }
 
+// b holds at least `bytes`: kept, or freed and allocated anew (the caller has synchronized whatever may still
+// read it).  A failure is IPMZ_ERR_NOMEM and leaves b empty and the solver usable: the next call tries again
+int grow(ipmz_qp* s, GrowBuf& b, size_t bytes, bool zero = false) {
+  if (bytes <= b.bytes) return IPMZ_OK;
+  if (b.p) {
+    s->allocs.erase(std::find(s->allocs.begin(), s->allocs.end(), static_cast<void*>(b.p)));
+    hipFree(b.p);
+  }
+  b = GrowBuf{dev_alloc<char>(s, bytes, zero), bytes};
+  if (!s->alloc_failed) return IPMZ_OK;
+  b = GrowBuf{};
+  s->alloc_failed = false;  // (create_solver's flag)
+  (void)hipGetLastError();
+  return fail(IPMZ_ERR_NOMEM, "device allocation failed");
+}
+
 void drop_graph(ipmz_qp* s) {
   if (s->gexec) hipGraphExecDestroy(s->gexec);
   if (s->graph) hipGraphDestroy(s->graph);
@@ -148,29 +170,52 @@ void carve(const ipmz_qp* s, double* base, double** slots) {
 
 QPDev& q0(ipmz_qp* s) { return s->hq[0]; }
 
+// The factor / solve path a solver runs, from its configuration alone: the fp64 augmented LDL^T of one QP or of a
+// batch, the normal-equations reduction, the fp32 factor with fp64 refinement (both B == 1), and
+// EqualityHandling::None's Bunch-Kaufman -- B == 1 from IPMZ_BK_GRID_MIN up (whole-device factor, device-wide
+// solve) and below it (one workgroup), B > 1 (one workgroup per system)
+enum class Path { Ldlt, LdltBatch, Normal, Mixed, BkGrid, BkSmall, BkBatch };
+Path path_of(const ipmz_qp* s) {
+  if (s->eqnone) return s->B > 1 ? Path::BkBatch : s->N >= IPMZ_BK_GRID_MIN ? Path::BkGrid : Path::BkSmall;
+  if (s->normal) return Path::Normal;
+  if (s->mixed) return Path::Mixed;
+  return s->B == 1 ? Path::Ldlt : Path::LdltBatch;
+}
+
 // the solver's own workspaces at the context's current blocking: s->ws
-// (B == 1, augmented LDL^T) and s->nws (normal equations, N = n + m + p)
+// (Path::Ldlt) and s->nws (Path::Normal, N = n + m + p)
 LdltWs ldlt_ws_of(const ipmz_qp* s) { return ldlt_ws(s->ws, s->N, nbo_for(s->ctx, s->N), s->ctx->nbi); }
-NormalWs normal_ws_of(const ipmz_qp* s) { return normal_ws(s->nws, s->N, nbo_for(s->ctx, s->N), s->ctx->nbi); }
+NormalWs normal_ws_of(const ipmz_qp* s) { return normal_ws(s->nws.p, s->N, nbo_for(s->ctx, s->N), s->ctx->nbi); }
+
+// the batch's strides as the batched LDL^T factor and the blocked solves take them
+BatchStrides batch_strides(const ipmz_qp* s, const double* K0) {
+  return BatchStrides{s->B, s->sK, s->sD, s->sL, s->sW, s->pflags, K0, s->small_kernel};
+}
+TrsmBatch trsm_batch(const ipmz_qp* s, int64_t sB) { return TrsmBatch{s->B, s->sK, s->sD, s->sL, sB}; }
 
 int solve_batch(ipmz_qp* s, hipStream_t st, int which) {
-  if (s->eqnone && s->bkfws) {  // overwriting_solve_bunch_kaufman, device-wide (L' in K)
-    HIP_OK(bk_run(s->K, s->ldk, s->N, s->bklt, s->ipiv, bk_ws(s->bkfws, s->N), q0(s).b, st));
-  } else if (s->eqnone && s->bklt) {  // overwriting_solve_bunch_kaufman on the transposed factor
-    HIP_OK(bk_solve_lt(s->bklt, s->N, s->ipiv, q0(s).b, st));
-  } else if (s->eqnone) {  // overwriting_solve_bunch_kaufman
-    HIP_OK(bk_solve(s->K, s->ldk, s->N, s->ipiv, q0(s).b, s->B, s->sK, s->sP, s->sb, st));
-  } else if (s->normal) {
-    return normal_solve_impl(s->ctx, s->n, s->m + s->p, s->K, s->ldk, s->D, normal_ws_of(s), q0(s).b);
-  } else if (s->mixed) {
-    HIP_OK(mixed_solve(s->K, s->ldk, s->mw, q0(s).b, s->ir_tol, s->ir_max, st));
-    HIP_OK(hipMemcpyAsync(q0(s).scal + IPMZ_SC_IR_RATIO_AFF + 2 * which, s->mw.stat, 2 * sizeof(double),
-                          hipMemcpyDeviceToDevice, st));
-  } else if (s->B == 1) {
-    HIP_OK(solve_ws(s->K, s->ldk, s->N, s->D, ldlt_ws_of(s), s->ctx->nbi, q0(s).b, st));
-  } else {
-    HIP_OK(ldlt_solve_batched(s->K, s->ldk, s->N, s->D, s->bLinv, s->ctx->nbi, q0(s).b, s->B, s->sK, s->sD, s->sL,
-                              s->sb, st));
+  switch (path_of(s)) {
+    case Path::BkGrid:  // overwriting_solve_bunch_kaufman, device-wide (L' in K)
+      HIP_OK(bk_run(s->K, s->ldk, s->N, s->bklt, s->ipiv, bk_ws(s->bkfws, s->N), q0(s).b, st));
+      break;
+    case Path::BkSmall:
+    case Path::BkBatch:  // overwriting_solve_bunch_kaufman
+      HIP_OK(bk_solve(s->K, s->ldk, s->N, s->ipiv, q0(s).b, s->B, s->sK, s->sP, s->sb, st));
+      break;
+    case Path::Normal:
+      return normal_solve_impl(s->ctx, s->n, s->m + s->p, s->K, s->ldk, s->D, normal_ws_of(s), q0(s).b);
+    case Path::Mixed:
+      HIP_OK(mixed_solve(s->K, s->ldk, s->mw, q0(s).b, s->ir_tol, s->ir_max, st));
+      HIP_OK(hipMemcpyAsync(q0(s).scal + IPMZ_SC_IR_RATIO_AFF + 2 * which, s->mw.stat, 2 * sizeof(double),
+                            hipMemcpyDeviceToDevice, st));
+      break;
+    case Path::Ldlt:
+      HIP_OK(solve_ws(s->K, s->ldk, s->N, s->D, ldlt_ws_of(s), s->ctx->nbi, q0(s).b, st));
+      break;
+    case Path::LdltBatch:
+      HIP_OK(ldlt_solve_batched(s->K, s->ldk, s->N, s->D, s->bLinv, s->ctx->nbi, q0(s).b, s->B, s->sK, s->sD, s->sL,
+                                s->sb, st));
+      break;
   }
   return IPMZ_OK;
 }
@@ -178,35 +223,30 @@ int solve_batch(ipmz_qp* s, hipStream_t st, int which) {
 // info_reset: the caller already reset the batched factor's info word
 bool uses_k0(const ipmz_qp* s);
 int factor_batch(ipmz_qp* s, TrailTimer* tt, bool info_reset) {
-  if (s->eqnone) {  // zero diagonal block: symmetric_indefinite_factorization (reference kp behaviour)
-    if (s->bkws) {
-      HIP_OK(bk_factor_grid(s->K, s->ldk, s->N, s->ipiv, s->binfo, 0, s->bkws, s->ctx->stream));
-      HIP_OK(bk_transpose(s->K, s->ldk, s->N, s->bklt, s->ctx->stream));
-      if (s->bkfws)  // L' into K (the factor is not read again this step)
-        HIP_OK(bk_setup(s->K, s->ldk, s->N, s->ipiv, s->binfo, s->bklt, s->K, s->ldk, bk_ws(s->bkfws, s->N),
-                        s->ctx->stream));
-      return IPMZ_OK;
-    }
-    HIP_OK(bk_factor(s->K, s->ldk, s->N, s->ipiv, s->binfo, 0, s->B, s->sK, s->sP, s->ctx->stream));
-    return IPMZ_OK;
-  }
-  if (s->mixed) return mixed_factor_impl(s->ctx, s->K, s->ldk, s->mw, tt);
+  hipStream_t st = s->ctx->stream;
   const int nbo = nbo_for(s->ctx, s->N);
-  if (s->normal)
-    return normal_factor_impl(s->ctx, s->n, s->m + s->p, s->K, s->ldk, s->D, normal_ws_of(s), nbo, tt);
-  if (s->B == 1) return factor_impl(s->ctx, s->N, s->K, s->ldk, s->D, ldlt_ws_of(s), nbo, tt);
-  BatchStrides bs;
-  bs.B = s->B;
-  bs.sK = s->sK;
-  bs.sD = s->sD;
-  bs.sL = s->sL;
-  bs.sW = s->sW;
-  bs.pflags = s->pflags;
-  bs.small_kernel = s->small_kernel;
-  bs.K0 = info_reset && uses_k0(s) ? s->K0 : nullptr;  // (info_reset: the fused step, whose pre phase assembled into K0)
-  if (!info_reset) HIP_OK(hipMemsetAsync(s->binfo, 0x7f, sizeof(int), s->ctx->stream));
-  HIP_OK(ldlt_factor_batched(s->K, s->ldk, s->N, s->D, s->bLinv, s->bW, nbo, s->ctx->nbi, s->binfo, s->ctx->stream,
-                             bs));
+  switch (path_of(s)) {
+    // EqualityHandling::None, zero diagonal block: symmetric_indefinite_factorization (reference kp behaviour)
+    case Path::BkGrid:
+      HIP_OK(bk_factor_grid(s->K, s->ldk, s->N, s->ipiv, s->binfo, 0, s->bkws, st));
+      HIP_OK(bk_transpose(s->K, s->ldk, s->N, s->bklt, st));
+      // L' into K (the factor is not read again this step)
+      HIP_OK(bk_setup(s->K, s->ldk, s->N, s->ipiv, s->binfo, s->bklt, s->K, s->ldk, bk_ws(s->bkfws, s->N), st));
+      return IPMZ_OK;
+    case Path::BkSmall:
+    case Path::BkBatch:
+      HIP_OK(bk_factor(s->K, s->ldk, s->N, s->ipiv, s->binfo, 0, s->B, s->sK, s->sP, st));
+      return IPMZ_OK;
+    case Path::Mixed: return mixed_factor_impl(s->ctx, s->K, s->ldk, s->mw, tt);
+    case Path::Normal:
+      return normal_factor_impl(s->ctx, s->n, s->m + s->p, s->K, s->ldk, s->D, normal_ws_of(s), nbo, tt);
+    case Path::Ldlt: return factor_impl(s->ctx, s->N, s->K, s->ldk, s->D, ldlt_ws_of(s), nbo, tt);
+    case Path::LdltBatch: break;
+  }
+  // (info_reset: the fused step, whose pre phase assembled into K0)
+  if (!info_reset) HIP_OK(hipMemsetAsync(s->binfo, 0x7f, sizeof(int), st));
+  HIP_OK(ldlt_factor_batched(s->K, s->ldk, s->N, s->D, s->bLinv, s->bW, nbo, s->ctx->nbi, s->binfo, st,
+                             batch_strides(s, info_reset && uses_k0(s) ? s->K0 : nullptr)));
   return IPMZ_OK;
 }
 
@@ -216,7 +256,7 @@ bool fused_phases(const ipmz_qp* s) { return s->B > 1 && s->N <= IPMZ_FUSED_NMAX
 // ... whose solves are the small batched solve (solve_batch's last branch,
 // nbi 64): then both solves and the phases between them run as one launch
 bool fused_solves(const ipmz_qp* s) {
-  return fused_phases(s) && !s->eqnone && !s->normal && !s->mixed && s->ctx->nbi == 64 && fused_solves_ok(s->N, s->ldk) &&
+  return fused_phases(s) && path_of(s) == Path::LdltBatch && s->ctx->nbi == 64 && fused_solves_ok(s->N, s->ldk) &&
          !(debug_inject_mask() & IPMZ_DEBUG_NO_FUSED_SOLVES);
 }
 // the fused step keeps the assembled matrix in K0 when the small batched
@@ -432,8 +472,7 @@ int create_solver(ipmz_ctx* ctx, const ipmz_qp_config* cfg, int B, ipmz_qp** out
   s->D = dev_array(s, N, &s->sD);
   s->sb = sNb;
   if (B == 1) {
-    s->ws_bytes = ldlt_ws(nullptr, N, nbo_for(ctx, N), ctx->nbi).total;
-    s->ws = dev_alloc<char>(s, (size_t)s->ws_bytes, true);
+    s->ws = dev_alloc<char>(s, (size_t)ldlt_ws(nullptr, N, nbo_for(ctx, N), ctx->nbi).total, true);
   } else {
     const int64_t nblk = (N + ctx->nbi - 1) / ctx->nbi;
     // zeroed once: the wave-specialized small factor writes only the lower
@@ -451,7 +490,7 @@ int create_solver(ipmz_ctx* ctx, const ipmz_qp_config* cfg, int B, ipmz_qp** out
     s->sP = round_up(N, 16);
     s->ipiv = dev_alloc<int>(s, (size_t)(s->sP * B), false);
     if (!s->binfo) s->binfo = dev_alloc<int>(s, 64, false);
-    if (B == 1 && N >= IPMZ_BK_GRID_MIN) {
+    if (path_of(s) == Path::BkGrid) {
       s->bkws = dev_alloc<char>(s, bk_grid_ws_bytes(N), false);
       s->bklt = dev_alloc<double>(s, (size_t)N * N, false);
       s->bkfws = dev_alloc<char>(s, (size_t)bk_ws(nullptr, N).total, true);
@@ -583,6 +622,14 @@ bool step_forks(const ipmz_qp* s) {
   return (s->N + nbo - 1) / nbo >= 3;
 }
 
+// a forked step still in flight (queue depth 1, step_impl) reads the storage,
+// and takes the events of the context's pool, that a factor enqueued now would
+int wait_pending_step(ipmz_qp* s) {
+  if (s->step_pending) HIP_OK(hipEventSynchronize(s->step_done));
+  s->step_pending = false;
+  return IPMZ_OK;
+}
+
 int step_impl(ipmz_qp* s, int flags) {
   if (!s || !s->loaded) return fail(IPMZ_ERR_STATE, "load or generate the QP first");
   HIP_OK(hipSetDevice(s->ctx->device));
@@ -611,8 +658,8 @@ int step_impl(ipmz_qp* s, int flags) {
     // tools/step_sync_ab.py), so at most one such step is in flight: the host
     // waits for the previous one before enqueuing the next.
     if (!s->step_done) HIP_OK(hipEventCreateWithFlags(&s->step_done, hipEventDisableTiming));
-    if (s->step_pending) HIP_OK(hipEventSynchronize(s->step_done));
-    s->step_pending = false;
+    int rc = wait_pending_step(s);
+    if (rc) return rc;
     // On a stream the caller made (torch's default or side streams) the step
     // runs on the context's own stream, forked from the caller's, and the host
     // waits for it before the caller's stream is joined to it: a join left
@@ -628,7 +675,7 @@ int step_impl(ipmz_qp* s, int flags) {
       HIP_OK(hipStreamWaitEvent(own, s->step_in, 0));
       s->ctx->stream = own;
     }
-    const int rc = run_step(s, flags);
+    rc = run_step(s, flags);
     s->ctx->stream = caller;
     if (rc) return rc;
     HIP_OK(hipEventRecord(s->step_done, own));
@@ -675,39 +722,72 @@ int step_impl(ipmz_qp* s, int flags) {
   return IPMZ_OK;
 }
 
+// The sticky error words a path's kernels raise on a spin timeout (pe: the
+// factor's, se: the persistent solve's; null where the path has none), the
+// sentence for each, and the info word -- of a Newton step (step: no info), or
+// of the factor and prepared solve that the *_kkt_solve* / *_newton_solve_multi
+// calls enqueue (kkt_finish; never Path::Normal or Path::Mixed)
+struct ErrWords {
+  const int* info = nullptr;
+  const unsigned *pe = nullptr, *se = nullptr;
+  const char *pe_text = PANEL_TIMEOUT, *se_text = SOLVE_TIMEOUT;
+};
+ErrWords err_words(const ipmz_qp* s, bool step) {
+  ErrWords e;
+  if (!step) e.info = s->binfo;
+  switch (path_of(s)) {
+    case Path::Mixed:
+      e.pe = s->mw.pctrl + PANEL_ERR_WORD;
+      e.se = s->mw.ctrl + SOLVE_ERR_WORD;
+      e.pe_text = e.se_text = ": a hand-off inside a persistent kernel of the mixed-precision factor / solve timed out; "
+                              "the step is invalid";
+      break;
+    case Path::Normal:
+    case Path::Ldlt: {
+      const LdltWs w = s->normal ? normal_ws_of(s).k : ldlt_ws_of(s);  // (kkt_finish: through read_info)
+      e.pe = w.pctrl + PANEL_ERR_WORD;
+      e.se = w.ctrl + SOLVE_ERR_WORD;
+      break;
+    }
+    case Path::LdltBatch:
+      // only a factor that ran the two-workgroup kernel has a word to read (its launch zeroes it; the default
+      // wave-specialized factor at C4's N = 320 has no cross-workgroup hand-off and needs no sync for it)
+      if (s->ctx->nbi == 64 && small_pair_used(s->small_kernel, s->pflags != nullptr, s->B, s->N))
+        e.pe = s->pflags + (size_t)s->B * IPMZ_PAIR_FLAGS;
+      e.pe_text = step ? ": a hand-off of the two-workgroup batched factor timed out; the step is invalid"
+                       : ": a hand-off of the two-workgroup batched factor timed out; the factor is invalid";
+      break;
+    case Path::BkGrid:
+      e.pe = bk_grid_err_word(s->bkws, s->N);
+      e.se = bk_ws(s->bkfws, s->N).ctrl + SOLVE_ERR_WORD;
+      e.pe_text = step ? ": a grid barrier of the whole-device Bunch-Kaufman factor timed out; the step is invalid"
+                       : ": a grid barrier of the whole-device Bunch-Kaufman factor timed out; the factor is invalid";
+      if (step)
+        e.se_text = ": a hand-off inside the persistent triangular solve of the Bunch-Kaufman factor timed out; the "
+                    "step is invalid";
+      break;
+    case Path::BkSmall:  // the one-workgroup kernels have no cross-workgroup spins; the prepared solve's sweeps have
+      if (!step) e.se = bk_solve_ws(s->bkpws.p, s->N).k.ctrl + SOLVE_ERR_WORD;
+      break;
+    case Path::BkBatch: break;  // no cross-workgroup spins; an info word per system (bk_batch_info)
+  }
+  return e;
+}
+
 // sticky error words of every persistent-kernel workspace the step uses
 int qp_status(ipmz_qp* s) {
-  hipStream_t st = s->ctx->stream;
-  if (s->mixed) {
-    const char* text = ": a hand-off inside a persistent kernel of the mixed-precision factor / solve timed out; the "
-                       "step is invalid";
-    return ws_result(st, nullptr, s->mw.pctrl + PANEL_ERR_WORD, s->mw.ctrl + SOLVE_ERR_WORD, "Newton step", text, text);
-  }
-  if (s->normal || (s->B == 1 && !s->eqnone)) {
-    const LdltWs w = s->normal ? normal_ws_of(s).k : ldlt_ws_of(s);
-    return ws_result(st, nullptr, w.pctrl + PANEL_ERR_WORD, w.ctrl + SOLVE_ERR_WORD,
-                     s->normal ? "Newton step (normal equations)" : "Newton step");
-  }
-  // only a step whose factor ran the two-workgroup kernel has a word to read
-  // (that kernel's launch zeroes it; the default wave-specialized factor at
-  // C4's N = 320 has no cross-workgroup hand-off and needs no sync here)
-  if (!s->eqnone && s->ctx->nbi == 64 && small_pair_used(s->small_kernel, s->pflags != nullptr, s->B, s->N))
-    return ws_result(st, nullptr, s->pflags + (size_t)s->B * IPMZ_PAIR_FLAGS, nullptr, "Newton step",
-                     ": a hand-off of the two-workgroup batched factor timed out; the step is invalid");
-  if (s->bkws)  // (the device-wide solve's word only where that solve runs)
-    return ws_result(st, nullptr, bk_grid_err_word(s->bkws, s->N),
-                     s->bkfws ? bk_ws(s->bkfws, s->N).ctrl + SOLVE_ERR_WORD : nullptr, "Newton step",
-                     ": a grid barrier of the whole-device Bunch-Kaufman factor timed out; the step is invalid",
-                     ": a hand-off inside the persistent triangular solve of the Bunch-Kaufman factor timed out; the "
-                     "step is invalid");
-  return IPMZ_OK;  // batched / one-workgroup Bunch-Kaufman kernels have no cross-workgroup spins
+  const ErrWords e = err_words(s, true);
+  if (!e.pe && !e.se) return IPMZ_OK;
+  return ws_result(s->ctx->stream, nullptr, e.pe, e.se, s->normal ? "Newton step (normal equations)" : "Newton step",
+                   e.pe_text, e.se_text);
 }
+
+// the B scalar blocks are one allocation with a stride: bytes between two QPs'
+size_t scal_pitch(const ipmz_qp* s) { return (s->B > 1 ? (s->hq[1].scal - s->hq[0].scal) : SC_COUNT) * 8; }
 
 int scalars_impl(ipmz_qp* s, double* out, int count) {
   HIP_OK(hipSetDevice(s->ctx->device));
-  // the B scalar blocks are one allocation with a stride: one 2-D copy
-  const size_t pitch = (s->B > 1 ? (s->hq[1].scal - s->hq[0].scal) : SC_COUNT) * 8;
-  HIP_OK(hipMemcpy2DAsync(out, SC_COUNT * 8, s->hq[0].scal, pitch, SC_COUNT * 8, count, hipMemcpyDeviceToHost,
+  HIP_OK(hipMemcpy2DAsync(out, SC_COUNT * 8, s->hq[0].scal, scal_pitch(s), SC_COUNT * 8, count, hipMemcpyDeviceToHost,
                           s->ctx->stream));
   HIP_OK(hipStreamSynchronize(s->ctx->stream));
   return s->loaded ? qp_status(s) : IPMZ_OK;
@@ -774,6 +854,40 @@ std::vector<double> state_in(const ipmz_qp* s, const double* in) {
   }
   return v;
 }
+
+// The bodies of the ipmz_qp_* / ipmz_batch_* accessor pairs (arguments checked by the callers).
+// The scalar blocks of the first count QPs to dst (device), dense; asynchronous
+int copy_scalars_impl(ipmz_qp* s, double* dst, int count) {
+  HIP_OK(hipSetDevice(s->ctx->device));
+  hipStream_t st = s->ctx->stream;
+  HIP_OK(count == 1 ? hipMemcpyAsync(dst, s->hq[0].scal, SC_COUNT * 8, hipMemcpyDeviceToDevice, st)
+                    : hipMemcpy2DAsync(dst, SC_COUNT * 8, s->hq[0].scal, scal_pitch(s), SC_COUNT * 8, count,
+                                       hipMemcpyDeviceToDevice, st));
+  return IPMZ_OK;
+}
+// the iterate `in` (host, the reference's order) into QPs [first, last), then every QP evaluated; synchronizes
+int set_state_impl(ipmz_qp* s, int first, int last, const double* in) {
+  HIP_OK(hipSetDevice(s->ctx->device));
+  const std::vector<double> v = state_in(s, in);
+  for (int i = first; i < last; ++i)
+    HIP_OK(hipMemcpyAsync(s->hq[i].v[0], v.data(), s->state_len * 8, hipMemcpyHostToDevice, s->ctx->stream));
+  HIP_OK(qp_evaluate(s->qb, s->ctx->stream));
+  HIP_OK(hipStreamSynchronize(s->ctx->stream));
+  return IPMZ_OK;
+}
+// the assembled KKT matrix of QP i (lower triangle, zeros above) to out (host, N x N)
+int get_kkt_impl(ipmz_qp* s, int i, double* out) {
+  HIP_OK(hipSetDevice(s->ctx->device));
+  hipStream_t st = s->ctx->stream;
+  // (the whole matrix of every QP into K, as the non-fused step's assembly: the kept K0 is not touched)
+  HIP_OK(qp_assemble(s->qb, st));
+  HIP_OK(hipMemcpy2DAsync(out, (size_t)s->N * 8, s->hq[i].K, s->ldk * 8, (size_t)s->N * 8, s->N, hipMemcpyDeviceToHost,
+                          st));
+  HIP_OK(hipStreamSynchronize(st));
+  for (int r = 0; r < s->N; ++r)
+    for (int c = r + 1; c < s->N; ++c) out[(int64_t)r * s->N + c] = 0.0;
+  return IPMZ_OK;
+}
 }  // namespace
 
 extern "C" {
@@ -795,9 +909,7 @@ int ipmz_qp_destroy(ipmz_qp* s) {
     }
     delete[] s->tr_pairs;
   }
-  for (void* p : s->allocs) hipFree(p);
-  if (s->mmws) hipFree(s->mmws);
-  if (s->nmws) hipFree(s->nmws);
+  for (void* p : s->allocs) hipFree(p);  // (the GrowBufs' too)
   if (s->mw.hev) hipEventDestroy(s->mw.hev);
   if (s->mw.hst) hipHostFree(s->mw.hst);
   ipmz_ctx* ctx = s->ctx;
@@ -845,9 +957,7 @@ int ipmz_qp_device_scalars(ipmz_qp* s, double** out) {
 
 int ipmz_qp_copy_scalars(ipmz_qp* s, double* dst) {
   if (!s || !dst) return fail(IPMZ_ERR_INVALID, "null argument");
-  HIP_OK(hipSetDevice(s->ctx->device));
-  HIP_OK(hipMemcpyAsync(dst, s->hq[0].scal, SC_COUNT * 8, hipMemcpyDeviceToDevice, s->ctx->stream));
-  return IPMZ_OK;
+  return copy_scalars_impl(s, dst, 1);  // QP 0
 }
 
 int ipmz_qp_solve(ipmz_qp* s, int max_iter, double* trace, int* iterations) {
@@ -890,45 +1000,23 @@ int ipmz_qp_get_state(ipmz_qp* s, int which, double* out) {
 
 int ipmz_qp_set_state(ipmz_qp* s, const double* in) {
   if (!s || !in) return fail(IPMZ_ERR_INVALID, "bad arguments");
-  HIP_OK(hipSetDevice(s->ctx->device));
-  const std::vector<double> v = state_in(s, in);
-  for (int i = 0; i < s->B; ++i)
-    HIP_OK(hipMemcpyAsync(s->hq[i].v[0], v.data(), s->state_len * 8, hipMemcpyHostToDevice, s->ctx->stream));
-  HIP_OK(qp_evaluate(s->qb, s->ctx->stream));
-  HIP_OK(hipStreamSynchronize(s->ctx->stream));
-  s->loaded = true;
-  return IPMZ_OK;
+  const int rc = set_state_impl(s, 0, s->B, in);  // every QP
+  if (!rc) s->loaded = true;
+  return rc;
 }
 
 int ipmz_qp_kkt_dim(ipmz_qp* s) { return s ? s->N : 0; }
 
 int ipmz_qp_get_kkt(ipmz_qp* s, double* out) {
   if (!s || !out) return fail(IPMZ_ERR_INVALID, "bad arguments");
-  HIP_OK(hipSetDevice(s->ctx->device));
-  hipStream_t st = s->ctx->stream;
-  HIP_OK(qp_assemble(s->qb, st));
-  HIP_OK(hipMemcpy2DAsync(out, (size_t)s->N * 8, s->K, s->ldk * 8, (size_t)s->N * 8, s->N, hipMemcpyDeviceToHost,
-                          st));
-  HIP_OK(hipStreamSynchronize(st));
-  for (int i = 0; i < s->N; ++i)
-    for (int j = i + 1; j < s->N; ++j) out[(int64_t)i * s->N + j] = 0.0;
-  return IPMZ_OK;
+  return get_kkt_impl(s, 0, out);
 }
 
 int ipmz_batch_get_kkt(ipmz_qp* s, int index, double* out) {
   int rc = check_index(s, index);
   if (rc) return rc;
   if (!out) return fail(IPMZ_ERR_INVALID, "bad arguments");
-  HIP_OK(hipSetDevice(s->ctx->device));
-  hipStream_t st = s->ctx->stream;
-  // (the whole matrix of every QP into K, as the non-fused step's assembly: the kept K0 is not touched)
-  HIP_OK(qp_assemble(s->qb, st));
-  HIP_OK(hipMemcpy2DAsync(out, (size_t)s->N * 8, s->hq[index].K, s->ldk * 8, (size_t)s->N * 8, s->N,
-                          hipMemcpyDeviceToHost, st));
-  HIP_OK(hipStreamSynchronize(st));
-  for (int i = 0; i < s->N; ++i)
-    for (int j = i + 1; j < s->N; ++j) out[(int64_t)i * s->N + j] = 0.0;
-  return IPMZ_OK;
+  return get_kkt_impl(s, index, out);
 }
 
 // Batched multi-right-hand-side solve (trsm.hip): which of the three paths
@@ -956,34 +1044,45 @@ static constexpr int BATCH_MULTI_CROSSOVER = 4;
 
 static int batch_multi_impl(ipmz_qp* s, double* B, int64_t ldb, int64_t sB, int nrhs) {
   hipStream_t st = s->ctx->stream;
-  const int dbg = debug_inject_mask(), nbi = s->ctx->nbi;
-  if (nrhs < BATCH_MULTI_CROSSOVER && !(nrhs >= 2 && (dbg & IPMZ_DEBUG_MULTI_BLOCKED))) {
+  const int nbi = s->ctx->nbi;
+  const MultiPlan plan =
+      multi_plan(nrhs, BATCH_MULTI_CROSSOVER, IPMZ_SOLVE_MULTI_PANEL, debug_inject_mask(), MultiKind::Batch);
+  if (!plan.blocked) {
     for (int r = 0; r < nrhs; ++r)
       HIP_OK(ldlt_solve_batched(s->K, s->ldk, s->N, s->D, s->bLinv, nbi, B + (int64_t)r * ldb, s->B, s->sK, s->sD,
                                 s->sL, sB, st));
     return IPMZ_OK;
   }
-  TrsmBatch tb;
-  tb.B = s->B;
-  tb.sK = s->sK;
-  tb.sD = s->sD;
-  tb.sL = s->sL;
-  tb.sB = sB;
+  const TrsmBatch tb = trsm_batch(s, sB);
   // one launch per batch where a system's slab fits a workgroup's LDS, unless
   // a panel width is forced; else the panel chain over all QPs
-  if (!(dbg & (IPMZ_DEBUG_MULTI_W128 | IPMZ_DEBUG_MULTI_W512)) && ldlt_solve_fused_eligible(s->N, nbi)) {
+  if (plan.fused && ldlt_solve_fused_eligible(s->N, nbi)) {
     HIP_OK(ldlt_solve_fused(s->K, s->ldk, s->N, s->D, s->bLinv, nbi, B, ldb, nrhs, st, tb));
     return IPMZ_OK;
   }
-  // (both width bits together: the panel chain at its default width, for tools/batch_multi_bench.py)
-  const bool w512 = dbg & IPMZ_DEBUG_MULTI_W512, w128 = dbg & IPMZ_DEBUG_MULTI_W128;
-  const int pw = w512 && w128 ? IPMZ_SOLVE_MULTI_PANEL : w512 ? 512 : w128 ? 128 : IPMZ_SOLVE_MULTI_PANEL;
-  HIP_OK(ldlt_solve_multi<double>(s->K, s->ldk, s->N, s->D, s->bLinv, nbi, B, ldb, nrhs, pw, st, tb));
+  HIP_OK(ldlt_solve_multi<double>(s->K, s->ldk, s->N, s->D, s->bLinv, nbi, B, ldb, nrhs, plan.width, st, tb));
+  return IPMZ_OK;
+}
+
+// What every call that takes a block of right-hand sides checks first: the data is loaded, and the block `name`
+// -- per QP nrhs rows of len (`len_name`) elements, ld apart, the QPs' blocks sB apart -- is what the blocked
+// kernels' 16-byte loads can address (aligned false: handed on to an entry point with its own alignment rule)
+static int check_rhs_block(const ipmz_qp* s, const std::string& who, int nrhs, const char* name, const void* p,
+                           int64_t ld, int64_t sB, int64_t len, const char* len_name, bool aligned = true) {
+  if (!s->loaded) return fail(IPMZ_ERR_STATE, who + ": load (and initialize) the QP first");
+  if (nrhs < 0 || ld < len || (ld & 1) || (nrhs > 0 && !p) ||
+      (s->B > 1 && (sB < (int64_t)nrhs * ld || (sB & 1))))
+    return fail(IPMZ_ERR_INVALID, who + ": bad arguments (nrhs >= 0; " + name + ": not null, row stride >= " + len_name +
+                                      " and even" + (s->B > 1 ? ", QP stride >= nrhs * row stride and even)" : ")"));
+  if (aligned && nrhs > 0 && ((uintptr_t)p & 15))
+    return fail(IPMZ_ERR_INVALID, who + ": " + name + " must be 16-byte aligned");
+  if (path_of(s) == Path::BkBatch && (s->N > IPMZ_BK_NMAX || s->B > 65535))  // the batched prepared solve's grid
+    return fail(IPMZ_ERR_INVALID, who + ": EqualityHandling::None batches: N <= 4096 and batch <= 65535");
   return IPMZ_OK;
 }
 
 // What the four *_kkt_solve* calls and the two *_newton_solve_multi calls
-// share, by the solver's kind (single or batch, LDL^T or Bunch-Kaufman):
+// share, by the solver's path:
 // kkt_ws_ensure  the Bunch-Kaufman prepared solves' workspace, on first use;
 // kkt_enqueue    the step's own assembly and factor on the storage the next
 //                step overwrites anyway (it assembles and factors again: the
@@ -992,82 +1091,71 @@ static int batch_multi_impl(ipmz_qp* s, double* B, int64_t ldb, int64_t sB, int 
 // kkt_finish     the one synchronize: the sticky error words, then the info
 //                word(s).  info (host, batch ints, may be null) is filled per
 //                QP for Bunch-Kaufman batches only.
-static int kkt_ws_ensure(ipmz_qp* s) {
-  if (!s->eqnone) return IPMZ_OK;
-  // single QPs below IPMZ_BK_GRID_MIN: the steps solve on F itself; batches:
-  // no step uses prepared solves.  Allocated on first use and kept
-  char** slot = s->B == 1 ? &s->bkmws : &s->bkbws;
-  if (*slot || (s->B == 1 && s->bkfws)) return IPMZ_OK;
-  const size_t bytes = s->B == 1 ? (size_t)bk_solve_ws(nullptr, s->N).total : (size_t)bk_batch_ws(nullptr, s->N, s->B).total;
-  void* w = nullptr;
-  if (hipMalloc(&w, bytes) != hipSuccess) {
-    (void)hipGetLastError();
-    return fail(IPMZ_ERR_NOMEM, "device allocation failed");
-  }
-  s->allocs.push_back(w);
-  *slot = static_cast<char*>(w);
-  return IPMZ_OK;
-}
-
-// the persistent solve's sticky error word of a single QP's Bunch-Kaufman path
-static const unsigned* bk_single_se(const ipmz_qp* s) {
-  return (s->bkfws ? bk_ws(s->bkfws, s->N) : bk_solve_ws(s->bkmws, s->N).k).ctrl + SOLVE_ERR_WORD;
+static int kkt_ws_ensure(ipmz_qp* s) {  // (kept: the steps of these two paths solve on F itself)
+  const Path path = path_of(s);
+  if (path == Path::BkSmall) return grow(s, s->bkpws, (size_t)bk_solve_ws(nullptr, s->N).total);
+  if (path == Path::BkBatch) return grow(s, s->bkpws, (size_t)bk_batch_ws(nullptr, s->N, s->B).total);
+  return IPMZ_OK;  // (Path::BkGrid: every step prepares its solve)
 }
 
 static int kkt_enqueue(ipmz_qp* s, double* B, int64_t ldb, int64_t sB, int nrhs) {
   hipStream_t st = s->ctx->stream;
-  int rc;
-  if (s->B == 1 && !s->eqnone) {
-    HIP_OK(qp_assemble(s->qb, st));
-    rc = factor_impl(s->ctx, s->N, s->K, s->ldk, s->D, ldlt_ws_of(s), nbo_for(s->ctx, s->N), nullptr);
-    if (!rc) rc = ipmz_ldlt_solve_multi(s->ctx, s->N, s->K, s->ldk, s->D, s->ws, B, ldb, nrhs);
-    unwatch(s->ctx);  // s->ws is the solver's: checked in kkt_finish, not at a later sync
-    return rc;
-  }
-  if (s->B == 1) {
-    HIP_OK(qp_assemble(s->qb, st));
-    if ((rc = factor_batch(s, nullptr, false))) return rc;
-    if (s->bkfws) {  // factor_batch left LT in bklt, L' in K and the operators in bkfws
-      rc = bk_multi_impl(s->ctx, s->N, s->K, s->ldk, s->ipiv, s->bklt, s->K, s->ldk, bk_ws(s->bkfws, s->N), B, ldb, nrhs);
-    } else {
-      const BkSolveWs w = bk_solve_ws(s->bkmws, s->N);
-      HIP_OK(bk_transpose(s->K, s->ldk, s->N, w.LT, st));
-      HIP_OK(bk_setup(s->K, s->ldk, s->N, s->ipiv, s->binfo, w.LT, w.Lp, w.ldp, w.k, st));
-      rc = bk_multi_impl(s->ctx, s->N, s->K, s->ldk, s->ipiv, w.LT, w.Lp, w.ldp, w.k, B, ldb, nrhs);
-    }
-    unwatch(s->ctx);  // the workspace is the solver's: checked in kkt_finish, not at a later sync
-    return rc;
-  }
-  // batches (no forked step to wait for: step_forks is false for them).  The
-  // whole matrix of every QP goes into K and is factored there in place
+  // The whole matrix of every QP goes into K and is factored there in place
   // (factor_batch without K0), as the non-fused step does.  The fused step's
   // kept matrix K0 -- its off-diagonal part written once per load -- is
   // neither read nor written; that step rewrites K0's diagonal and all of L in
   // K itself.
   HIP_OK(qp_assemble(s->qb, st));
-  if ((rc = factor_batch(s, nullptr, false))) return rc;
-  if (!s->eqnone) return batch_multi_impl(s, B, ldb, sB, nrhs);
-  if (nrhs > 0) {
-    const BkBatchWs w = bk_batch_ws(s->bkbws, s->N, s->B);
-    if ((rc = bk_batch_prepare(s->ctx, s->N, s->B, s->K, s->ldk, s->sK, s->ipiv, s->sP, s->binfo, w))) return rc;
-    if ((rc = bk_batch_multi_impl(s->ctx, s->N, s->B, s->K, s->ldk, s->sK, s->ipiv, s->sP, w, B, ldb, sB, nrhs)))
-      return rc;
+  int rc = factor_batch(s, nullptr, false);
+  if (rc) return rc;
+  switch (path_of(s)) {
+    case Path::Ldlt:
+      rc = ipmz_ldlt_solve_multi(s->ctx, s->N, s->K, s->ldk, s->D, s->ws, B, ldb, nrhs);
+      break;
+    case Path::LdltBatch: return batch_multi_impl(s, B, ldb, sB, nrhs);
+    case Path::BkGrid:  // factor_batch left LT in bklt, L' in K and the operators in bkfws
+      rc = bk_multi_impl(s->ctx, s->N, s->K, s->ldk, s->ipiv, s->bklt, s->K, s->ldk, bk_ws(s->bkfws, s->N), B, ldb, nrhs);
+      break;
+    case Path::BkSmall: {
+      const BkSolveWs w = bk_solve_ws(s->bkpws.p, s->N);
+      HIP_OK(bk_transpose(s->K, s->ldk, s->N, w.LT, st));
+      HIP_OK(bk_setup(s->K, s->ldk, s->N, s->ipiv, s->binfo, w.LT, w.Lp, w.ldp, w.k, st));
+      rc = bk_multi_impl(s->ctx, s->N, s->K, s->ldk, s->ipiv, w.LT, w.Lp, w.ldp, w.k, B, ldb, nrhs);
+      break;
+    }
+    case Path::BkBatch: {
+      if (nrhs == 0) return IPMZ_OK;
+      const BkBatchWs w = bk_batch_ws(s->bkpws.p, s->N, s->B);
+      if ((rc = bk_batch_prepare(s->ctx, s->N, s->B, s->K, s->ldk, s->sK, s->ipiv, s->sP, s->binfo, w))) return rc;
+      return bk_batch_multi_impl(s->ctx, s->N, s->B, s->K, s->ldk, s->sK, s->ipiv, s->sP, w, B, ldb, sB, nrhs);
+    }
+    default: break;  // (Path::Normal, Path::Mixed: rejected by every caller)
   }
-  return IPMZ_OK;
+  unwatch(s->ctx);  // the single paths' workspace is the solver's: checked in kkt_finish, not at a later sync
+  return rc;
 }
 
 static int kkt_finish(ipmz_qp* s, const char* what, int* info) {
-  hipStream_t st = s->ctx->stream;
-  if (s->B == 1 && !s->eqnone) return read_info(s->ctx, ldlt_ws_of(s));  // checks the error words of s->ws itself
-  if (s->B == 1)
-    return ws_result(st, s->binfo, s->bkws ? bk_grid_err_word(s->bkws, s->N) : nullptr, bk_single_se(s), what,
-                     ": a grid barrier of the whole-device Bunch-Kaufman factor timed out; the factor is invalid");
-  if (s->eqnone) return bk_batch_info(st, s->binfo, s->B, info);
-  // the info word, and the sticky error word of the two-workgroup factor where
-  // it ran (qp_status's rule)
-  const bool pair = s->ctx->nbi == 64 && small_pair_used(s->small_kernel, s->pflags != nullptr, s->B, s->N);
-  return ws_result(st, s->binfo, pair ? s->pflags + (size_t)s->B * IPMZ_PAIR_FLAGS : nullptr, nullptr, what,
-                   ": a hand-off of the two-workgroup batched factor timed out; the factor is invalid");
+  const Path path = path_of(s);
+  if (path == Path::Ldlt) return read_info(s->ctx, ldlt_ws_of(s));  // checks the error words of s->ws itself
+  if (path == Path::BkBatch) return bk_batch_info(s->ctx->stream, s->binfo, s->B, info);
+  const ErrWords e = err_words(s, false);
+  return ws_result(s->ctx->stream, e.info, e.pe, e.se, what, e.pe_text, e.se_text);
+}
+
+// the four *_kkt_solve* calls behind their own checks of the solver's path
+static int kkt_solve(ipmz_qp* s, const char* who, int nrhs, double* B, int64_t ldb, int64_t sB, int* info) {
+  const Path path = path_of(s);
+  // (Path::Ldlt hands B on to ipmz_ldlt_solve_multi: its alignment rule, K and B from 2 rows on)
+  int rc = check_rhs_block(s, who, nrhs, "B", B, ldb, sB, s->N, "N", path != Path::Ldlt);
+  if (rc) return rc;
+  HIP_OK(hipSetDevice(s->ctx->device));
+  // (as the four stood before they shared this body: the batch calls check for a capture, _qp_kkt_solve_bk waits)
+  if (s->B > 1 && (rc = not_capturing(s->ctx, who))) return rc;
+  if ((path == Path::BkGrid || path == Path::BkSmall) && (rc = wait_pending_step(s))) return rc;
+  if ((rc = kkt_ws_ensure(s))) return rc;
+  if ((rc = kkt_enqueue(s, B, ldb, sB, nrhs))) return rc;
+  return kkt_finish(s, who, info);  // synchronizes
 }
 
 int ipmz_batch_kkt_solve(ipmz_qp* s, int nrhs, double* B, int64_t ldb, int64_t sB) {
@@ -1076,18 +1164,7 @@ int ipmz_batch_kkt_solve(ipmz_qp* s, int nrhs, double* B, int64_t ldb, int64_t s
   if (s->eqnone)
     return fail(IPMZ_ERR_INVALID, "ipmz_batch_kkt_solve: EqualityHandling::None batches factor with Bunch-Kaufman, "
                                   "which has no batched multi-right-hand-side solve (fp64 LDL^T batches only)");
-  if (s->normal || s->mixed)
-    return fail(IPMZ_ERR_INVALID, "ipmz_batch_kkt_solve: fp64 augmented LDL^T batches only");
-  if (!s->loaded) return fail(IPMZ_ERR_STATE, "ipmz_batch_kkt_solve: load and initialize the batch first");
-  if (nrhs < 0 || ldb < s->N || (ldb & 1) || sB < (int64_t)nrhs * ldb || (sB & 1) || (nrhs > 0 && !B))
-    return fail(IPMZ_ERR_INVALID, "ipmz_batch_kkt_solve: bad arguments (nrhs >= 0, ldb >= N and even, sB >= nrhs * "
-                                  "ldb and even)");
-  if (nrhs > 0 && ((uintptr_t)B & 15)) return fail(IPMZ_ERR_INVALID, "ipmz_batch_kkt_solve: B must be 16-byte aligned");
-  HIP_OK(hipSetDevice(s->ctx->device));
-  int rc = not_capturing(s->ctx, "ipmz_batch_kkt_solve");
-  if (rc) return rc;
-  if ((rc = kkt_enqueue(s, B, ldb, sB, nrhs))) return rc;
-  return kkt_finish(s, "ipmz_batch_kkt_solve", nullptr);  // synchronizes
+  return kkt_solve(s, "ipmz_batch_kkt_solve", nrhs, B, ldb, sB, nullptr);
 }
 
 int ipmz_batch_kkt_solve_bk(ipmz_qp* s, int nrhs, double* B, int64_t ldb, int64_t sB, int* info) {
@@ -1097,23 +1174,10 @@ int ipmz_batch_kkt_solve_bk(ipmz_qp* s, int nrhs, double* B, int64_t ldb, int64_
     if (info) info[0] = rc;
     return rc;
   }
-  if (!s->eqnone || s->normal || s->mixed)
+  if (!s->eqnone)
     return fail(IPMZ_ERR_INVALID, "ipmz_batch_kkt_solve_bk: EqualityHandling::None batches only (the Bunch-Kaufman "
                                   "factor); the LDL^T handlings solve with ipmz_batch_kkt_solve");
-  if (!s->loaded) return fail(IPMZ_ERR_STATE, "ipmz_batch_kkt_solve_bk: load and initialize the batch first");
-  if (nrhs < 0 || ldb < s->N || (ldb & 1) || sB < (int64_t)nrhs * ldb || (sB & 1) || (nrhs > 0 && !B))
-    return fail(IPMZ_ERR_INVALID, "ipmz_batch_kkt_solve_bk: bad arguments (nrhs >= 0, ldb >= N and even, sB >= nrhs "
-                                  "* ldb and even)");
-  if (nrhs > 0 && ((uintptr_t)B & 15))
-    return fail(IPMZ_ERR_INVALID, "ipmz_batch_kkt_solve_bk: B must be 16-byte aligned");
-  if (s->N > IPMZ_BK_NMAX || s->B > 65535)
-    return fail(IPMZ_ERR_INVALID, "ipmz_batch_kkt_solve_bk: N <= 4096 and batch <= 65535");
-  HIP_OK(hipSetDevice(s->ctx->device));
-  int rc = not_capturing(s->ctx, "ipmz_batch_kkt_solve_bk");
-  if (rc) return rc;
-  if ((rc = kkt_ws_ensure(s))) return rc;
-  if ((rc = kkt_enqueue(s, B, ldb, sB, nrhs))) return rc;
-  return kkt_finish(s, "ipmz_batch_kkt_solve_bk", info);  // synchronizes
+  return kkt_solve(s, "ipmz_batch_kkt_solve_bk", nrhs, B, ldb, sB, info);
 }
 
 int ipmz_qp_kkt_solve(ipmz_qp* s, int nrhs, double* B, int64_t ldb) {
@@ -1127,13 +1191,7 @@ int ipmz_qp_kkt_solve(ipmz_qp* s, int nrhs, double* B, int64_t ldb) {
     return fail(IPMZ_ERR_INVALID, "ipmz_qp_kkt_solve: the normal-equations reduction is enabled (augmented LDL^T only)");
   if (s->mixed)
     return fail(IPMZ_ERR_INVALID, "ipmz_qp_kkt_solve: mixed precision is enabled (fp64 LDL^T only)");
-  if (!s->loaded) return fail(IPMZ_ERR_STATE, "load or generate the QP first");
-  if (nrhs < 0 || ldb < s->N || (ldb & 1) || (nrhs > 0 && !B))
-    return fail(IPMZ_ERR_INVALID, "ipmz_qp_kkt_solve: bad arguments (nrhs >= 0, ldb >= N and even)");
-  HIP_OK(hipSetDevice(s->ctx->device));
-  const int rc = kkt_enqueue(s, B, ldb, 0, nrhs);
-  if (rc) return rc;
-  return kkt_finish(s, "ipmz_qp_kkt_solve", nullptr);  // synchronizes
+  return kkt_solve(s, "ipmz_qp_kkt_solve", nrhs, B, ldb, 0, nullptr);
 }
 
 int ipmz_qp_kkt_solve_bk(ipmz_qp* s, int nrhs, double* B, int64_t ldb) {
@@ -1142,21 +1200,7 @@ int ipmz_qp_kkt_solve_bk(ipmz_qp* s, int nrhs, double* B, int64_t ldb) {
   if (!s->eqnone)
     return fail(IPMZ_ERR_INVALID, "ipmz_qp_kkt_solve_bk: EqualityHandling::None only (the Bunch-Kaufman factor); "
                                   "the LDL^T handlings solve with ipmz_qp_kkt_solve");
-  if (s->normal) return fail(IPMZ_ERR_INVALID, "ipmz_qp_kkt_solve_bk: the normal-equations reduction is enabled");
-  if (s->mixed) return fail(IPMZ_ERR_INVALID, "ipmz_qp_kkt_solve_bk: mixed precision is enabled");
-  if (!s->loaded) return fail(IPMZ_ERR_STATE, "load or generate the QP first");
-  if (nrhs < 0 || ldb < s->N || (ldb & 1) || (nrhs > 0 && !B))
-    return fail(IPMZ_ERR_INVALID, "ipmz_qp_kkt_solve_bk: bad arguments (nrhs >= 0, ldb >= N and even)");
-  if (nrhs > 0 && ((uintptr_t)B & 15)) return fail(IPMZ_ERR_INVALID, "ipmz_qp_kkt_solve_bk: B must be 16-byte aligned");
-  HIP_OK(hipSetDevice(s->ctx->device));
-  if (s->step_pending) {  // a forked step still in flight reads the storage factored below
-    HIP_OK(hipEventSynchronize(s->step_done));
-    s->step_pending = false;
-  }
-  int rc = kkt_ws_ensure(s);
-  if (rc) return rc;
-  if ((rc = kkt_enqueue(s, B, ldb, 0, nrhs))) return rc;
-  return kkt_finish(s, "ipmz_qp_kkt_solve_bk", nullptr);  // synchronizes
+  return kkt_solve(s, "ipmz_qp_kkt_solve_bk", nrhs, B, ldb, 0, nullptr);
 }
 
 // compute_search_direction_ for a block of residual vectors: rhs_elem's
@@ -1171,43 +1215,21 @@ static int newton_multi(ipmz_qp* s, const char* who, int nrhs, const double* R, 
   if (s->eqss)
     return fail(IPMZ_ERR_INVALID, w + ": EqualityHandling::SlackedSlacks / NaiveSlacks keep a permuted, merged view of "
                                       "the Newton order on the device; not served");
-  if (!s->loaded) return fail(IPMZ_ERR_STATE, w + ": load (and initialize) the QP first");
-  const int64_t L = s->state_len;
-  if (nrhs < 0 || ldr < L || ldd < L || (ldr & 1) || (ldd & 1) || (nrhs > 0 && (!R || !Dir)))
-    return fail(IPMZ_ERR_INVALID, w + ": bad arguments (nrhs >= 0, ldr >= state_len, ldd >= state_len, both even)");
-  if (s->B > 1 && (sR < (int64_t)nrhs * ldr || sD < (int64_t)nrhs * ldd || (sR & 1) || (sD & 1)))
-    return fail(IPMZ_ERR_INVALID, w + ": bad arguments (sR >= nrhs * ldr, sD >= nrhs * ldd, both even)");
-  if (nrhs > 0 && (((uintptr_t)R & 15) || ((uintptr_t)Dir & 15)))
-    return fail(IPMZ_ERR_INVALID, w + ": R and Dir must be 16-byte aligned");
-  if (s->eqnone && s->B > 1 && (s->N > IPMZ_BK_NMAX || s->B > 65535))
-    return fail(IPMZ_ERR_INVALID, w + ": EqualityHandling::None batches: N <= 4096 and batch <= 65535");
-  HIP_OK(hipSetDevice(s->ctx->device));
-  int rc = not_capturing(s->ctx, who);
+  int rc = check_rhs_block(s, w, nrhs, "R", R, ldr, sR, s->state_len, "state_len");
+  if (!rc) rc = check_rhs_block(s, w, nrhs, "Dir", Dir, ldd, sD, s->state_len, "state_len");
   if (rc) return rc;
-  if (s->step_pending) {  // a forked step still in flight reads the storage factored below
-    HIP_OK(hipEventSynchronize(s->step_done));
-    s->step_pending = false;
-  }
+  HIP_OK(hipSetDevice(s->ctx->device));
+  if ((rc = not_capturing(s->ctx, who))) return rc;
+  if ((rc = wait_pending_step(s))) return rc;
   if ((rc = kkt_ws_ensure(s))) return rc;
   // the reduced right-hand sides: not Dir itself (the solves see rows of this
   // stride whatever ldd is, and nothing relies on the head of a Newton-order
   // row being the KKT order).  Every call ends synchronized, so growing it
   // here is safe
   const int64_t ldw = round_up(s->N, 2), sW = (int64_t)nrhs * ldw;
-  if (nrhs > s->nmws_nrhs) {
-    if (s->nmws) hipFree(s->nmws);
-    s->nmws = nullptr;
-    s->nmws_nrhs = 0;
-    void* p = nullptr;
-    if (hipMalloc(&p, (size_t)(sW * s->B) * sizeof(double)) != hipSuccess) {
-      (void)hipGetLastError();
-      return fail(IPMZ_ERR_NOMEM, "device allocation failed");
-    }
-    s->nmws = static_cast<double*>(p);
-    s->nmws_nrhs = nrhs;
-  }
+  if ((rc = grow(s, s->nmws, (size_t)(sW * s->B) * sizeof(double)))) return rc;
   hipStream_t st = s->ctx->stream;
-  double* W = s->nmws;
+  double* W = reinterpret_cast<double*>(s->nmws.p);
   if (nrhs > 0) HIP_OK(qp_rhs_multi(s->qb, R, ldr, sR, W, ldw, sW, nrhs, st));
   if ((rc = kkt_enqueue(s, W, ldw, sW, nrhs))) return rc;
   if (nrhs > 0) {
@@ -1215,7 +1237,7 @@ static int newton_multi(ipmz_qp* s, const char* who, int nrhs, const double* R, 
     if (alpha) HIP_OK(qp_ratio_multi(s->qb, Dir, ldd, sD, alpha, nrhs, st));
   }
   rc = kkt_finish(s, who, info);  // synchronizes
-  if (info && !(s->eqnone && s->B > 1))
+  if (info && path_of(s) != Path::BkBatch)
     for (int q = 0; q < s->B; ++q) info[q] = rc;
   return rc;
 }
@@ -1242,33 +1264,23 @@ int ipmz_batch_newton_solve_multi(ipmz_qp* s, int nrhs, const double* R, int64_t
 
 // the QP's mixed-precision workspace, allocated once (a captured step keeps its addresses)
 static int ensure_mixed_ws(ipmz_qp* s) {
-  if (s->mws) return IPMZ_OK;
-  // all of it is acquired before any of it is stored in s: a failure leaves
-  // s->mws null, and the next call tries again
+  if (s->mw.hst) return IPMZ_OK;
+  // s->mw is filled last: a failure leaves mw.hst null, and the next call tries again (with the mws it has)
   const int nbo = nbo_for(s->ctx, s->N);
-  const int64_t bytes = mixed_ws_bytes(s->N, nbo);
-  void *w = nullptr, *h = nullptr, *hd = nullptr;
+  const int rc = grow(s, s->mws, (size_t)mixed_ws_bytes(s->N, nbo), true);  // zeroed: sticky error words start clear
+  if (rc) return rc;
+  void *h = nullptr, *hd = nullptr;
   hipEvent_t hev = nullptr;
-  int rc = IPMZ_OK;
-  if (hipMalloc(&w, (size_t)bytes) != hipSuccess) rc = fail(IPMZ_ERR_NOMEM, "device allocation failed");
   // the stop test's host-mapped word (eager solves wait on it)
-  else if (hipHostMalloc(&h, 64, hipHostMallocMapped | hipHostMallocCoherent) != hipSuccess)
-    rc = fail(IPMZ_ERR_NOMEM, "host allocation failed");
-  else {
-    hipError_t e = hipMemset(w, 0, (size_t)bytes);  // sticky error words start clear
-    if (e == hipSuccess) e = hipHostGetDevicePointer(&hd, h, 0);
-    if (e == hipSuccess) e = hipEventCreateWithFlags(&hev, hipEventDisableTiming);
-    if (e != hipSuccess) rc = hip_fail(e, "ensure_mixed_ws", __FILE__, __LINE__);
+  if (hipHostMalloc(&h, 64, hipHostMallocMapped | hipHostMallocCoherent) != hipSuccess)
+    return fail(IPMZ_ERR_NOMEM, "host allocation failed");
+  hipError_t e = hipHostGetDevicePointer(&hd, h, 0);
+  if (e == hipSuccess) e = hipEventCreateWithFlags(&hev, hipEventDisableTiming);
+  if (e != hipSuccess) {
+    hipHostFree(h);
+    return hip_fail(e, "ensure_mixed_ws", __FILE__, __LINE__);
   }
-  if (rc) {
-    if (hev) hipEventDestroy(hev);
-    if (h) hipHostFree(h);
-    hipFree(w);
-    return rc;
-  }
-  s->allocs.push_back(w);
-  s->mws = static_cast<char*>(w);
-  mixed_ws_carve(s->mws, s->N, nbo, s->mw);
+  mixed_ws_carve(s->mws.p, s->N, nbo, s->mw);
   s->mw.hst = static_cast<unsigned*>(h);
   s->mw.hst[0] = s->mw.hst[1] = 0u;
   s->mw.hst_dev = static_cast<unsigned*>(hd);
@@ -1288,33 +1300,19 @@ int ipmz_qp_kkt_solve_mixed(ipmz_qp* s, int nrhs, double* B, int64_t ldb, double
   if (s->normal)
     return fail(IPMZ_ERR_INVALID, "ipmz_qp_kkt_solve_mixed: the normal-equations reduction is enabled (augmented "
                                   "system only)");
-  if (!s->loaded) return fail(IPMZ_ERR_STATE, "load or generate the QP first");
-  if (nrhs < 0 || max_refine < 0 || ldb < s->N || (ldb & 1) || (nrhs > 0 && !B))
-    return fail(IPMZ_ERR_INVALID, "ipmz_qp_kkt_solve_mixed: bad arguments (nrhs >= 0, max_refine >= 0, ldb >= N and "
-                                  "even)");
-  if (nrhs > 0 && ((uintptr_t)B & 15)) return fail(IPMZ_ERR_INVALID, "ipmz_qp_kkt_solve_mixed: B must be 16-byte aligned");
+  int rc = check_rhs_block(s, "ipmz_qp_kkt_solve_mixed", nrhs, "B", B, ldb, 0, s->N, "N");
+  if (rc) return rc;
+  if (max_refine < 0) return fail(IPMZ_ERR_INVALID, "ipmz_qp_kkt_solve_mixed: bad arguments (max_refine >= 0)");
   ipmz_ctx* ctx = s->ctx;
   HIP_OK(hipSetDevice(ctx->device));
-  int rc = not_capturing(ctx, "ipmz_qp_kkt_solve_mixed");
-  if (rc) return rc;
-  if (s->step_pending) {  // a forked step still in flight uses the event pool the factor below takes
-    HIP_OK(hipEventSynchronize(s->step_done));
-    s->step_pending = false;
-  }
+  if ((rc = not_capturing(ctx, "ipmz_qp_kkt_solve_mixed"))) return rc;
+  if ((rc = wait_pending_step(s))) return rc;
   if ((rc = ensure_mixed_ws(s))) return rc;
   const int cap = std::max(nrhs, 1);
-  if (cap > s->mmws_nrhs) {
-    HIP_OK(hipStreamSynchronize(ctx->stream));
-    if (s->mmws) hipFree(s->mmws);
-    s->mmws = nullptr;
-    s->mmws_nrhs = 0;
-    MixedMultiWs m;
-    void* p = nullptr;
-    if (hipMalloc(&p, (size_t)mixed_multi_ws_carve(nullptr, s->N, cap, m)) != hipSuccess)
-      return fail(IPMZ_ERR_NOMEM, "device allocation failed");
-    s->mmws = static_cast<char*>(p);
-    s->mmws_nrhs = cap;
-  }
+  MixedMultiWs m;
+  const size_t mbytes = (size_t)mixed_multi_ws_carve(nullptr, s->N, cap, m);
+  if (mbytes > s->mmws.bytes) HIP_OK(hipStreamSynchronize(ctx->stream));  // earlier solves may still read the old one
+  if ((rc = grow(s, s->mmws, mbytes))) return rc;
   // the step's own assembly, and the fp32 factor in the workspace a mixed step
   // factors into again before it solves: the iterate is only read
   hipStream_t st = ctx->stream;
@@ -1324,8 +1322,7 @@ int ipmz_qp_kkt_solve_mixed(ipmz_qp* s, int nrhs, double* B, int64_t ldb, double
   w.hst_dev = nullptr;
   w.hev = nullptr;
   if ((rc = mixed_factor_impl(ctx, s->K, s->ldk, w, nullptr))) return rc;
-  MixedMultiWs m;
-  mixed_multi_ws_carve(s->mmws, s->N, cap, m);
+  mixed_multi_ws_carve(s->mmws.p, s->N, cap, m);
   if (nrhs == 1) {
     HIP_OK(mixed_solve(s->K, s->ldk, w, B, tol, max_refine, st));
     HIP_OK(hipMemcpyAsync(m.stat, w.stat, 2 * sizeof(double), hipMemcpyDeviceToDevice, st));
@@ -1363,14 +1360,9 @@ int ipmz_qp_set_reduction(ipmz_qp* s, int reduction) {
   if (reduction == IPMZ_REDUCTION_NORMAL && (s->B != 1 || s->mixed || s->eqnone || s->eqpen || s->naive))
     return fail(IPMZ_ERR_INVALID, "normal equations: single QPs, not with mixed precision, Regularization equalities");
   HIP_OK(hipSetDevice(s->ctx->device));
-  if (reduction == IPMZ_REDUCTION_NORMAL && !s->nws) {
-    const int64_t bytes = normal_ws_of(s).total;  // (s->nws is null: sizes only; no NaiveSlacks here, N = n + m + p)
-    void* w = nullptr;
-    if (hipMalloc(&w, (size_t)bytes) != hipSuccess) return fail(IPMZ_ERR_NOMEM, "device allocation failed");
-    s->allocs.push_back(w);
-    HIP_OK(hipMemset(w, 0, (size_t)bytes));  // sticky error words start clear
-    s->nws = static_cast<char*>(w);
-  }
+  // (s->nws empty: normal_ws_of gives sizes only; no NaiveSlacks here, N = n + m + p.  Zeroed: sticky error words)
+  if (reduction == IPMZ_REDUCTION_NORMAL && !s->nws.p && grow(s, s->nws, (size_t)normal_ws_of(s).total, true))
+    return IPMZ_ERR_NOMEM;
   s->normal = reduction == IPMZ_REDUCTION_NORMAL;
   drop_graph(s);
   return IPMZ_OK;
@@ -1437,20 +1429,11 @@ int ipmz_batch_set_state(ipmz_qp* s, int index, const double* in) {
   int rc = check_index(s, index);
   if (rc) return rc;
   if (!in) return fail(IPMZ_ERR_INVALID, "null state");
-  HIP_OK(hipSetDevice(s->ctx->device));
-  const std::vector<double> v = state_in(s, in);
-  HIP_OK(hipMemcpyAsync(s->hq[index].v[0], v.data(), s->state_len * 8, hipMemcpyHostToDevice, s->ctx->stream));
-  HIP_OK(qp_evaluate(s->qb, s->ctx->stream));
-  HIP_OK(hipStreamSynchronize(s->ctx->stream));
-  return IPMZ_OK;
+  return set_state_impl(s, index, index + 1, in);
 }
 int ipmz_batch_copy_scalars(ipmz_qp* s, double* dst) {
   if (!s || !dst) return fail(IPMZ_ERR_INVALID, "null argument");
-  HIP_OK(hipSetDevice(s->ctx->device));
-  // the B scalar blocks are one allocation with a stride of SC_COUNT doubles
-  HIP_OK(hipMemcpy2DAsync(dst, SC_COUNT * 8, s->hq[0].scal, (s->B > 1 ? (s->hq[1].scal - s->hq[0].scal) : SC_COUNT) * 8,
-                          SC_COUNT * 8, s->B, hipMemcpyDeviceToDevice, s->ctx->stream));
-  return IPMZ_OK;
+  return copy_scalars_impl(s, dst, s->B);
 }
 int ipmz_batch_summary(ipmz_qp* s, double* dst) {
   if (!s || !dst) return fail(IPMZ_ERR_INVALID, "null argument");
