@@ -39,6 +39,11 @@
  *                                  solve for a batch of systems of one order (N <= 4096) on
  *                                  caller-owned storage, and ipmz_qp_kkt_solve_bk for every
  *                                  QP of an IPMZ_EQ_NONE batch at once
+ *   ipmz_batch_load_device, ipmz_batch_copy_state
+ *                               <- no reference counterpart: build_environment for a whole
+ *                                  batch from device memory (strided blocks, shared or per
+ *                                  QP, validated and copied by kernels), and the state of
+ *                                  every QP in the reference's Newton order to device memory
  *   ipmz_qp_create + ipmz_qp_load_host
  *                               <- NumericalOptimization::build_environment
  *                                  (EnvironmentBuilder.h:19-20, EnvironmentBuilder.cpp:7-76)
@@ -529,6 +534,77 @@ int ipmz_batch_initialize(ipmz_qp* qp);
 int ipmz_batch_scalars(ipmz_qp* qp, double* out);
 int ipmz_batch_get_state(ipmz_qp* qp, int index, int which, double* host_out);
 int ipmz_batch_set_state(ipmz_qp* qp, int index, const double* host_vars);
+/* The whole batch loaded from device memory, and its states read back to
+ * device memory: neither the data nor the answers pass through the host, and
+ * no call is made per QP.
+ *
+ * ipmz_qp_device_data describes the data of every QP as strided blocks of
+ * doubles on the context's device.  Matrices are row-major with a row stride
+ * (ldq, lda, ldc >= n) and a QP stride; vectors have a QP stride; strides are
+ * in elements.  QP q's block starts q * (QP stride) elements after the
+ * pointer, and a QP stride of 0 is ONE block shared by every QP (parametric
+ * QPs with a common Q / A / C).  A non-zero QP stride is at least the block's
+ * extent ((rows - 1) * row stride + n, or the vector's length); no stride is
+ * negative.  There is no alignment rule: blocks whose pointer is 16-byte
+ * aligned and whose strides are even are copied with 16-byte accesses, the
+ * others element by element, with equal results.  Elements outside the blocks
+ * (row padding, the space between QPs) are never read.  A NULL block keeps
+ * the data the solver already holds; blocks of dimension 0 (A, l_A, u_A with
+ * m == 0; C, d with p == 0) are ignored whatever they hold. */
+typedef struct ipmz_qp_device_data {
+  const double* Q;    /* n rows of n */
+  int64_t ldq, sQ;
+  const double* A;    /* m rows of n */
+  int64_t lda, sA;
+  const double* C;    /* p rows of n */
+  int64_t ldc, sC;
+  const double *c, *l_x, *u_x; /* n each */
+  int64_t sc, slx, sux;
+  const double *l_A, *u_A;     /* m each */
+  int64_t slA, suA;
+  const double* d;    /* p */
+  int64_t sd;
+} ipmz_qp_device_data;
+/* Load every QP of the solver (a solver of ipmz_qp_create is a batch of one)
+ * from `data`, then do what ipmz_batch_initialize does: a fresh iterate, the
+ * kept KKT matrix and the residuals rebuilt from the data the solver now
+ * holds -- the supplied blocks merged with the kept ones (the parametric
+ * re-load: e.g. c and d only); the scalar blocks restart too, so that the
+ * solver equals a new one loaded with the merged data.  On the context's stream, in this order: the
+ * bound check (one kernel), one synchronize for its verdict, the copy
+ * kernels, the initialization (which synchronizes).  The caller orders
+ * whatever produced the input blocks before the context's stream (the same
+ * stream, an event, or a synchronize); the blocks are no longer read once the
+ * call returns.
+ *
+ * build_environment's validation, over every QP: !(l_x[k] < u_x[k]) and
+ * !(l_A[k] <= u_A[k]) are violations (a NaN therefore is one), for the bound
+ * pairs of which the call supplies at least one side -- the other side is then
+ * the one the solver holds.  A violation returns IPMZ_ERR_INVALID with a
+ * message naming the QP, the bound and the index of the first one in the order
+ * (QP, l_x before l_A, index), whatever the kernel's schedule; NOTHING is
+ * written: the data, the iterate and the loaded state stay as they were and
+ * the solver steps on as if the call had not been made.
+ *
+ * IPMZ_ERR_INVALID also for a null qp or data, a row stride < n, a negative
+ * stride, a non-zero QP stride below the block's extent (batches only).
+ * IPMZ_ERR_STATE for a NULL block of non-zero dimension that the solver has
+ * never held for every QP (held: filled by an earlier device load, by
+ * ipmz_qp_load_host, by ipmz_batch_load_host of every QP, or by
+ * ipmz_qp_generate), and while the context's stream is capturing (the call
+ * synchronizes).  A step graph captured earlier (IPMZ_STEP_GRAPH) stays valid:
+ * it holds addresses and the kernel selection, which a load does not change. */
+int ipmz_batch_load_device(ipmz_qp* qp, const ipmz_qp_device_data* data);
+/* ipmz_batch_get_state of every QP at once, to device memory: row q of dst
+ * (device, at dst + q * ld, ld >= ipmz_qp_state_len) receives exactly the
+ * ipmz_qp_state_len doubles ipmz_batch_get_state(qp, q, which, ..) returns --
+ * the reference's Newton order, for IPMZ_EQ_SLACKED_SLACKS / IPMZ_EQ_NAIVE_SLACKS
+ * the same permutation of the step's merged slots, applied by the kernel.
+ * dst[q][state_len .. ld) is never written.  One launch on the context's
+ * stream: asynchronous, no allocation, no synchronize, so it may be enqueued
+ * into a caller's graph capture.  IPMZ_ERR_INVALID for a bad `which`, a null
+ * dst or ld < state_len; IPMZ_ERR_STATE before a load. */
+int ipmz_batch_copy_state(ipmz_qp* qp, int which, double* dst_device, int64_t ld);
 /* Enqueue a device-to-device copy of all batch * IPMZ_SC_COUNT scalars
  * (QP-major) to dst (device): the input of the cross-GPU convergence summary. */
 int ipmz_batch_copy_scalars(ipmz_qp* qp, double* dst_device);
@@ -675,8 +751,8 @@ int ipmz_batch_kkt_solve_bk(ipmz_qp* qp, int nrhs, double* B, int64_t ldb, int64
  *
  * IPMZ_ERR_INVALID: an enabled normal-equations reduction or mixed precision;
  * IPMZ_EQ_SLACKED_SLACKS / IPMZ_EQ_NAIVE_SLACKS (their public state is a
- * permuted, merged view of the step's slots; the device permutation this call
- * would need is a follow-up); bad strides or alignment; IPMZ_EQ_NONE batches
+ * permuted, merged view of the step's slots; ipmz_batch_copy_state applies that
+ * permutation on the device, this call does not yet); bad strides or alignment; IPMZ_EQ_NONE batches
  * with N > 4096.  IPMZ_ERR_STATE before a load, between a load and
  * ipmz_batch_initialize, and while the context's stream is capturing. */
 int ipmz_qp_newton_solve_multi(ipmz_qp* qp, int nrhs, const double* R, int64_t ldr, double* Dir, int64_t ldd,

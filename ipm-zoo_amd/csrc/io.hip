@@ -1,0 +1,220 @@
+// Whole batches in and out of a solver without a trip through host memory
+// (ipmz_batch_load_device, ipmz_batch_copy_state): build_environment's bound
+// check over every QP of a caller's strided device blocks, the copy of those
+// blocks into the storage the QPDev descriptors name, and the state vectors
+// of every QP into the rows of one matrix in the reference's Newton order.
+//
+// All three are plain loads and stores, HBM-bound.  The QP index is a looped
+// grid dimension (any batch size), every offset is 64-bit, and consecutive
+// threads take consecutive elements of a row.
+#include <climits>
+
+#include "common.h"
+#include "kernels.h"
+
+namespace ipmz {
+
+namespace {
+constexpr int NT = 256;
+
+// a grid of at most ~4096 workgroups: x over one QP's `per` work items (grid-stride), y over the QPs (looped)
+dim3 io_grid(int64_t per, int B) {
+  int64_t gx = (per + NT - 1) / NT;
+  gx = gx < 1 ? 1 : gx > 2048 ? 2048 : gx;
+  int64_t gy = 4096 / gx;
+  gy = gy < 1 ? 1 : gy > B ? B : gy;
+  return dim3((unsigned)gx, (unsigned)gy);
+}
+
+__device__ __forceinline__ unsigned long long wave_min_u64(unsigned long long v) {
+  for (int off = 32; off > 0; off >>= 1) {
+    const unsigned long long o = __shfl_xor(v, off, 64);
+    v = o < v ? o : v;
+  }
+  return v;
+}
+}  // namespace
+
+// ---------------------------------------------------------------------------
+// EnvironmentBuilder.cpp:12-17 over the batch: item k < n of QP z is the pair
+// (l_x[k], u_x[k]), item n + k the pair (l_A[k], u_A[k]).  A side the caller
+// does not supply is the one the solver holds; a pair with neither side
+// supplied is not an item (nx / na = 0).  The smallest key of a violated item
+// wins whatever the schedule: one atomicMin per wave that saw one.
+__global__ void __launch_bounds__(NT) k_io_validate(const QPDev* __restrict__ qs, QpIoData in, int B, int nx, int na,
+                                                    unsigned long long* __restrict__ verdict) {
+  const int per = nx + na;
+  unsigned long long key = IPMZ_IO_VALID;
+  for (int z = blockIdx.y; z < B; z += gridDim.y) {
+    const QPDev& q = qs[z];
+    const double* lx = in.lx ? in.lx + (int64_t)z * in.slx : q.lx;
+    const double* ux = in.ux ? in.ux + (int64_t)z * in.sux : q.ux;
+    const double* lA = in.lA ? in.lA + (int64_t)z * in.slA : q.lA;
+    const double* uA = in.uA ? in.uA + (int64_t)z * in.suA : q.uA;
+    for (int t = blockIdx.x * NT + threadIdx.x; t < per; t += gridDim.x * NT) {
+      bool bad;
+      int kind, k;
+      if (t < nx) {
+        kind = 0, k = t;
+        bad = !(lx[k] < ux[k]);
+      } else {
+        kind = 1, k = t - nx;
+        bad = !(lA[k] <= uA[k]);
+      }
+      if (bad) {
+        const unsigned long long cand = io_key(z, kind, k);
+        key = cand < key ? cand : key;
+      }
+    }
+  }
+  key = wave_min_u64(key);
+  if ((threadIdx.x & 63) == 0 && key != IPMZ_IO_VALID) atomicMin(verdict, key);
+}
+
+hipError_t qp_io_validate(const QPBatch& qb, const QpIoData& in, unsigned long long* verdict, hipStream_t st) {
+  const int nx = (in.lx || in.ux) ? qb.h.n : 0, na = (in.lA || in.uA) ? qb.h.m_usr : 0;
+  hipError_t e = hipMemsetAsync(verdict, 0xff, sizeof(unsigned long long), st);  // IPMZ_IO_VALID
+  if (e != hipSuccess || nx + na == 0) return e;
+  hipLaunchKernelGGL(k_io_validate, io_grid(nx + na, qb.B), dim3(NT), 0, st, qb.d, in, qb.B, nx, na, verdict);
+  return hipGetLastError();
+}
+
+// ---------------------------------------------------------------------------
+// One matrix block: rows x n elements of every QP from src + z sq + i ld + j
+// to the QP's own Q / A / C (which = 0 / 1 / 2) at i ldn + j; columns [n, ldn)
+// are not touched.  VEC: 16-byte accesses (the host checked that src, ld and
+// sq allow them; the destination rows are 64-byte aligned) -- a row is
+// n / 2 pairs and, for odd n, one last element.
+template <bool VEC>
+__global__ void __launch_bounds__(NT) k_io_pack_matrix(const QPDev* __restrict__ qs, const double* __restrict__ src,
+                                                       int64_t ld, int64_t sq, int rows, int which, int B) {
+  const int n = qs[0].n;
+  const int64_t ldn = qs[0].ldn;
+  const int ipr = VEC ? (n + 1) / 2 : n;  // work items per row
+  const int64_t per = (int64_t)rows * ipr;
+  const bool small = per <= INT_MAX;  // (32-bit division where it serves)
+  for (int z = blockIdx.y; z < B; z += gridDim.y) {
+    const QPDev& q = qs[z];
+    double* dst = const_cast<double*>(which == 0 ? q.Q : which == 1 ? q.A : q.C);
+    const double* s = src + (int64_t)z * sq;
+    for (int64_t t = blockIdx.x * (int64_t)NT + threadIdx.x; t < per; t += (int64_t)gridDim.x * NT) {
+      int64_t i;
+      int j;
+      if (small) {
+        i = (unsigned)t / (unsigned)ipr;
+        j = (unsigned)t % (unsigned)ipr;
+      } else {
+        i = t / ipr;
+        j = (int)(t % ipr);
+      }
+      if (VEC) {
+        const int c = 2 * j;
+        if (c + 1 < n)
+          *reinterpret_cast<double2*>(dst + i * ldn + c) = *reinterpret_cast<const double2*>(s + i * ld + c);
+        else
+          dst[i * ldn + c] = s[i * ld + c];
+      } else {
+        dst[i * ldn + j] = s[i * ld + j];
+      }
+    }
+  }
+}
+
+// The vector blocks in one launch: c, l_x, u_x (n), l_A, u_A (m_usr), d
+// (p_usr); with eqss the equality rows m_usr.. of l_A and u_A receive d too.
+__global__ void __launch_bounds__(NT) k_io_pack_vectors(const QPDev* __restrict__ qs, QpIoData in, int B) {
+  const int n = qs[0].n, m = qs[0].m_usr, p = qs[0].p_usr;
+  for (int z = blockIdx.y; z < B; z += gridDim.y) {
+    const QPDev& q = qs[z];
+    for (int t = blockIdx.x * NT + threadIdx.x; t < n || t < m || t < p; t += gridDim.x * NT) {
+      if (t < n) {
+        if (in.c) const_cast<double*>(q.c)[t] = in.c[(int64_t)z * in.sc + t];
+        if (in.lx) const_cast<double*>(q.lx)[t] = in.lx[(int64_t)z * in.slx + t];
+        if (in.ux) const_cast<double*>(q.ux)[t] = in.ux[(int64_t)z * in.sux + t];
+      }
+      if (t < m) {
+        if (in.lA) const_cast<double*>(q.lA)[t] = in.lA[(int64_t)z * in.slA + t];
+        if (in.uA) const_cast<double*>(q.uA)[t] = in.uA[(int64_t)z * in.suA + t];
+      }
+      if (t < p && in.d) {
+        const double v = in.d[(int64_t)z * in.sd + t];
+        const_cast<double*>(q.d)[t] = v;
+        if (q.eqss) const_cast<double*>(q.lA)[m + t] = const_cast<double*>(q.uA)[m + t] = v;
+      }
+    }
+  }
+}
+
+static bool io_vec_ok(const double* p, int64_t ld, int64_t sq) { return !((uintptr_t)p & 15) && !(ld & 1) && !(sq & 1); }
+
+hipError_t qp_io_pack(const QPBatch& qb, const QpIoData& in, hipStream_t st) {
+  const QPDev& h = qb.h;
+  const struct {
+    const double* p;
+    int64_t ld, sq;
+    int rows;
+  } mats[3] = {{in.Q, in.ldq, in.sQ, h.n}, {in.A, in.lda, in.sA, h.m_usr}, {in.C, in.ldc, in.sC, h.p_usr}};
+  for (int w = 0; w < 3; ++w) {
+    if (!mats[w].p || mats[w].rows == 0) continue;
+    if (io_vec_ok(mats[w].p, mats[w].ld, mats[w].sq))
+      hipLaunchKernelGGL(k_io_pack_matrix<true>, io_grid((int64_t)mats[w].rows * ((h.n + 1) / 2), qb.B), dim3(NT), 0, st,
+                         qb.d, mats[w].p, mats[w].ld, mats[w].sq, mats[w].rows, w, qb.B);
+    else
+      hipLaunchKernelGGL(k_io_pack_matrix<false>, io_grid((int64_t)mats[w].rows * h.n, qb.B), dim3(NT), 0, st, qb.d,
+                         mats[w].p, mats[w].ld, mats[w].sq, mats[w].rows, w, qb.B);
+  }
+  if (in.c || in.lx || in.ux || in.lA || in.uA || in.d) {
+    const int mx = h.n > h.m_usr ? (h.n > h.p_usr ? h.n : h.p_usr) : (h.m_usr > h.p_usr ? h.m_usr : h.p_usr);
+    hipLaunchKernelGGL(k_io_pack_vectors, io_grid(mx, qb.B), dim3(NT), 0, st, qb.d, in, qb.B);
+  }
+  return hipGetLastError();
+}
+
+// ---------------------------------------------------------------------------
+// Row z of dst (row stride ld) <- the state_len doubles of QP z's iterate,
+// affine direction, direction or residuals (which = IPMZ_STATE_*) in the
+// reference's Newton order; columns [state_len, ld) are not written.
+//
+// EqualityHandling::SlackedSlacks / NaiveSlacks run the p_usr equality rows
+// as inequality rows, so the step's slots hold [lambda_g lambda_v], [lambda_h
+// lambda_w], [g v], [h w] while the reference's order is lambda_g, lambda_h,
+// lambda_v, lambda_w, ..., g, h, v, w (formulations.txt; qp.cpp eqss_perm is
+// the host form of the same map).  The source index of element k follows
+// from the segment lengths alone.
+__device__ __forceinline__ int64_t eqss_block(int64_t k, int64_t m, int64_t p) {
+  const int64_t mp = m + p;                      // in: [a m][b m][a' p][b' p]; stored: [a m a' p][b m b' p]
+  if (k < m) return k;                           // a
+  if (k < 2 * m) return mp + (k - m);            // b
+  if (k < 2 * m + p) return m + (k - 2 * m);     // a'
+  return mp + m + (k - 2 * m - p);               // b'
+}
+__device__ __forceinline__ int64_t eqss_source(int64_t k, const QPDev& q) {
+  const int64_t n = q.n, m = q.m_usr, p = q.p_usr, mp = m + p;
+  const int64_t duals = q.naive ? n : n + 2 * mp;  // after x (NaiveSlacks) or x, [lambda_A lambda_C], [s t]
+  if (k < duals) return k;
+  if (k < duals + 2 * mp) return duals + eqss_block(k - duals, m, p);
+  const int64_t slacks = duals + 2 * mp + (q.vlo ? n : 0) + (q.vup ? n : 0);  // after lambda_y, lambda_z
+  if (k < slacks) return k;
+  if (k < slacks + 2 * mp) return slacks + eqss_block(k - slacks, m, p);
+  return k;  // y, z
+}
+
+__global__ void __launch_bounds__(NT) k_io_gather_state(const QPDev* __restrict__ qs, int which, double* __restrict__ dst,
+                                                        int64_t ld, int B) {
+  const int64_t L = qs[0].state_len;
+  const bool eqss = qs[0].eqss;
+  for (int z = blockIdx.y; z < B; z += gridDim.y) {
+    const QPDev& q = qs[z];
+    const double* src = which == 0 ? q.v[0] : which == 1 ? q.daff[0] : which == 2 ? q.dir[0] : q.r[0];
+    double* row = dst + (int64_t)z * ld;
+    for (int64_t k = blockIdx.x * (int64_t)NT + threadIdx.x; k < L; k += (int64_t)gridDim.x * NT)
+      row[k] = src[eqss ? eqss_source(k, q) : k];
+  }
+}
+
+hipError_t qp_gather_state(const QPBatch& qb, int which, double* dst, int64_t ld, hipStream_t st) {
+  hipLaunchKernelGGL(k_io_gather_state, io_grid(qb.h.state_len, qb.B), dim3(NT), 0, st, qb.d, which, dst, ld, qb.B);
+  return hipGetLastError();
+}
+
+}  // namespace ipmz

@@ -518,4 +518,32 @@ hipError_t qp_fused_solves(const QPBatch& qb, const double* K, int64_t ld, int N
                            double* b, int64_t sK, int64_t sD, int64_t sL, int64_t sb, int freeze, hipStream_t st);
 hipError_t qp_fused_eval(const QPBatch& qb, hipStream_t st);
 
+// io.hip ---------------------------------------------------------------------
+// A caller's problem data in device memory (ipmz_qp_device_data with the
+// blocks this call does not take -- not supplied, or of dimension 0 -- null):
+// matrices with a row stride and a QP stride, vectors with a QP stride, in
+// elements; a QP stride of 0 is one block shared by every QP.
+struct QpIoData {
+  const double *Q, *A, *C;
+  int64_t ldq, sQ, lda, sA, ldc, sC;
+  const double *c, *lx, *ux, *lA, *uA, *d;
+  int64_t sc, slx, sux, slA, suA, sd;
+};
+// The bound check's verdict word: IPMZ_IO_VALID, or the smallest key of a
+// violated bound in the order (QP, l_x < u_x before l_A <= u_A, index)
+constexpr unsigned long long IPMZ_IO_VALID = ~0ull;
+constexpr unsigned long long io_key(int qp, int kind, int k) {
+  return ((unsigned long long)(unsigned)qp << 33) | ((unsigned long long)kind << 32) | (unsigned)k;
+}
+// build_environment's check (!(l_x < u_x), !(l_A <= u_A): NaN is a violation)
+// of the bound pairs of which `in` supplies a side, the other side being the
+// solver's; resets and fills *verdict (device).  Independent of scheduling.
+hipError_t qp_io_validate(const QPBatch& qb, const QpIoData& in, unsigned long long* verdict, hipStream_t st);
+// every supplied block into the solver's storage: exactly the elements the
+// host load writes (columns [n, ldn) and the space between QPs keep their bits)
+hipError_t qp_io_pack(const QPBatch& qb, const QpIoData& in, hipStream_t st);
+// row z of dst (device, row stride ld >= state_len) <- QP z's state `which`
+// (IPMZ_STATE_*) in the reference's Newton order; one launch, no allocation
+hipError_t qp_gather_state(const QPBatch& qb, int which, double* dst, int64_t ld, hipStream_t st);
+
 }  // namespace ipmz

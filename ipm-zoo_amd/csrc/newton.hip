@@ -1383,7 +1383,7 @@ __global__ __launch_bounds__(FT) __attribute__((amdgpu_waves_per_eu(8))) void k_
   __shared__ double sh[FT / 64];
   __shared__ unsigned last;
   const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
-  const int n = q.n, m = q.m, p = q.p, N = q.N;
+  const int n = q.n, m = q.m, p = q.p;
   const int gw = blockIdx.x * (FT / 64) + wave, nw = gridDim.x * (FT / 64);
   const double* x = q.v[X];
   const int nr = n + m + p;
@@ -1478,7 +1478,9 @@ __global__ __launch_bounds__(FT) __attribute__((amdgpu_waves_per_eu(8))) void k_
   if (!last) return;
   if (tid == 0) st_sc1(q.done, 0u);
   double res2 = 0.0, comp = 0.0, fa = 0.0, fb = 0.0;
-  for (int t = tid; t < N; t += FT) residual_elem<true>(q, t, 0.0, res2, comp, fa, fb);
+  // (n + m + p elements, not N: NaiveSlacks has 2 m KKT rows for the m elements of the inequality block, and an
+  // element past the last one would read and write the equality slots out of range)
+  for (int t = tid; t < nr; t += FT) residual_elem<true>(q, t, 0.0, res2, comp, fa, fb);
   res2 = block_allsum<FT>(res2, sh);
   comp = block_allsum<FT>(comp, sh);
   fa = block_allsum<FT>(fa, sh);

@@ -38,6 +38,13 @@ struct ipmz_qp {
   int* binfo = nullptr;
   int64_t sL = 0, sW = 0;
   bool loaded = false;
+  // ipmz_batch_load_device: the data blocks the solver holds for every QP (HELD_* bits; a block this call does not
+  // supply must be held), the QPs a host load has filled since the last whole-batch fill, and the device word the
+  // bound check answers in
+  unsigned held = 0;
+  std::vector<char> host_filled;
+  int host_filled_count = 0;
+  unsigned long long* verdict = nullptr;
   // mixed precision (C5): fp32 factor of S K S + fp64 refinement
   bool mixed = false;
   double ir_tol = 1e-12;
@@ -147,6 +154,12 @@ int grow(ipmz_qp* s, GrowBuf& b, size_t bytes, bool zero = false) {
   (void)hipGetLastError();
   return fail(IPMZ_ERR_NOMEM, "device allocation failed");
 }
+
+// ipmz_qp::held
+enum : unsigned {
+  HELD_Q = 1, HELD_C = 2, HELD_A = 4, HELD_LA = 8, HELD_UA = 16, HELD_CEQ = 32, HELD_D = 64, HELD_LX = 128,
+  HELD_UX = 256, HELD_ALL = 511
+};
 
 void drop_graph(ipmz_qp* s) {
   if (s->gexec) hipGraphExecDestroy(s->gexec);
@@ -497,6 +510,7 @@ int create_solver(ipmz_ctx* ctx, const ipmz_qp_config* cfg, int B, ipmz_qp** out
     }
   }
   s->dq = dev_alloc<QPDev>(s, B, false);
+  s->verdict = dev_alloc<unsigned long long>(s, 8, false);
   // every failure from here on leaves through ipmz_qp_destroy: it frees what
   // was allocated and gives the context's user count back
   auto bail = [&](int rc) {
@@ -930,6 +944,7 @@ int ipmz_qp_load_host(ipmz_qp* s, const double* Q, const double* c, const double
     int rc = load_one(s, i, Q, c, A, lA, uA, C, d, lx, ux);
     if (rc) return rc;
   }
+  s->held = HELD_ALL;
   return initialize(s);
 }
 
@@ -937,6 +952,7 @@ int ipmz_qp_generate(ipmz_qp* s, uint64_t seed) {
   if (!s) return fail(IPMZ_ERR_INVALID, "null qp");
   HIP_OK(hipSetDevice(s->ctx->device));
   HIP_OK(qp_generate(s->qb, seed, s->ctx->stream));
+  s->held = HELD_ALL;
   return initialize(s);
 }
 
@@ -1407,6 +1423,12 @@ int ipmz_batch_load_host(ipmz_qp* s, int index, const double* Q, const double* c
   int rc = check_index(s, index);
   if (rc) return rc;
   if ((rc = load_one(s, index, Q, c, A, lA, uA, C, d, lx, ux))) return rc;
+  // (every block is held once each QP has been filled)
+  if (s->host_filled.empty()) s->host_filled.assign((size_t)s->B, 0);
+  if (!s->host_filled[(size_t)index]) {
+    s->host_filled[(size_t)index] = 1;
+    if (++s->host_filled_count == s->B) s->held = HELD_ALL;
+  }
   // the kept KKT matrix K0 (off-diagonal part written only by
   // initialize) and the residuals still hold the old data: no step
   // until ipmz_batch_initialize rebuilds them
@@ -1467,6 +1489,91 @@ int ipmz_batch_set_factor_kernel(ipmz_qp* s, int kernel) {
                                   "(N <= 1024) with 2 * batch <= #CU");
   drop_graph(s);  // the captured step has the other kernel baked in
   s->small_kernel = kernel;
+  return IPMZ_OK;
+}
+
+// build_environment for the whole batch from device memory: the bound check
+// (one launch, one synchronize for its verdict), the copy of every supplied
+// block (io.hip), then initialize().  A captured step graph stays: it holds the
+// addresses of the solver's storage and the kernel selection, neither of which
+// a load changes, and reads the data and the kept matrix K0 -- whose
+// off-diagonal part initialize() rewrites from the new data -- when replayed.
+int ipmz_batch_load_device(ipmz_qp* s, const ipmz_qp_device_data* data) {
+  const std::string who = "ipmz_batch_load_device";
+  if (!s || !data) return fail(IPMZ_ERR_INVALID, who + ": null argument");
+  const int n = s->n, m = s->m_usr, p = s->p_usr;
+  // blocks of dimension 0 are ignored whatever they hold
+  QpIoData in{};
+  in.Q = data->Q, in.ldq = data->ldq, in.sQ = data->sQ;
+  in.c = data->c, in.sc = data->sc;
+  in.lx = data->l_x, in.slx = data->slx;
+  in.ux = data->u_x, in.sux = data->sux;
+  if (m) {
+    in.A = data->A, in.lda = data->lda, in.sA = data->sA;
+    in.lA = data->l_A, in.slA = data->slA;
+    in.uA = data->u_A, in.suA = data->suA;
+  }
+  if (p) {
+    in.C = data->C, in.ldc = data->ldc, in.sC = data->sC;
+    in.d = data->d, in.sd = data->sd;
+  }
+  struct Block {
+    const char* name;
+    const double* ptr;
+    int64_t rows, ld, sq;  // rows 0: a vector of n / m / p elements (ld: its length)
+    unsigned bit;
+  };
+  const Block blocks[9] = {{"Q", in.Q, n, in.ldq, in.sQ, HELD_Q},        {"A", in.A, m, in.lda, in.sA, HELD_A},
+                           {"C", in.C, p, in.ldc, in.sC, HELD_CEQ},      {"c", in.c, 0, n, in.sc, HELD_C},
+                           {"l_x", in.lx, 0, n, in.slx, HELD_LX},        {"u_x", in.ux, 0, n, in.sux, HELD_UX},
+                           {"l_A", in.lA, 0, m, in.slA, HELD_LA},        {"u_A", in.uA, 0, m, in.suA, HELD_UA},
+                           {"d", in.d, 0, p, in.sd, HELD_D}};
+  unsigned supplied = 0, absent = (m ? 0 : HELD_A | HELD_LA | HELD_UA) | (p ? 0 : HELD_CEQ | HELD_D);
+  for (const Block& b : blocks) {
+    if (!b.ptr) continue;
+    supplied |= b.bit;
+    if (b.rows && b.ld < n)
+      return fail(IPMZ_ERR_INVALID, who + ": " + b.name + ": row stride " + std::to_string(b.ld) + " < n");
+    if (b.ld < 0 || b.sq < 0) return fail(IPMZ_ERR_INVALID, who + ": " + b.name + ": negative stride");
+    const int64_t extent = b.rows ? (b.rows - 1) * b.ld + n : b.ld;
+    if (s->B > 1 && b.sq != 0 && b.sq < extent)
+      return fail(IPMZ_ERR_INVALID, who + ": " + b.name + ": QP stride " + std::to_string(b.sq) +
+                                        " is neither 0 (shared) nor at least the block's extent " + std::to_string(extent));
+  }
+  if (const unsigned missing = HELD_ALL & ~(supplied | absent | s->held)) {
+    std::string names;
+    for (const Block& b : blocks)
+      if (missing & b.bit) names += std::string(names.empty() ? "" : ", ") + b.name;
+    return fail(IPMZ_ERR_STATE, who + ": not supplied and never loaded or generated: " + names);
+  }
+  HIP_OK(hipSetDevice(s->ctx->device));
+  int rc = not_capturing(s->ctx, "ipmz_batch_load_device");
+  if (rc) return rc;
+  if ((rc = wait_pending_step(s))) return rc;
+  hipStream_t st = s->ctx->stream;
+  unsigned long long verdict = IPMZ_IO_VALID;
+  HIP_OK(qp_io_validate(s->qb, in, s->verdict, st));
+  HIP_OK(hipMemcpyAsync(&verdict, s->verdict, sizeof verdict, hipMemcpyDeviceToHost, st));
+  HIP_OK(hipStreamSynchronize(st));
+  if (verdict != IPMZ_IO_VALID)  // nothing was written
+    return fail(IPMZ_ERR_INVALID, who + ": QP " + std::to_string(verdict >> 33) +
+                                      ((verdict >> 32 & 1) ? ": l_A <= u_A violated at " : ": l_x < u_x violated at ") +
+                                      std::to_string(verdict & 0xffffffffull));
+  HIP_OK(qp_io_pack(s->qb, in, st));
+  // the scalar blocks as a new solver has them: the last step's entries belong to the data just replaced
+  HIP_OK(hipMemsetAsync(s->hq[0].scal, 0, scal_pitch(s) * (size_t)s->B, st));
+  s->held |= supplied;
+  return initialize(s);
+}
+
+int ipmz_batch_copy_state(ipmz_qp* s, int which, double* dst, int64_t ld) {
+  if (!s) return fail(IPMZ_ERR_INVALID, "null qp");
+  if (which < IPMZ_STATE_VARS || which > IPMZ_STATE_RES || !dst || ld < s->state_len)
+    return fail(IPMZ_ERR_INVALID, "ipmz_batch_copy_state: bad arguments (which: IPMZ_STATE_*; dst: not null, row stride "
+                                  ">= state_len)");
+  if (!s->loaded) return fail(IPMZ_ERR_STATE, "ipmz_batch_copy_state: load or generate the QP first");
+  HIP_OK(hipSetDevice(s->ctx->device));
+  HIP_OK(qp_gather_state(s->qb, which, dst, ld, s->ctx->stream));
   return IPMZ_OK;
 }
 

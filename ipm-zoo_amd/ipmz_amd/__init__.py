@@ -54,6 +54,7 @@ EXPORTS = [
     "ipmz_bk_factor_batch", "ipmz_bk_batch_solve_workspace_bytes", "ipmz_bk_prepare_solve_batch",
     "ipmz_bk_solve_multi_batch", "ipmz_batch_kkt_solve_bk",
     "ipmz_qp_newton_solve_multi", "ipmz_batch_newton_solve_multi",
+    "ipmz_batch_load_device", "ipmz_batch_copy_state",
 ]
 SOLVE_MULTI_PANEL = 256  # include/ipmz.h IPMZ_SOLVE_MULTI_PANEL: column panel of the blocked multi-rhs solve
 REDUCTION_AUGMENTED, REDUCTION_NORMAL = 0, 1
@@ -87,6 +88,42 @@ class _QPConfig(ctypes.Structure):
     _fields_ = [("n", ctypes.c_int), ("m", ctypes.c_int), ("p", ctypes.c_int), ("delta", ctypes.c_double),
                 ("equality_handling", ctypes.c_int), ("inequality_handling", ctypes.c_int),
                 ("inequality_bounds", ctypes.c_int), ("variable_bounds", ctypes.c_int)]
+
+
+class _QPDeviceData(ctypes.Structure):
+    """include/ipmz.h ipmz_qp_device_data: device pointers, strides in elements."""
+    _fields_ = [("Q", _VP), ("ldq", _I64), ("sQ", _I64), ("A", _VP), ("lda", _I64), ("sA", _I64),
+                ("C", _VP), ("ldc", _I64), ("sC", _I64), ("c", _VP), ("l_x", _VP), ("u_x", _VP),
+                ("sc", _I64), ("slx", _I64), ("sux", _I64), ("l_A", _VP), ("u_A", _VP), ("slA", _I64), ("suA", _I64),
+                ("d", _VP), ("sd", _I64)]
+
+
+def _tensor_block(t, batch, rows, cols):
+    """A torch tensor as one block of ipmz_qp_device_data: (data_ptr, row stride, QP stride), strides in elements.
+
+    rows is None for a vector block -- t of shape (batch, cols), or (cols,) shared by every QP -- else the block is
+    a matrix: (batch, rows, cols), or (rows, cols) shared.  A shared block, and one expanded along the batch
+    dimension (batch stride 0), has QP stride 0.  Nothing is copied: the strides go to the kernel as they are.
+    ValueError for a dtype other than float64, another shape, or an inner stride other than 1."""
+    import torch
+    name = "matrix" if rows is not None else "vector"
+    if not isinstance(t, torch.Tensor) or t.dtype != torch.float64:
+        raise ValueError(f"{name} block: a float64 torch tensor is needed, got {getattr(t, 'dtype', type(t))}")
+    inner = (cols,) if rows is None else (rows, cols)
+    shape = tuple(t.shape)
+    if shape == (batch,) + inner:
+        sq = t.stride(0) if batch > 1 else 0
+        strides = t.stride()[1:]
+    elif shape == inner:
+        sq = 0
+        strides = t.stride()
+    else:
+        raise ValueError(f"{name} block: shape {shape} is neither {(batch,) + inner} nor {inner}")
+    if cols > 1 and strides[-1] != 1:
+        raise ValueError(f"{name} block: inner stride {strides[-1]}, must be 1 (elements of a row adjacent)")
+    # (the stride of a dimension of size 1 means nothing: a single row is given the row length)
+    ld = 0 if rows is None else (strides[0] if rows > 1 else max(strides[0], cols))
+    return t.data_ptr(), ld, sq
 
 
 def _load():
@@ -181,6 +218,8 @@ def _load():
         "ipmz_batch_kkt_solve_bk": ([_VP, _I, _VP, _I64, _I64, ctypes.POINTER(_I)], _I),
         "ipmz_qp_newton_solve_multi": ([_VP, _I, _VP, _I64, _VP, _I64, _VP], _I),
         "ipmz_batch_newton_solve_multi": ([_VP, _I, _VP, _I64, _I64, _VP, _I64, _I64, _VP, ctypes.POINTER(_I)], _I),
+        "ipmz_batch_load_device": ([_VP, ctypes.POINTER(_QPDeviceData)], _I),
+        "ipmz_batch_copy_state": ([_VP, _I, _VP, _I64], _I),
     }
     for name, (args, res) in sig.items():
         fn = getattr(lib, name)
@@ -542,6 +581,81 @@ class Optimizer:
 
     def generate(self, seed):
         _check(lib.ipmz_qp_generate(self.h, seed), "ipmz_qp_generate")
+
+    # -- device-resident load and read-back (torch CUDA tensors; nothing passes through host memory) --
+    def _order_torch_stream(self, torch):
+        """Work already enqueued on torch's current stream comes before what the context enqueues next: nothing to
+        do when the context runs on that stream, else that stream is synchronized."""
+        cur = torch.cuda.current_stream(self.ctx.device)
+        if not self.ctx.on_stream(cur.cuda_stream):
+            cur.synchronize()
+
+    def _on_device(self, t, name):
+        if not t.is_cuda or t.device.index != self.ctx.device:
+            raise ValueError(f"{name}: tensor on {t.device}, the context is on cuda:{self.ctx.device}")
+
+    def load_tensors(self, Q=None, c=None, l_x=None, u_x=None, A_ineq=None, l_A_ineq=None, u_A_ineq=None, A_eq=None,
+                     b_eq=None):
+        """build_environment for every QP of the solver from float64 CUDA tensors (Data's names), then a fresh
+        iterate: ipmz_batch_load_device.  Matrices are (batch, rows, n) or (rows, n) shared by every QP, vectors
+        (batch, len) or (len,) shared; any row / batch strides (views, .expand), inner stride 1; nothing is copied.
+        None keeps the block the solver holds (e.g. load_tensors(c=c2, b_eq=d2) for a parametric re-load)."""
+        import torch
+        batch = lib.ipmz_batch_size(self.h)
+        n, m, p = self.n, self.m, self.p
+        d = _QPDeviceData()
+        keep = []  # the tensors stay referenced until the call returns
+
+        def put(t, name, rows, cols, ptr, ld, sq):
+            if t is None or cols == 0 or rows == 0:
+                return
+            if not isinstance(t, torch.Tensor):
+                raise ValueError(f"{name}: a torch tensor is needed")
+            self._on_device(t, name)
+            blk = _tensor_block(t, batch, rows, cols)
+            keep.append(t)
+            setattr(d, ptr, blk[0])
+            if ld:
+                setattr(d, ld, blk[1])
+            setattr(d, sq, blk[2])
+
+        put(Q, "Q", n, n, "Q", "ldq", "sQ")
+        put(A_ineq, "A_ineq", m, n, "A", "lda", "sA")
+        put(A_eq, "A_eq", p, n, "C", "ldc", "sC")
+        put(c, "c", None, n, "c", None, "sc")
+        put(l_x, "l_x", None, n, "l_x", None, "slx")
+        put(u_x, "u_x", None, n, "u_x", None, "sux")
+        put(l_A_ineq, "l_A_ineq", None, m, "l_A", None, "slA")
+        put(u_A_ineq, "u_A_ineq", None, m, "u_A", None, "suA")
+        put(b_eq, "b_eq", None, p, "d", None, "sd")
+        self._order_torch_stream(torch)
+        _check(lib.ipmz_batch_load_device(self.h, ctypes.byref(d)), "ipmz_batch_load_device")
+        del keep
+
+    def state_tensor(self, which=0, out=None):
+        """The state `which` (0 iterate, 1 affine direction, 2 direction, 3 residuals) of every QP as a
+        (batch, state_len) float64 CUDA tensor, row q what state(q, which) returns: ipmz_batch_copy_state.
+        out: a 2-D float64 tensor on the context's device with batch rows, inner stride 1 and row stride >=
+        state_len (its columns from state_len on are not written).  Returns after ctx.sync()."""
+        import torch
+        batch, L = lib.ipmz_batch_size(self.h), self.state_len
+        if out is None:
+            out = torch.empty((batch, L), dtype=torch.float64, device=f"cuda:{self.ctx.device}")
+        else:
+            self._on_device(out, "out")
+            if out.dtype != torch.float64 or out.dim() != 2 or out.shape[0] != batch or \
+                    (out.shape[1] > 1 and out.stride(1) != 1):
+                raise ValueError(f"out: a float64 ({batch}, >= {L}) tensor with inner stride 1 is needed")
+        # (too few columns: the library refuses the row stride; the stride of a single row means nothing)
+        ld = out.shape[1] if out.shape[1] < L or batch == 1 else out.stride(0)
+        self._order_torch_stream(torch)
+        _check(lib.ipmz_batch_copy_state(self.h, which, _VP(out.data_ptr()), ld), "ipmz_batch_copy_state")
+        self.ctx.sync()
+        return out[:, :L]
+
+    def solution_tensor(self):
+        """x of every QP, (batch, n): x leads the Newton order in every formulation."""
+        return self.state_tensor(0)[:, :self.n]
 
     def step(self, flags=0):
         _check(lib.ipmz_qp_step(self.h, flags), "ipmz_qp_step")
