@@ -458,6 +458,7 @@ struct QPDev {
   double* K;      // KKT / factor (N x ldk)
   double* K0;     // batches of small systems: the assembled KKT kept across steps (the factor reads it, writes L to K); nullptr: none
   double *v0, *r0, *scal0;  // initial iterate snapshot (benchmark restarts)
+  double* Cx0;              // ... and its C x, which PenaltyFunction's corrector row reads (corrector_elem)
   unsigned* done;           // fused evaluation: arrival counter of the QP's workgroups (0 between launches)
 };
 

@@ -1122,13 +1122,23 @@ hipError_t qp_update(const QPBatch& qb, int freeze, hipStream_t st) {
 
 // Benchmark restart: a converged iterate is reset (on device, no host sync)
 // to the saved initial state, so every timed step is a real Newton step.
-__global__ void k_restart_copy(const QPDev* __restrict__ qs) {
-  const QPDev& q = qs[blockIdx.y];
-  if (q.scal[SC_CONVERGED] == 0.0) return;
-  for (int64_t t = blockIdx.x * (int64_t)NT + threadIdx.x; t < q.state_len; t += (int64_t)gridDim.x * NT) {
+// Element t of the restart copy (the callers stride over state_len elements;
+// p <= state_len).  PenaltyFunction: C x goes back too -- its corrector row is
+// rebuilt from q.Cx (corrector_elem), which otherwise still holds the
+// converged iterate's; no other formulation reads a product of the evaluation
+// between a restart and the next evaluation.
+__device__ __forceinline__ void restart_elem(const QPDev& q, int64_t t) {
+  if (t < q.state_len) {
     q.v[0][t] = q.v0[t];
     q.r[0][t] = q.r0[t];
   }
+  if (q.eqpen && t < q.p) q.Cx[t] = q.Cx0[t];
+}
+__global__ void k_restart_copy(const QPDev* __restrict__ qs) {
+  const QPDev& q = qs[blockIdx.y];
+  if (q.scal[SC_CONVERGED] == 0.0) return;
+  for (int64_t t = blockIdx.x * (int64_t)NT + threadIdx.x; t < q.state_len; t += (int64_t)gridDim.x * NT)
+    restart_elem(q, t);
 }
 __global__ void k_restart_scal(const QPDev* __restrict__ qs) {
   const QPDev& q = qs[blockIdx.y];
@@ -1184,6 +1194,7 @@ __global__ void k_save_initial(const QPDev* __restrict__ qs) {
   for (int64_t t = blockIdx.x * (int64_t)NT + threadIdx.x; t < q.state_len; t += (int64_t)gridDim.x * NT) {
     q.v0[t] = q.v[0][t];
     q.r0[t] = q.r[0][t];
+    if (q.eqpen && t < q.p) q.Cx0[t] = q.Cx[t];
   }
   if (blockIdx.x == 0 && threadIdx.x < SC_COUNT) q.scal0[threadIdx.x] = q.scal[threadIdx.x];
 }
@@ -1216,10 +1227,7 @@ __global__ __launch_bounds__(FT) void k_fused_pre(const QPDev* __restrict__ qs, 
   double* const KT = kmode == KMODE_K ? q.K : q.K0;
   if (info && lead && blockIdx.y == 0 && tid == 0) *info = 0x7f7f7f7f;  // the factor's first-failure word
   if (lead && restart && q.scal[SC_CONVERGED] != 0.0) {
-    for (int64_t t = tid; t < q.state_len; t += FT) {
-      q.v[0][t] = q.v0[t];
-      q.r[0][t] = q.r0[t];
-    }
+    for (int64_t t = tid; t < q.state_len; t += FT) restart_elem(q, t);
     __syncthreads();  // every thread has read SC_CONVERGED
     if (tid == 0) {
       const double restarts = q.scal[SC_RESTARTS];

@@ -464,6 +464,7 @@ int create_solver(ipmz_ctx* ctx, const ipmz_qp_config* cfg, int B, ipmz_qp** out
   double* Ax = dev_array(s, m);
   double* d = dev_array(s, s->p_usr, &sp);
   double* Cx = dev_array(s, p);
+  double* Cx0 = dev_array(s, p);
   double* v = dev_array(s, s->state_len, &sS);
   double* r = dev_array(s, s->state_len);
   double* da = dev_array(s, s->state_len);
@@ -556,6 +557,7 @@ int create_solver(ipmz_ctx* ctx, const ipmz_qp_config* cfg, int B, ipmz_qp** out
     q.Ax = Ax + i * sm;
     q.d = d + i * sp;
     q.Cx = Cx + i * sp;
+    q.Cx0 = Cx0 + i * sp;
     carve(s, v + i * sS, q.v);
     carve(s, r + i * sS, q.r);
     carve(s, da + i * sS, q.daff);

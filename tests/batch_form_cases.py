@@ -1,0 +1,151 @@
+"""Every Newton-system formulation through every batched step path: the table
+shared by tests/test_gpu_batch_forms.py (the steps on the device) and
+tests/test_oracle_batch_forms.py (the conditions the table relies on, checked
+without a GPU).  No GPU work and no assertions here.
+
+Every QP of a batch is oracle.gen_qp(n, m, p, seed0 + i), as Batch.generate.
+"""
+import collections
+import functools
+
+import ipmz_amd as I
+import oracle
+
+# csrc/kernels.h (test_oracle_batch_forms.py checks them against the sources)
+FUSED_NMAX = 1024            # IPMZ_FUSED_NMAX: B > 1 and N <= this -> the per-QP k_fused_* phases
+SMALL_NMAX = 1024            # IPMZ_SMALL_NMAX: nbi 64 and N <= this -> the small batched factor (reads K0)
+FUSED_SOLVES_NMAX = 4096     # fused_solves_ok
+DEBUG_NO_K0 = 8192           # IPMZ_DEBUG_NO_K0: the fused pre phase assembles the whole matrix into K
+DEBUG_NO_FUSED_SOLVES = 16384  # IPMZ_DEBUG_NO_FUSED_SOLVES: k_fused_mid / k_fused_post as launches of their own
+FT = 512                     # newton.hip: threads of k_fused_pre / mid / post / eval
+PRE_UNIT = 128               # k_fused_pre: columns per copy unit
+CUS = 256                    # compute units of an MI355X (k0-w8 takes the count from the device at run time)
+
+# ---------------------------------------------------------------------------
+# formulations: name -> (I.Batch keywords, oracle constructor, KKT order)
+Formulation = collections.namedtuple("Formulation", "name kw oracle order")
+
+
+def _n_m_p(n, m, p):
+    return n + m + p
+
+
+def _n_2m_p(n, m, p):
+    return n + 2 * m + p
+
+
+def _n_2mp(n, m, p):
+    return n + 2 * (m + p)
+
+
+def _form(*a, **k):
+    f = oracle.Form(*a, **k)
+    return lambda qp: oracle.OracleQP(qp, form=f)
+
+
+FORMS = collections.OrderedDict((f.name, f) for f in [
+    Formulation("box", dict(), oracle.OracleQP, _n_m_p),  # the default: the control
+    Formulation("vlo", dict(variable_bounds=I.BOUNDS_LOWER), _form(False, 3, 1), _n_m_p),
+    Formulation("vup", dict(variable_bounds=I.BOUNDS_UPPER), _form(False, 3, 2), _n_m_p),
+    Formulation("vnone", dict(variable_bounds=I.BOUNDS_NONE), _form(False, 3, 0), _n_m_p),
+    Formulation("alo", dict(inequality_bounds=I.BOUNDS_LOWER), _form(False, 1, 3), _n_m_p),
+    Formulation("aup", dict(inequality_bounds=I.BOUNDS_UPPER), _form(False, 2, 3), _n_m_p),
+    Formulation("sl", dict(inequality_handling=I.INEQ_SLACKS), _form(True, 3, 3), _n_m_p),
+    Formulation("naive", dict(inequality_handling=I.INEQ_NAIVE_SLACKS), _form(naive=True), _n_2m_p),
+    Formulation("pen", dict(equality_handling=I.EQ_PENALTY), lambda qp: oracle.OracleQP(qp, eq_penalty=True), _n_m_p),
+    # no K0 and no fused solve: every fused row runs KMODE_K + k_bk_factor + separate mid and post (intended)
+    Formulation("none", dict(equality_handling=I.EQ_NONE), lambda qp: oracle.OracleQP(qp, eq_none=True), _n_m_p),
+    Formulation("eqss", dict(equality_handling=I.EQ_SLACKED_SLACKS), oracle.EqSlackedOracle, _n_m_p),
+    Formulation("naiveeq", dict(inequality_handling=I.INEQ_NAIVE_SLACKS, equality_handling=I.EQ_NAIVE_SLACKS),
+                lambda qp: oracle.EqSlackedOracle(qp, naive=True), _n_2mp),
+])
+
+# ---------------------------------------------------------------------------
+# shapes (n, m, p): the smallest at which each loop can go wrong
+S1 = (48, 16, 8)       # every loop a single pass; N 72 / 88 (naive) / 96 (naiveeq)
+S2 = (560, 140, 60)    # N 760 / 900 / 960: N > 512 (strided 512-thread loops), n > 128 (several units per row),
+#                        every N <= 1024 (every formulation on the fused path)
+S0 = (64, 0, 8)        # m == 0: ratio_elem's explicit-bounds branch; vnone: comp_count == 0
+S128 = (96, 24, 8)     # on an nbi = 128 context
+SL = (800, 200, 40)    # N 1040 / 1240 / 1280: past IPMZ_FUSED_NMAX, the non-fused kernels with gridDim.y = B
+# p > max(n, m): the last p - max(n, m) elements of the equality blocks are reached only by the third argument of the
+# update's max(n, m, p) (no shape above has p > n); the equality-slack formulations run it as m + p > n inequality
+# rows.  SP on the fused path (N 48 / 56 / 80), SPL past it (N 1060 / 1260 / 1720: qp_update's max3)
+SP = (16, 8, 24)
+SPL = (400, 100, 560)
+SHAPE_NAMES = {S1: "S1", S2: "S2", S0: "S0", S128: "S128", SL: "SL", SP: "SP", SPL: "SPL"}
+S0_FORMS = ("box", "vlo", "vup", "vnone", "sl", "pen", "none", "eqss")  # (one-sided inequality bounds need m > 0)
+# Only the formulations whose KKT matrix stays well conditioned with more equality rows than variables: C x = d is
+# then inconsistent, EqualityHandling::None's matrix is singular and Regularization's holds it with delta^2 = 1e-8
+# (condition number 4e8, against 10 for these three: test_oracle_batch_forms.py) -- directions there carry
+# cond x 2^-53 of rounding whatever path computes them, which says nothing about the path
+SP_FORMS = ("pen", "eqss", "naiveeq")
+SHAPE_FORMS = {S0: S0_FORMS, SP: SP_FORMS, SPL: SP_FORMS}
+
+# seed0 per (shape, formulation): one value per shape for every formulation
+SEED0 = {S1: 7, S2: 40, S0: 20, S128: 7, SL: 100, SP: 7, SPL: 60}
+
+
+def seed0(shape, form):
+    return SEED0[shape]
+
+
+# ---------------------------------------------------------------------------
+# paths: id, context ("default" / "nbi128"), debug mask, shape, B (None: the device's CU count + 1), steps
+Path = collections.namedtuple("Path", "id ctx mask shape B steps")
+PATHS = collections.OrderedDict((r.id, r) for r in [
+    Path("k0-w16-S1", "default", 0, S1, 3, 3),   # KMODE_K0_DIAG, small factor from K0, k_fused_solves<16>, k_fused_eval
+    Path("k0-w16-S2", "default", 0, S2, 2, 3),   # ... strided loops, multi-unit rows; KMODE_K0_OFFDIAG at initialize
+    Path("k0-w16-S0", "default", 0, S0, 3, 3),   # m == 0
+    Path("k0-w8", "default", 0, S1, None, 2),    # k_fused_solves<8> (B > device_cus())
+    Path("separate", "default", DEBUG_NO_FUSED_SOLVES, S2, 2, 3),  # k_fused_mid / k_fused_post as 512-thread launches
+    Path("no-k0", "default", DEBUG_NO_K0, S2, 2, 3),  # KMODE_K: the whole matrix assembled by k_fused_pre
+    Path("nbi128", "nbi128", 0, S128, 3, 3),     # KMODE_K + chain factor + separate phases
+    Path("nonfused", "default", 0, SL, 2, 2),    # run_step's else branch; none: batched Bunch-Kaufman, N = 1040
+    Path("k0-w16-SP", "default", 0, SP, 3, 3),   # p > max(n, m) in fused_post_body's update
+    Path("nonfused-SPL", "default", 0, SPL, 2, 2),  # ... and in qp_update's grid
+])
+
+
+def batch_of(path, cus=CUS):
+    return cus + 1 if path.B is None else path.B
+
+
+def forms_of(path):
+    return [f for f in FORMS if f in SHAPE_FORMS.get(path.shape, FORMS)]
+
+
+CASES = [(pid, f) for pid, path in PATHS.items() for f in forms_of(path)]
+CASE_IDS = [f"{pid}-{f}" for pid, f in CASES]
+# (path id, formulation) -> the message of the refusal ipmz_batch_create answers with; create_solver
+# (csrc/qp.cpp) refuses none of the table's combinations (test_oracle_batch_forms.py restates its rules)
+REFUSED = {}
+
+# ---------------------------------------------------------------------------
+# freeze / solve_all / restart (k0-w16-S1's shape and batch): every formulation that converges (Slacks does not:
+# the reference's corrector defect), its seed0 and the oracle's iterations to convergence of seeds seed0 .. seed0 + 2
+SOLVE_SHAPE = S1
+SOLVE_B = 3
+RESTART_STEPS = 12
+SOLVE = collections.OrderedDict([
+    ("box", (7, (6, 5, 7))), ("vlo", (7, (6, 5, 7))), ("vup", (7, (6, 5, 6))),
+    # (5, 5, 5) at seeds 7 .. 9, and 5 at all but five of the seeds 0 .. 2999; 1225 is the first that takes 6
+    ("vnone", (1224, (5, 6, 5))),
+    ("alo", (7, (6, 5, 7))), ("aup", (7, (6, 5, 7))), ("naive", (7, (6, 5, 7))), ("pen", (7, (6, 6, 7))),
+    ("none", (7, (6, 5, 7))), ("eqss", (7, (6, 6, 7))), ("naiveeq", (7, (6, 6, 7))),
+])
+
+
+@functools.lru_cache(maxsize=None)
+def qp(shape, seed):
+    """The generated QP, never modified, made once per session."""
+    return oracle.gen_qp(*shape, seed)
+
+
+def oracles(form, shape, B, seed):
+    """Fresh oracle runs (at the initial iterate) of the B QPs of a batch."""
+    return [FORMS[form].oracle(qp(shape, seed + i)) for i in range(B)]
+
+
+def kkt_order(form, shape):
+    return FORMS[form].order(*shape)

@@ -1,0 +1,233 @@
+"""Every Newton-system formulation through every batched step path, through the
+public ABI only, every QP of every batch against its own oracle run.
+
+newton.hip implements twelve Newton systems behind one set of element
+functions, and a batch runs them through code no single QP launches:
+k_fused_pre in its three modes, k_fused_solves<16> and <8>, k_fused_mid /
+k_fused_post as launches of their own, k_fused_eval, and the non-fused kernels
+with gridDim.y = B.  The fused bodies restate their loop bounds by hand
+(n + mk against n + m, the eqpen rows, max(n, m, p), state_len, n + m + p
+residual elements against N KKT rows), so each can be wrong for one
+formulation only.  tests/batch_form_cases.py holds the table (formulations x
+paths, shapes, seeds); tests/test_oracle_batch_forms.py checks on the CPU that
+no QP converges inside a compared window, that each path row lands on the
+kernels it names and that the freeze / restart seeds converge after the tabled
+counts.
+
+The oracle follows the device, not the other way round: the batch is never
+touched with set_state between steps.  set_state re-evaluates every QP through
+the non-fused qp_evaluate, so a loop that resets the batch after each step
+reads f, res, mu and converged that k_fused_eval never wrote, and every step
+starts from an evaluation the step path did not make.  Here each step's
+directions, step lengths and updated iterate are compared against the oracle
+stepped from the same iterate; then the oracle takes the device's iterate, the
+scalars and the residual vector the step itself left are compared against the
+oracle's evaluation of that iterate, and the next step starts from them.
+
+Bounds (tests/batch_compare.py, BASELINE.json north star): the initial iterate
+bitwise; alpha_aff, mu_aff, sigma, alpha, every block of both directions and
+of the updated iterate within 1e-9 relative; ||dx_gpu - dx_cpu||_inf < 1e-10;
+f, res, mu and ||r||_2 within 1e-12 relative of the oracle's evaluation of the
+device's iterate.  Every case prints its worst figures before asserting them.
+"""
+import numpy as np
+import pytest
+
+import batch_form_cases as fc
+from batch_compare import STATE_KEYS, Worst, _compare_step, _rel
+
+pytestmark = pytest.mark.gpu
+I = pytest.importorskip("ipmz_amd")
+torch = pytest.importorskip("torch")
+
+UPDATE, RNORM = "updated iterate blocks rel", "|r|_2 against res rel"
+EXTRA_BOUNDS = {UPDATE: 1e-9, RNORM: 1e-12}
+
+
+@pytest.fixture(scope="module")
+def ctx():
+    return I.Context(0)
+
+
+@pytest.fixture(scope="module")
+def ctx128():
+    """A context of its own with nbi = 128: the blocking is set before any
+    Batch is sized for it and never changed."""
+    c = I.Context(0, nbi=128)
+    yield c
+    c.close()
+
+
+@pytest.fixture(autouse=True)
+def clear_debug():
+    yield
+    I.debug_inject(0)
+
+
+def _evaluator(o):
+    """The oracle object that evaluates an iterate (EqSlackedOracle wraps one
+    over the merged rows: the same x, and the same residual elements in another
+    order)."""
+    return getattr(o, "o", o)
+
+
+def _steps_device_leads(bt, orcs, steps, w):
+    for i, o in enumerate(orcs):
+        assert np.array_equal(bt.state(i, 0), o.vars()), i  # generator + initial iterate: bitwise
+    for it in range(steps):
+        recs = []
+        for i, o in enumerate(orcs):
+            done, rec = o.iterate()
+            assert done == 0, (it, i)  # (test_oracle_batch_forms.py: never inside these windows)
+            recs.append(rec)
+        bt.step()
+        sc = bt.batch_scalars()
+        for i, o in enumerate(orcs):
+            _compare_step(w, o, recs[i], sc[i], bt.state(i, 1), bt.state(i, 2), (it, i))
+            v = bt.state(i, 0)
+            sg, sr = o.split(v), o.split(o.vars())
+            for s in o.order:  # the update: v + 0.995 alpha d, element-wise
+                w.add(UPDATE, np.abs(sg[s] - sr[s]).max() / max(1.0, np.abs(sr[s]).max()), (it, i, s))
+            # the oracle follows the device; what the step itself left against the oracle's evaluation of that iterate
+            o.set_vars(v)
+            ev = _evaluator(o)
+            for k, ref in zip(STATE_KEYS, (ev.objective(), ev.residual_norm(), ev.mu())):
+                w.add("f/res/mu rel", _rel(sc[i, I.SC[k]], ref), (it, i, k))
+            w.add(RNORM, _rel(float(np.linalg.norm(bt.state(i, 3))), ev.residual_norm()), (it, i))
+            assert sc[i, I.SC["converged"]] == 0.0, (it, i)
+
+
+@pytest.mark.parametrize("pid,form", fc.CASES, ids=fc.CASE_IDS)
+def test_batch_form_steps_vs_oracle(request, pid, form):
+    """Every row of tests/batch_form_cases.py's path table for every
+    formulation it lists for the row's shape, all QPs of the batch (257 for
+    k0-w8 on a 256-CU device).
+
+    Measured on an MI355X, worst over the 98 cases: f / res / mu 3.1e-15,
+    ||r||_2 2.9e-15, step scalars 5.4e-15, direction blocks 3.8e-14, updated
+    iterate 2.6e-14 relative, dx 4.6e-14 -- the project's bounds hold for every
+    case, the EqualityHandling::None (Bunch-Kaufman) ones included, and none
+    needed a bound derived from the single-QP run."""
+    path = fc.PATHS[pid]
+    c = request.getfixturevalue("ctx128" if path.ctx == "nbi128" else "ctx")
+    n, m, p = path.shape
+    B = fc.batch_of(path, torch.cuda.get_device_properties(0).multi_processor_count)
+    kw, seed = fc.FORMS[form].kw, fc.seed0(path.shape, form)
+    N = fc.kkt_order(form, path.shape)
+    I.debug_inject(path.mask)
+    if (pid, form) in fc.REFUSED:
+        with pytest.raises(I.IpmzError, match=fc.REFUSED[pid, form]):
+            I.Batch(n, m, p, B, c, **kw)
+        return
+    if path.ctx == "nbi128":
+        assert c.blocking(N) == (256, 128)
+    else:
+        assert c.blocking(N)[1] == 64
+    bt = I.Batch(n, m, p, B, c, **kw)
+    assert bt.N == N
+    bt.generate(seed)
+    w = Worst(f"{pid} {form} N={N} B={B}", EXTRA_BOUNDS)
+    _steps_device_leads(bt, fc.oracles(form, path.shape, B, seed), path.steps, w)
+    bt.close()
+    w.check()
+
+
+# ---------------------------------------------------------------------------
+# freeze, solve_all and restart through the fused kernels, per formulation
+@pytest.mark.parametrize("form", list(fc.SOLVE))
+def test_batch_form_freeze_and_solve_all(ctx, form):
+    """test_nonfused_solve_all_and_freeze on k0-w16-S1's shape for every
+    formulation that converges: solve_all converges every QP after the largest
+    oracle count with every x within 1e-7 of its oracle's; a second batch
+    stepped by hand converges QP by QP after the oracle's counts, a converged
+    QP keeps its iterate and its f, res, mu, converged bitwise while the
+    others step (freeze = 1 in fused_post_body; k_fused_eval re-evaluates the
+    unchanged iterate), and the twin ends bitwise where solve_all did."""
+    n, m, p = fc.SOLVE_SHAPE
+    B = fc.SOLVE_B
+    seed, iters = fc.SOLVE[form]
+    kw = fc.FORMS[form].kw
+    orcs = fc.oracles(form, fc.SOLVE_SHAPE, B, seed)
+    for o in orcs:
+        while o.iterate()[0] == 0:
+            pass
+    bt = I.Batch(n, m, p, B, ctx, **kw)
+    bt.generate(seed)
+    its, nconv = bt.solve_all(100)
+    assert (its, nconv) == (max(iters), B)
+    worst = max(np.abs(bt.state(i, 0)[:n] - o.vars()[:n]).max() for i, o in enumerate(orcs))
+    print(f"{form} solve_all: worst |x - x_cpu| {worst:.3e} (bound 1e-7)", flush=True)
+    assert worst < 1e-7
+
+    hb = I.Batch(n, m, p, B, ctx, **kw)
+    hb.generate(seed)
+    first = [None] * B  # steps taken when QP i first reports converged
+    frozen = {}
+    keep = [I.SC[k] for k in STATE_KEYS + ("converged",)]
+    for it in range(1, max(iters) + 1):
+        hb.step()
+        sc = hb.batch_scalars()
+        for i in range(B):
+            if sc[i, I.SC["converged"]] != 0.0 and first[i] is None:
+                first[i] = it
+                frozen[i] = (hb.state(i, 0), sc[i, keep].copy())
+            elif first[i] is not None:
+                assert np.array_equal(hb.state(i, 0), frozen[i][0]), (it, i)
+                assert np.array_equal(sc[i, keep], frozen[i][1]), (it, i)
+    assert tuple(first) == iters
+    for i in range(B):
+        assert np.array_equal(hb.state(i, 0), bt.state(i, 0)), i
+    bt.close()
+    hb.close()
+
+
+def _restart_vs_oracle(ctx, form, B):
+    n, m, p = fc.SOLVE_SHAPE
+    seed = fc.SOLVE[form][0]
+    orcs = fc.oracles(form, fc.SOLVE_SHAPE, B, seed)
+    bt = I.Batch(n, m, p, B, ctx, **fc.FORMS[form].kw)
+    bt.generate(seed)
+    w = Worst(f"{form} restart B={B}")
+    restarts = [0] * B
+    for it in range(fc.RESTART_STEPS):
+        pre = [bt.state(i, 0) for i in range(B)]
+        conv = bt.batch_scalars()[:, I.SC["converged"]].copy()
+        bt.step(I.STEP_RESTART_IF_CONVERGED)
+        sc = bt.batch_scalars()
+        for i in range(B):
+            if conv[i]:
+                restarts[i] += 1
+                orcs[i] = fc.FORMS[form].oracle(fc.qp(fc.SOLVE_SHAPE, seed + i))
+            else:
+                orcs[i].set_vars(pre[i])
+            done, rec = orcs[i].iterate()
+            assert done == 0, (it, i)
+            _compare_step(w, orcs[i], rec, sc[i], bt.state(i, 1), bt.state(i, 2), (it, i))
+        assert np.array_equal(sc[:, I.SC["restarts"]], np.array(restarts, dtype=float)), it
+    bt.close()
+    w.check()
+    assert min(restarts) >= 1, restarts
+
+
+@pytest.mark.parametrize("form", list(fc.SOLVE))
+def test_batch_form_restart(ctx, form):
+    """test_nonfused_restart_vs_oracle for k_fused_pre's restart, which copies
+    state_len elements of v and r (a length that differs per formulation) and
+    the saved scalars: STEP_RESTART_IF_CONVERGED for 12 steps, each step
+    against the oracle from the pre-step iterate, or against a fresh oracle at
+    the initial iterate when the QP had converged before the step (fresh: the
+    PenaltyFunction block reads the mu of the previous step, which the restart
+    resets too); SC_RESTARTS exact; every QP restarts at least once.
+
+    This test found that a restart left C x of the converged iterate in place,
+    from which PenaltyFunction's corrector rebuilds its lambda_C row: the
+    corrector direction of the step after a restart was off by 9e-2 relative
+    in lambda_C and 8e-3 in x (the other formulations read no product of the
+    evaluation there).  The restart now restores C x as well."""
+    _restart_vs_oracle(ctx, form, fc.SOLVE_B)
+
+
+def test_penalty_restart_nonfused_kernels(ctx):
+    """The same for PenaltyFunction through k_restart_copy / k_restart_scal: a
+    batch of one QP takes run_step's non-fused branch, as a single Optimizer."""
+    _restart_vs_oracle(ctx, "pen", 1)

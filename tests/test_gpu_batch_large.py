@@ -29,19 +29,20 @@ bitwise; f, res, mu within 1e-12 relative; alpha_aff, mu_aff, sigma, alpha
 and every block of both directions within 1e-9 relative;
 ||dx_gpu - dx_cpu||_inf < 1e-10.  After every step each QP is reset to its
 oracle's iterate.  Every case prints its worst figures before asserting them.
+(The bounds and the comparison helpers live in tests/batch_compare.py, shared
+with tests/test_gpu_batch_forms.py -- whose loop does not reset the batch: the
+reset re-evaluates every QP with the non-fused qp_evaluate.)
 """
 import numpy as np
 import pytest
 
 import batch_large_cases as bc
 import oracle
+from batch_compare import DX_TOL, STATE_KEYS, Worst, _compare_step, _rel
 from golden_io import load, trace
 
 pytestmark = pytest.mark.gpu
 I = pytest.importorskip("ipmz_amd")
-DX_TOL = 1e-10
-STATE_KEYS = ("f", "res", "mu")
-STEP_KEYS = ("alpha_aff", "mu_aff", "sigma", "alpha")
 
 
 @pytest.fixture(scope="module")
@@ -56,45 +57,6 @@ def ctx128():
     c = I.Context(0, nbi=128)
     yield c
     c.close()
-
-
-class Worst:
-    """Worst figure per bound over a case, with where it occurred."""
-
-    BOUNDS = {"f/res/mu rel": 1e-12, "step scalars rel": 1e-9, "direction blocks rel": 1e-9, "|dx - dx_cpu|": DX_TOL}
-
-    def __init__(self, label, bounds=None):
-        self.label = label
-        self.bounds = dict(self.BOUNDS, **(bounds or {}))
-        self.fig = {k: (0.0, None) for k in self.bounds}
-
-    def add(self, key, err, where):
-        err = float("inf") if np.isnan(err) else float(err)
-        if err > self.fig[key][0]:
-            self.fig[key] = (err, where)
-
-    def check(self):
-        for k, (err, where) in self.fig.items():
-            print(f"{self.label}: {k} {err:.3e} (bound {self.bounds[k]:.3e}) at {where}", flush=True)
-        for k, (err, where) in self.fig.items():
-            assert err < self.bounds[k], (self.label, k, err, self.bounds[k], where)
-
-
-def _rel(got, ref):
-    return abs(got - ref) / max(1.0, abs(ref))
-
-
-def _compare_step(w, o, rec, sc, daff, dirv, where):
-    """One QP's step against its oracle's (rec: the oracle's record, sc: the
-    batch's scalars after the step)."""
-    n = o.qp["n"]
-    for k in STEP_KEYS:
-        w.add("step scalars rel", _rel(sc[I.SC[k]], rec[k]), where + (k,))
-    for tag, got, ref in (("daff", daff, o.daff()), ("dir", dirv, o.dir())):
-        sg, sr = o.split(got), o.split(ref)
-        for s in o.order:
-            w.add("direction blocks rel", np.abs(sg[s] - sr[s]).max() / max(1.0, np.abs(sr[s]).max()), where + (tag, s))
-        w.add("|dx - dx_cpu|", np.abs(got[:n] - ref[:n]).max(), where + (tag,))
 
 
 def _steps_vs_oracle(bt, orcs, steps, w):

@@ -105,6 +105,8 @@ def test_formulation_blocked_vs_oracle(ctx, tag, form):
 
 
 def test_formulation_batch_matches_single(ctx):
+    """(Batch steps of every formulation are compared with the oracle in
+    tests/test_gpu_batch_forms.py.)"""
     n, m, B = 96, 24, 3
     form = dict(inequality_handling=I.INEQ_SLACKED_SLACKS, inequality_bounds=I.BOUNDS_LOWER,
                 variable_bounds=I.BOUNDS_UPPER)
@@ -228,6 +230,8 @@ def test_naive_slacks_vs_oracle(ctx, n, m, p, seed):
 
 
 def test_naive_slacks_batch_and_solve(ctx):
+    """(The batch step below is only run; batch steps of NaiveSlacks are
+    compared with the oracle in tests/test_gpu_batch_forms.py.)"""
     n, m, p, B = 64, 16, 8, 3
     bt = I.Batch(n, m, p, B, ctx, inequality_handling=I.INEQ_NAIVE_SLACKS)
     bt.generate(5)
