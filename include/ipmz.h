@@ -60,6 +60,11 @@
  *                                  vectors r_v of the Newton system in, full Newton
  *                                  directions and their maximum steps out, any number of
  *                                  rows from one factor, for a QP or every QP of a batch
+ *   ipmz_qp_newton_adjoint_multi, ipmz_batch_newton_adjoint_multi
+ *                               <- no reference counterpart: the transpose of the map above
+ *                                  (J^T out = -g), cotangents of directions in, cotangents
+ *                                  with respect to the residual vectors out, from the same
+ *                                  factor and blocked solves
  *
  * Conventions
  *   - Plain pointers and sizes only.  "device" pointers are HIP device
@@ -760,6 +765,56 @@ int ipmz_qp_newton_solve_multi(ipmz_qp* qp, int nrhs, const double* R, int64_t l
 int ipmz_batch_newton_solve_multi(ipmz_qp* qp, int nrhs, const double* R, int64_t ldr, int64_t sR, double* Dir,
                                   int64_t ldd, int64_t sD, double* alpha /* device, batch*nrhs, QP-major, may be NULL */,
                                   int* info /* host, batch ints, may be NULL */);
+
+/* The transpose of ipmz_*_newton_solve_multi, for a backward pass through the
+ * Newton step: with Dir = M R the map of that call at the current iterate (M =
+ * -J^{-1}, J the Jacobian of the formulation's Newton system, which is not
+ * symmetric), for every QP q of the solver and every row r < nrhs
+ *
+ *     out = M^T g,   that is   J^T out = -g,
+ *
+ * so that <g, Dir(r)> = <out(g), r> for all g and r.  Row r of QP q of G is at
+ * G + q * sG + r * ldg (device) and holds L = ipmz_qp_state_len(qp) doubles in
+ * the layout of IPMZ_STATE_DAFF: the cotangent of a direction.  Out has the
+ * same shape (q * sO + r * ldo) and receives the cotangent with respect to the
+ * residual vectors r_v, in the layout of IPMZ_STATE_RES; both layouts are the
+ * same Newton order.
+ *
+ * Per row the forward call is b = G_r r (the augmented right-hand side), x =
+ * K^{-1} b, d = E x + F r (the delta_definitions), G_r, E and F element-local
+ * maps of the iterate alone.  K is symmetric, so every blocked K^{-1} is its own
+ * transpose, and out = F^T g + G_r^T K^{-1} (E^T g): E^T g of every row into
+ * the workspace of ipmz_*_newton_solve_multi, the same assembly, factor and
+ * blocked solves by the solver's formulation, then the expansion into every
+ * slot the formulation has.  The coefficients are read off the step's own
+ * expressions, not restated.  There is no step length.
+ *
+ * Arguments, as for the forward pair: nrhs >= 0 (nrhs == 0 still assembles,
+ * factors and returns the info word); ldg >= L, ldo >= L, both even; sG >= nrhs
+ * * ldg, sO >= nrhs * ldo, both even; G and Out 16-byte aligned.  All L
+ * elements of every Out row are written; Out[q][r][L .. ldo) and everything
+ * between nrhs * ldo and sO keep their bits.  G is never written unless it is
+ * Out: Out == G with ldo == ldg and sO == sG is allowed (in place -- a thread
+ * reads every g element it owns before it writes any out element it owns, and
+ * no element has two owners); any other overlap is the caller's error and is
+ * not detected.
+ *
+ * Returns, synchronizes and fills info (host, batch ints, may be NULL) like the
+ * forward pair; a solver that holds one QP forwards from the batch call to the
+ * single one (sG and sO ignored).  The iterate, the step's own slots, the
+ * scalar block, the matrix the fused steps keep across steps, a captured step
+ * graph and all later steps are unchanged, bitwise.  Stream-ordered launches
+ * only, no cross-workgroup waiting, no atomics: a row's result does not depend
+ * on the other rows, a QP's not on the other QPs, equal inputs give equal bits.
+ *
+ * Served and refused exactly like the forward pair: IPMZ_ERR_INVALID for an
+ * enabled normal-equations reduction or mixed precision, IPMZ_EQ_SLACKED_SLACKS
+ * / IPMZ_EQ_NAIVE_SLACKS, bad strides or alignment, IPMZ_EQ_NONE batches with
+ * N > 4096; IPMZ_ERR_STATE before a load, between a load and
+ * ipmz_batch_initialize, and while the context's stream is capturing. */
+int ipmz_qp_newton_adjoint_multi(ipmz_qp* qp, int nrhs, const double* G, int64_t ldg, double* Out, int64_t ldo);
+int ipmz_batch_newton_adjoint_multi(ipmz_qp* qp, int nrhs, const double* G, int64_t ldg, int64_t sG, double* Out,
+                                    int64_t ldo, int64_t sO, int* info /* host, batch ints, may be NULL */);
 
 /* Phase timing (HIP events on the context stream; eager launches only).
  * ms: host array of IPMZ_PH_COUNT floats, cumulative since enable. */

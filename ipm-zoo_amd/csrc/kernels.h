@@ -46,7 +46,8 @@ namespace ipmz {
 //         its table says; both bits = the unsplit solve (all three bitwise alike,
 //         tests/test_gpu_solve_split.py),
 // 2097152 / 4194304 = ipmz_*_newton_solve_multi's element-wise kernels take 1 / 8 rows per thread instead
-//         of IPMZ_NEWTON_MULTI_RPG; both bits = 2 (A/B, tools/newton_multi_bench.py; the same bits in every row)
+//         of IPMZ_NEWTON_MULTI_RPG; both bits = 2 (A/B, tools/newton_multi_bench.py; the same bits in every row);
+//         ipmz_*_newton_adjoint_multi's two kernels launch the same way,
 enum { IPMZ_INJECT_SOLVE = 1, IPMZ_INJECT_PANEL = 2, IPMZ_INJECT_GRAPH_FORKS = 4, IPMZ_DEBUG_CONVERT_ONLY = 16,
        IPMZ_DEBUG_ONE_STREAM = 32, IPMZ_DEBUG_TRACE = 64, IPMZ_DEBUG_F32_ENGINE = 128,
        IPMZ_DEBUG_NO_FOURTH = 256, IPMZ_DEBUG_IR_FULL = 512,
@@ -492,6 +493,13 @@ hipError_t qp_backsub_multi(const QPBatch& qb, const double* R, int64_t ldr, int
                             int64_t sW, double* D, int64_t ldd, int64_t sD, int nrhs, hipStream_t st);
 hipError_t qp_ratio_multi(const QPBatch& qb, const double* D, int64_t ldd, int64_t sD, double* alpha, int nrhs,
                           hipStream_t st);
+// The transposed map of the first two (ipmz_*_newton_adjoint_multi), same grid and row groups: row r of QP z of
+// Cot (the caller's G: a cotangent of a direction, Newton order) -> E^T g in row r of W; the solved W and Cot ->
+// M^T g in row r of Out (may be Cot, same strides), every slot the formulation has.
+hipError_t qp_adj_reduce_multi(const QPBatch& qb, const double* Cot, int64_t ldg, int64_t sG, double* W, int64_t ldw,
+                               int64_t sW, int nrhs, hipStream_t st);
+hipError_t qp_adj_expand_multi(const QPBatch& qb, const double* Cot, int64_t ldg, int64_t sG, const double* W,
+                               int64_t ldw, int64_t sW, double* Out, int64_t ldo, int64_t sO, int nrhs, hipStream_t st);
 hipError_t qp_mu_aff(const QPBatch& qb, hipStream_t st);
 hipError_t qp_corrector_residuals(const QPBatch& qb, hipStream_t st);
 hipError_t qp_update(const QPBatch& qb, int freeze, hipStream_t st);

@@ -953,6 +953,198 @@ hipError_t qp_backsub_multi(const QPBatch& qb, const double* R, int64_t ldr, int
   });
   return hipGetLastError();
 }
+// ---------------------------------------------------------------------------
+// The transposed map (ipmz_*_newton_adjoint_multi).  Per row the forward call
+// is b = G_r r (rhs_elem), x = K^{-1} b, d = E x + F r (backsub_elem), so
+// Dir = M r with M = F + E K^{-1} G_r; K is symmetric and G_r, E, F couple only
+// the slots element t owns at its own index, so
+//   M^T g = F^T g + G_r^T K^{-1} (E^T g)
+// is two element-wise kernels on the same grid around the same solves:
+//   k_adj_reduce_multi  row of G -> c = E^T g in the row of W
+//   k_adj_expand_multi  the solved row y of W and the row of G ->
+//                       out(slot, i) = sum_dslot F[dslot][slot] g(dslot, i) + G_r[slot] y(t)
+// The coefficients are not restated: rhs_elem / backsub_elem are linear and
+// homogeneous in (r, x), so two more accessors read them off the formulas.
+//   AdjReduceIO  val_t = double, r = 0, x(t) = 1: what backsub_elem assigns to
+//                d(slot, i) is E[slot]; the assignment adds E[slot] g(slot, i)
+//                to c for the RP rows.
+//   AdjExpandIO  val_t = RowVec<ADJ_LANES>, one lane per residual slot of the
+//                element (adj_lane: at most 6 meet in one), r(slot, i) the unit
+//                vector of the slot's lane, x = 0: what rhs_elem assigns to b(t)
+//                is G_r by lane, what backsub_elem assigns to d(slot, i) is row
+//                `slot` of F by lane; that assignment adds F[slot][lane]
+//                g(slot, i) to the lane's accumulator for the RP rows.
+// Both evaluate the coefficients once per element for the RP rows of the group.
+// The slots an element has are the ones the formulas touched (present); only
+// those are written.  A thread loads every g element it owns (in the d
+// assignments) before it stores any out element, so Out may be the block of
+// cotangents itself (Cot below: the caller's G, which is a slot's name here).
+#define ADJ_LANES 6
+__device__ __forceinline__ constexpr int adj_lane(int slot) {
+  // t < n: x y z lambda_y lambda_z | inequality rows: s g h lambda_A lambda_g lambda_h | equality rows: p lambda_C
+  return slot == X || slot == S || slot == P ? 0
+         : slot == Y || slot == G || slot == LC ? 1
+         : slot == Z || slot == H ? 2
+         : slot == LY || slot == LA ? 3
+         : slot == LZ || slot == LG ? 4
+                                    : 5;
+}
+// element e of cnt rows of the cotangent block, ld apart (rows past cnt: the last valid one again)
+template <int RP>
+__device__ __forceinline__ RowVec<RP> adj_load(const double* p, int64_t ld, int cnt) {
+  RowVec<RP> a;
+#pragma unroll
+  for (int k = 0; k < RP; ++k) a.v[k] = p[(k < cnt ? k : cnt - 1) * ld];
+  return a;
+}
+
+template <int RP>
+struct AdjReduceRef {
+  const double* g;
+  int64_t ldg;
+  int cnt;
+  RowVec<RP>& c;
+  __device__ __forceinline__ void operator=(double coef) const { c = c + coef * adj_load<RP>(g, ldg, cnt); }
+};
+template <int RP>
+struct AdjReduceIO {
+  typedef double val_t;
+  const QPDev& q;
+  const double* Cot;
+  int64_t ldg;
+  int cnt;
+  RowVec<RP>& c;
+  __device__ __forceinline__ double r(int, int) const { return 0.0; }
+  __device__ __forceinline__ double x(int) const { return 1.0; }
+  __device__ __forceinline__ AdjReduceRef<RP> d(int slot, int i) const {
+    return AdjReduceRef<RP>{Cot + (q.r[slot] - q.r[0]) + i, ldg, cnt, c};
+  }
+  __device__ __forceinline__ double zero() const { return 0.0; }
+};
+
+template <int RP>
+struct AdjExpandState {
+  RowVec<RP> acc[ADJ_LANES];  // by lane: sum over d slots of F[dslot][lane] g(dslot, i)
+  RowVec<ADJ_LANES> gr;       // G_r by lane
+  unsigned present;           // bit per slot the element has
+  int i;                      // ... all at this index
+};
+struct AdjCaptureRef {
+  RowVec<ADJ_LANES>& gr;
+  __device__ __forceinline__ void operator=(const RowVec<ADJ_LANES>& a) const { gr = a; }
+};
+template <int RP>
+struct AdjExpandRef {
+  const double* g;
+  int64_t ldg;
+  int cnt;
+  AdjExpandState<RP>& s;
+  __device__ __forceinline__ void operator=(const RowVec<ADJ_LANES>& coef) const {
+    const RowVec<RP> gv = adj_load<RP>(g, ldg, cnt);
+#pragma unroll
+    for (int l = 0; l < ADJ_LANES; ++l) s.acc[l] = s.acc[l] + coef.v[l] * gv;
+  }
+};
+template <int RP>
+struct AdjExpandIO {
+  typedef RowVec<ADJ_LANES> val_t;
+  const QPDev& q;
+  const double* Cot;
+  int64_t ldg;
+  int cnt;
+  AdjExpandState<RP>& s;
+  __device__ __forceinline__ void own(int slot, int i) const {
+    s.present |= 1u << slot;
+    s.i = i;
+  }
+  __device__ __forceinline__ val_t r(int slot, int i) const {
+    own(slot, i);
+    val_t a;
+#pragma unroll
+    for (int l = 0; l < ADJ_LANES; ++l) a.v[l] = l == adj_lane(slot) ? 1.0 : 0.0;
+    return a;
+  }
+  __device__ __forceinline__ AdjCaptureRef b(int) const { return AdjCaptureRef{s.gr}; }
+  __device__ __forceinline__ val_t x(int) const { return zero(); }
+  __device__ __forceinline__ AdjExpandRef<RP> d(int slot, int i) const {
+    own(slot, i);
+    return AdjExpandRef<RP>{Cot + (q.r[slot] - q.r[0]) + i, ldg, cnt, s};
+  }
+  __device__ __forceinline__ val_t zero() const {
+    val_t a;
+#pragma unroll
+    for (int l = 0; l < ADJ_LANES; ++l) a.v[l] = 0.0;
+    return a;
+  }
+};
+
+template <int RP>
+__global__ __launch_bounds__(NT) void k_adj_reduce_multi(const QPDev* __restrict__ qs, const double* __restrict__ Cot,
+                                                         int64_t ldg, int64_t sG, double* __restrict__ W, int64_t ldw,
+                                                         int64_t sW, int row0, int nrhs) {
+  const QPDev& q = qs[blockIdx.z];
+  const int t = blockIdx.x * NT + threadIdx.x;
+  const int r0 = row0 + blockIdx.y * RP;
+  if (t >= q.N || r0 >= nrhs) return;
+  const int cnt = nrhs - r0 < RP ? nrhs - r0 : RP;
+  Cot += blockIdx.z * sG + (int64_t)r0 * ldg;
+  W += blockIdx.z * sW + (int64_t)r0 * ldw;
+  RowVec<RP> c;
+#pragma unroll
+  for (int k = 0; k < RP; ++k) c.v[k] = 0.0;
+  backsub_elem(q, AdjReduceIO<RP>{q, Cot, ldg, cnt, c}, t);
+  RowRef<RP>{W + t, ldw, cnt} = c;
+}
+// (Cot, the caller's G, and Out without __restrict__: Out may be Cot)
+template <int RP>
+__global__ __launch_bounds__(NT) void k_adj_expand_multi(const QPDev* __restrict__ qs, const double* Cot, int64_t ldg,
+                                                         int64_t sG, const double* __restrict__ W, int64_t ldw,
+                                                         int64_t sW, double* Out, int64_t ldo, int64_t sO, int row0,
+                                                         int nrhs) {
+  const QPDev& q = qs[blockIdx.z];
+  const int t = blockIdx.x * NT + threadIdx.x;
+  const int r0 = row0 + blockIdx.y * RP;
+  if (t >= q.N || r0 >= nrhs) return;
+  const int cnt = nrhs - r0 < RP ? nrhs - r0 : RP;
+  Cot += blockIdx.z * sG + (int64_t)r0 * ldg;
+  W += blockIdx.z * sW + (int64_t)r0 * ldw;
+  Out += blockIdx.z * sO + (int64_t)r0 * ldo;
+  AdjExpandState<RP> s;
+  s.present = 0u;
+  s.i = 0;
+#pragma unroll
+  for (int l = 0; l < ADJ_LANES; ++l) {
+    s.gr.v[l] = 0.0;
+#pragma unroll
+    for (int k = 0; k < RP; ++k) s.acc[l].v[k] = 0.0;
+  }
+  const AdjExpandIO<RP> io{q, Cot, ldg, cnt, s};
+  rhs_elem(q, io, t);
+  backsub_elem(q, io, t);  // the last load of Cot
+  const RowVec<RP> y = adj_load<RP>(W + t, ldw, cnt);
+#pragma unroll
+  for (int slot = 0; slot < NSLOT; ++slot)
+    if (s.present >> slot & 1u)
+      RowRef<RP>{Out + (q.r[slot] - q.r[0]) + s.i, ldo, cnt} = s.acc[adj_lane(slot)] + s.gr.v[adj_lane(slot)] * y;
+}
+
+hipError_t qp_adj_reduce_multi(const QPBatch& qb, const double* Cot, int64_t ldg, int64_t sG, double* W, int64_t ldw,
+                               int64_t sW, int nrhs, hipStream_t st) {
+  newton_multi_launches(qb, nrhs, [&](auto rp, int row0, dim3 grid) {
+    hipLaunchKernelGGL((k_adj_reduce_multi<decltype(rp)::value>), grid, dim3(NT), 0, st, qb.d, Cot, ldg, sG, W, ldw, sW,
+                       row0, nrhs);
+  });
+  return hipGetLastError();
+}
+hipError_t qp_adj_expand_multi(const QPBatch& qb, const double* Cot, int64_t ldg, int64_t sG, const double* W,
+                               int64_t ldw, int64_t sW, double* Out, int64_t ldo, int64_t sO, int nrhs, hipStream_t st) {
+  newton_multi_launches(qb, nrhs, [&](auto rp, int row0, dim3 grid) {
+    hipLaunchKernelGGL((k_adj_expand_multi<decltype(rp)::value>), grid, dim3(NT), 0, st, qb.d, Cot, ldg, sG, W, ldw, sW,
+                       Out, ldo, sO, row0, nrhs);
+  });
+  return hipGetLastError();
+}
+
 hipError_t qp_ratio_multi(const QPBatch& qb, const double* D, int64_t ldd, int64_t sD, double* alpha, int nrhs,
                           hipStream_t st) {
   if (nrhs <= 0) return hipSuccess;

@@ -53,7 +53,8 @@ struct ipmz_qp {
   GrowBuf mws;
   // ipmz_qp_kkt_solve_mixed: the multi-right-hand-side workspace, for the largest nrhs seen
   GrowBuf mmws;
-  // ipmz_*_newton_solve_multi: the reduced right-hand sides, B x nrhs x round_up(N, 2) doubles, for the largest nrhs seen
+  // ipmz_*_newton_solve_multi / ipmz_*_newton_adjoint_multi: the reduced right-hand sides, B x nrhs x round_up(N, 2)
+  // doubles, for the largest nrhs seen
   GrowBuf nmws;
   // normal-equations reduction (C2)
   bool normal = false;
@@ -1225,16 +1226,19 @@ int ipmz_qp_kkt_solve_bk(ipmz_qp* s, int nrhs, double* B, int64_t ldb) {
 // reduction of every row into the solver's workspace, the formulation's own
 // factor and blocked solve there (kkt_enqueue), backsub_elem's
 // back-substitution into Dir and ratio_elem's step length per row.
-static int newton_multi(ipmz_qp* s, const char* who, int nrhs, const double* R, int64_t ldr, int64_t sR, double* Dir,
-                        int64_t ldd, int64_t sD, double* alpha, int* info) {
+// adjoint: the transposed map instead (ipmz_*_newton_adjoint_multi) -- R is the
+// block of cotangents G, Dir is Out = M^T G: E^T of every row into the
+// workspace, the same factor and solves (K is symmetric), then F^T g + G_r^T y.
+static int newton_multi(ipmz_qp* s, const char* who, bool adjoint, int nrhs, const double* R, int64_t ldr, int64_t sR,
+                        double* Dir, int64_t ldd, int64_t sD, double* alpha, int* info) {
   const std::string w(who);
   if (s->normal) return fail(IPMZ_ERR_INVALID, w + ": the normal-equations reduction is enabled (augmented system only)");
   if (s->mixed) return fail(IPMZ_ERR_INVALID, w + ": mixed precision is enabled (fp64 factors only)");
   if (s->eqss)
     return fail(IPMZ_ERR_INVALID, w + ": EqualityHandling::SlackedSlacks / NaiveSlacks keep a permuted, merged view of "
                                       "the Newton order on the device; not served");
-  int rc = check_rhs_block(s, w, nrhs, "R", R, ldr, sR, s->state_len, "state_len");
-  if (!rc) rc = check_rhs_block(s, w, nrhs, "Dir", Dir, ldd, sD, s->state_len, "state_len");
+  int rc = check_rhs_block(s, w, nrhs, adjoint ? "G" : "R", R, ldr, sR, s->state_len, "state_len");
+  if (!rc) rc = check_rhs_block(s, w, nrhs, adjoint ? "Out" : "Dir", Dir, ldd, sD, s->state_len, "state_len");
   if (rc) return rc;
   HIP_OK(hipSetDevice(s->ctx->device));
   if ((rc = not_capturing(s->ctx, who))) return rc;
@@ -1248,10 +1252,13 @@ static int newton_multi(ipmz_qp* s, const char* who, int nrhs, const double* R, 
   if ((rc = grow(s, s->nmws, (size_t)(sW * s->B) * sizeof(double)))) return rc;
   hipStream_t st = s->ctx->stream;
   double* W = reinterpret_cast<double*>(s->nmws.p);
-  if (nrhs > 0) HIP_OK(qp_rhs_multi(s->qb, R, ldr, sR, W, ldw, sW, nrhs, st));
+  if (nrhs > 0)
+    HIP_OK(adjoint ? qp_adj_reduce_multi(s->qb, R, ldr, sR, W, ldw, sW, nrhs, st)
+                   : qp_rhs_multi(s->qb, R, ldr, sR, W, ldw, sW, nrhs, st));
   if ((rc = kkt_enqueue(s, W, ldw, sW, nrhs))) return rc;
   if (nrhs > 0) {
-    HIP_OK(qp_backsub_multi(s->qb, R, ldr, sR, W, ldw, sW, Dir, ldd, sD, nrhs, st));
+    HIP_OK(adjoint ? qp_adj_expand_multi(s->qb, R, ldr, sR, W, ldw, sW, Dir, ldd, sD, nrhs, st)
+                   : qp_backsub_multi(s->qb, R, ldr, sR, W, ldw, sW, Dir, ldd, sD, nrhs, st));
     if (alpha) HIP_OK(qp_ratio_multi(s->qb, Dir, ldd, sD, alpha, nrhs, st));
   }
   rc = kkt_finish(s, who, info);  // synchronizes
@@ -1266,7 +1273,7 @@ int ipmz_qp_newton_solve_multi(ipmz_qp* s, int nrhs, const double* R, int64_t ld
   if (s->B != 1)
     return fail(IPMZ_ERR_INVALID, "ipmz_qp_newton_solve_multi: single QPs only, this is a batch "
                                   "(ipmz_batch_newton_solve_multi)");
-  return newton_multi(s, "ipmz_qp_newton_solve_multi", nrhs, R, ldr, 0, Dir, ldd, 0, alpha, nullptr);
+  return newton_multi(s, "ipmz_qp_newton_solve_multi", false, nrhs, R, ldr, 0, Dir, ldd, 0, alpha, nullptr);
 }
 
 int ipmz_batch_newton_solve_multi(ipmz_qp* s, int nrhs, const double* R, int64_t ldr, int64_t sR, double* Dir,
@@ -1277,7 +1284,26 @@ int ipmz_batch_newton_solve_multi(ipmz_qp* s, int nrhs, const double* R, int64_t
     if (info) info[0] = rc;
     return rc;
   }
-  return newton_multi(s, "ipmz_batch_newton_solve_multi", nrhs, R, ldr, sR, Dir, ldd, sD, alpha, info);
+  return newton_multi(s, "ipmz_batch_newton_solve_multi", false, nrhs, R, ldr, sR, Dir, ldd, sD, alpha, info);
+}
+
+int ipmz_qp_newton_adjoint_multi(ipmz_qp* s, int nrhs, const double* G, int64_t ldg, double* Out, int64_t ldo) {
+  if (!s) return fail(IPMZ_ERR_INVALID, "null qp");
+  if (s->B != 1)
+    return fail(IPMZ_ERR_INVALID, "ipmz_qp_newton_adjoint_multi: single QPs only, this is a batch "
+                                  "(ipmz_batch_newton_adjoint_multi)");
+  return newton_multi(s, "ipmz_qp_newton_adjoint_multi", true, nrhs, G, ldg, 0, Out, ldo, 0, nullptr, nullptr);
+}
+
+int ipmz_batch_newton_adjoint_multi(ipmz_qp* s, int nrhs, const double* G, int64_t ldg, int64_t sG, double* Out,
+                                    int64_t ldo, int64_t sO, int* info) {
+  if (!s) return fail(IPMZ_ERR_INVALID, "null qp");
+  if (s->B == 1) {
+    const int rc = ipmz_qp_newton_adjoint_multi(s, nrhs, G, ldg, Out, ldo);
+    if (info) info[0] = rc;
+    return rc;
+  }
+  return newton_multi(s, "ipmz_batch_newton_adjoint_multi", true, nrhs, G, ldg, sG, Out, ldo, sO, nullptr, info);
 }
 
 // the QP's mixed-precision workspace, allocated once (a captured step keeps its addresses)

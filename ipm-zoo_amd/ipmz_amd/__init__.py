@@ -54,6 +54,7 @@ EXPORTS = [
     "ipmz_bk_factor_batch", "ipmz_bk_batch_solve_workspace_bytes", "ipmz_bk_prepare_solve_batch",
     "ipmz_bk_solve_multi_batch", "ipmz_batch_kkt_solve_bk",
     "ipmz_qp_newton_solve_multi", "ipmz_batch_newton_solve_multi",
+    "ipmz_qp_newton_adjoint_multi", "ipmz_batch_newton_adjoint_multi",
     "ipmz_batch_load_device", "ipmz_batch_copy_state",
 ]
 SOLVE_MULTI_PANEL = 256  # include/ipmz.h IPMZ_SOLVE_MULTI_PANEL: column panel of the blocked multi-rhs solve
@@ -218,6 +219,8 @@ def _load():
         "ipmz_batch_kkt_solve_bk": ([_VP, _I, _VP, _I64, _I64, ctypes.POINTER(_I)], _I),
         "ipmz_qp_newton_solve_multi": ([_VP, _I, _VP, _I64, _VP, _I64, _VP], _I),
         "ipmz_batch_newton_solve_multi": ([_VP, _I, _VP, _I64, _I64, _VP, _I64, _I64, _VP, ctypes.POINTER(_I)], _I),
+        "ipmz_qp_newton_adjoint_multi": ([_VP, _I, _VP, _I64, _VP, _I64], _I),
+        "ipmz_batch_newton_adjoint_multi": ([_VP, _I, _VP, _I64, _I64, _VP, _I64, _I64, ctypes.POINTER(_I)], _I),
         "ipmz_batch_load_device": ([_VP, ctypes.POINTER(_QPDeviceData)], _I),
         "ipmz_batch_copy_state": ([_VP, _I, _VP, _I64], _I),
     }
@@ -748,6 +751,15 @@ class Optimizer:
         return _check(lib.ipmz_qp_newton_solve_multi(self.h, nrhs, _VP(R_ptr), ldr, _VP(D_ptr), ldd, _VP(alpha_ptr)),
                       "ipmz_qp_newton_solve_multi")
 
+    def newton_adjoint(self, G_ptr, Out_ptr, nrhs, ldg, ldo):
+        """The transpose of newton_solve at the current iterate: row r of G (device, nrhs rows of
+        state_len doubles in the order of daff(), stride ldg), the cotangent of a direction -> the
+        cotangent with respect to the residual row, J^T out = -g, in row r of Out (the order of
+        residuals(), stride ldo; Out may be G).  <g, newton_solve(r)> = <newton_adjoint(g), r>.
+        The same factor and blocked solves; returns the factor's info."""
+        return _check(lib.ipmz_qp_newton_adjoint_multi(self.h, nrhs, _VP(G_ptr), ldg, _VP(Out_ptr), ldo),
+                      "ipmz_qp_newton_adjoint_multi")
+
     def set_timing(self, on=True):
         _check(lib.ipmz_qp_set_timing(self.h, 1 if on else 0), "ipmz_qp_set_timing")
 
@@ -860,6 +872,15 @@ class Batch(Optimizer):
         rc = _check(lib.ipmz_batch_newton_solve_multi(self.h, nrhs, _VP(R_ptr), ldr, sR, _VP(D_ptr), ldd, sD,
                                                       _VP(alpha_ptr), info.ctypes.data_as(ctypes.POINTER(_I))),
                     "ipmz_batch_newton_solve_multi")
+        return (rc, info) if self.equality_handling == EQ_NONE else rc
+
+    def newton_adjoint_all(self, G_ptr, Out_ptr, nrhs, ldg, sG, ldo, sO):
+        """newton_adjoint for every QP of the batch at once: QP q's rows at G + q * sG and
+        Out + q * sO.  Returns what newton_solve_all returns."""
+        info = np.zeros(self.batch, dtype=np.int32)
+        rc = _check(lib.ipmz_batch_newton_adjoint_multi(self.h, nrhs, _VP(G_ptr), ldg, sG, _VP(Out_ptr), ldo, sO,
+                                                        info.ctypes.data_as(ctypes.POINTER(_I))),
+                    "ipmz_batch_newton_adjoint_multi")
         return (rc, info) if self.equality_handling == EQ_NONE else rc
 
     def batch_scalars(self):
