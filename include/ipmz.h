@@ -65,6 +65,11 @@
  *                                  (J^T out = -g), cotangents of directions in, cotangents
  *                                  with respect to the residual vectors out, from the same
  *                                  factor and blocked solves
+ *   ipmz_batch_data_vjp         <- no reference counterpart: that cotangent contracted with
+ *                                  d r_v / d (Q, c, A, l_A, u_A, C, d, l_x, u_x), the gradient
+ *                                  with respect to the problem data in the strided blocks
+ *                                  ipmz_batch_load_device reads (per QP, or summed over the
+ *                                  batch for shared blocks)
  *
  * Conventions
  *   - Plain pointers and sizes only.  "device" pointers are HIP device
@@ -815,6 +820,79 @@ int ipmz_batch_newton_solve_multi(ipmz_qp* qp, int nrhs, const double* R, int64_
 int ipmz_qp_newton_adjoint_multi(ipmz_qp* qp, int nrhs, const double* G, int64_t ldg, double* Out, int64_t ldo);
 int ipmz_batch_newton_adjoint_multi(ipmz_qp* qp, int nrhs, const double* G, int64_t ldg, int64_t sG, double* Out,
                                     int64_t ldo, int64_t sO, int* info /* host, batch ints, may be NULL */);
+
+/* The last link of a backward pass through a solved QP: the cotangent with
+ * respect to the residual vectors r_v (what the adjoint pair above returns)
+ * contracted with d r_v / d (Q, c, A, l_A, u_A, C, d, l_x, u_x) at the current
+ * iterate -- the gradient of a loss with respect to the problem data.  At a
+ * fixed iterate and a fixed mu every r_v is affine in the data ("shorthand
+ * definitions" of tests/golden/formulations.txt), so with w the cotangent row
+ * of a QP (J^T w = -g, the adjoint's own sign: dz = -J^{-1} r_theta dtheta)
+ *
+ *     dL/dtheta = (d r / d theta)^T w.
+ *
+ * In the default form: gc = w_x; gQ[i][j] = w_x[i] x[j]; gA[i][j] =
+ * w_lambda_A[i] x[j] + lambda_A[i] w_x[j]; gC the same with lambda_C; gd =
+ * -w_lambda_C; g l_x = w_lambda_y, g u_x = -w_lambda_z, g l_A = w_lambda_g,
+ * g u_A = -w_lambda_h.  IPMZ_INEQ_SLACKS: the bounds enter the complementarity
+ * rows multiplied by the duals (g l_x = -lambda_y w_lambda_y, g u_x = lambda_z
+ * w_lambda_z, and so for l_A, u_A).  IPMZ_INEQ_NAIVE_SLACKS: A x sits in
+ * r_lambda_g and r_lambda_h and A^T multiplies (lambda_h - lambda_g).  A bound
+ * the formulation does not have gets a zero gradient.  Conventions: mu is a
+ * constant of the call (the data's effect on IPMZ_SC_MU is not differentiated;
+ * it matters only for penalty equalities with IPMZ_INEQ_SLACKS); the n^2
+ * entries of Q are independent, gQ = w_x x^T is NOT symmetrised (a caller who
+ * keeps Q symmetric takes (gQ + gQ^T) / 2); IPMZ_EQ_REGULARIZATION's delta is
+ * not data.
+ *
+ * W (device): one row per QP at W + q * sW, ipmz_qp_state_len doubles in the
+ * layout of IPMZ_STATE_RES -- row 0 of Out of ipmz_batch_newton_adjoint_multi
+ * with sW = sO.  A solver of one QP ignores sW.  No alignment rule for W.
+ *
+ * ipmz_qp_device_grad is ipmz_qp_device_data with writable blocks and the same
+ * rules: strides in elements; a NULL block is not wanted; blocks of dimension 0
+ * are ignored whatever they hold; a row stride is at least n; a non-zero QP
+ * stride is at least the block's extent; no stride is negative; no alignment
+ * rule (16-byte stores where the pointer and strides allow them, element by
+ * element otherwise, with equal bits).  Nothing outside the blocks (row
+ * padding, the space between QPs) is written.  QP stride non-zero: QP q's block
+ * receives that QP's gradient, overwritten, never accumulated.  QP stride 0
+ * (batches): the ONE block receives the sum over all QPs -- the gradient of
+ * data that ipmz_batch_load_device shared.  Shared vector blocks: the batch is cut
+ * into 64 contiguous ranges, each summed in QP order, the ranges' sums then
+ * added in range order; shared matrix blocks are a product with the batch as
+ * the inner dimension on fp64 MFMA, chunks of 64 QPs each summed in QP order
+ * (in groups of four), the chunks' partials then summed in chunk order: an
+ * order fixed by the shape alone, no atomics, equal inputs give equal bits.  The partials live
+ * in a workspace of the solver (ceil(batch / 64) * max(n, m, p) * n doubles,
+ * allocated when a shared matrix block is first asked for, freed with the
+ * solver).
+ *
+ * Asynchronous on the context's stream, no synchronize; the iterate, the
+ * step's slots, the scalars, the kept KKT matrix, a captured step graph and all
+ * later steps are unchanged, bitwise: the call reads the iterate and W only.
+ *
+ * Served and refused like the adjoint pair: IPMZ_ERR_INVALID for a null qp, W
+ * or grad, bad strides, IPMZ_EQ_SLACKED_SLACKS / IPMZ_EQ_NAIVE_SLACKS, an
+ * enabled normal-equations reduction or mixed precision; IPMZ_ERR_STATE before
+ * a load, between a load and ipmz_batch_initialize, and when the workspace
+ * would have to be allocated while the context's stream is capturing;
+ * IPMZ_ERR_NOMEM when it cannot be had. */
+typedef struct ipmz_qp_device_grad {
+  double* Q;    /* n rows of n */
+  int64_t ldq, sQ;
+  double* A;    /* m rows of n */
+  int64_t lda, sA;
+  double* C;    /* p rows of n */
+  int64_t ldc, sC;
+  double *c, *l_x, *u_x; /* n each */
+  int64_t sc, slx, sux;
+  double *l_A, *u_A;     /* m each */
+  int64_t slA, suA;
+  double* d;    /* p */
+  int64_t sd;
+} ipmz_qp_device_grad;
+int ipmz_batch_data_vjp(ipmz_qp* qp, const double* W, int64_t sW, const ipmz_qp_device_grad* grad);
 
 /* Phase timing (HIP events on the context stream; eager launches only).
  * ms: host array of IPMZ_PH_COUNT floats, cumulative since enable. */

@@ -181,6 +181,20 @@ inline BkBatchWs bk_batch_ws(char* base, int N, int batch) {
   return w;
 }
 
+// ipmz_batch_data_vjp's shared matrix blocks: the chunks' partial products
+// (grad.hip; elems = qp_grad_part_elems of the batch)
+struct VjpWs {
+  double* part = nullptr;
+  int64_t total = 0;
+};
+inline VjpWs vjp_ws(char* base, int64_t elems) {
+  VjpWs w;
+  Carver c{base};
+  w.part = c.take<double>(elems);
+  w.total = c.off;
+  return w;
+}
+
 // the workspace whose sticky error words the next ipmz_ctx_sync checks (pe:
 // a panel factor's, may be null; se: a persistent solve's)
 inline void watch(ipmz_ctx* ctx, const unsigned* pe, const unsigned* se) {

@@ -590,4 +590,27 @@ hipError_t qp_io_pack(const QPBatch& qb, const QpIoData& in, hipStream_t st);
 // (IPMZ_STATE_*) in the reference's Newton order; one launch, no allocation
 hipError_t qp_gather_state(const QPBatch& qb, int which, double* dst, int64_t ld, hipStream_t st);
 
+// grad.hip -------------------------------------------------------------------
+// A caller's gradient blocks in device memory (ipmz_qp_device_grad with the
+// blocks this call does not write -- not wanted, or of dimension 0 -- null):
+// QpIoData's description with writable blocks.  A QP stride of 0 (batches) is
+// one block that receives the sum over the QPs.
+struct QpGradOut {
+  double *Q, *A, *C;
+  int64_t ldq, sQ, lda, sA, ldc, sC;
+  double *c, *lx, *ux, *lA, *uA, *d;
+  int64_t sc, slx, sux, slA, suA, sd;
+};
+// QPs per chunk of the shared matrix blocks' sum over the batch: every chunk's
+// partial product is one tile set of the workspace, summed in chunk order
+#define IPMZ_VJP_KCHUNK 64
+// elements of that workspace: ceil(B / IPMZ_VJP_KCHUNK) x max(n, m, p) x n (one matrix block at a time)
+int64_t qp_grad_part_elems(const QPBatch& qb);
+// (d r / d data)^T w of every QP, w = the row at W + z sW in the layout of
+// IPMZ_STATE_RES, into the blocks of o; part: the workspace above, read and
+// written only when a matrix block is shared (may be null otherwise).
+// Stream-ordered launches, no atomics; reads the iterate and W only
+hipError_t qp_data_vjp(const QPBatch& qb, const double* W, int64_t sW, const QpGradOut& o, double* part,
+                       hipStream_t st);
+
 }  // namespace ipmz

@@ -56,6 +56,8 @@ struct ipmz_qp {
   // ipmz_*_newton_solve_multi / ipmz_*_newton_adjoint_multi: the reduced right-hand sides, B x nrhs x round_up(N, 2)
   // doubles, for the largest nrhs seen
   GrowBuf nmws;
+  // ipmz_batch_data_vjp: the shared matrix blocks' partial products (vjp_ws), when one is first asked for
+  GrowBuf vjpws;
   // normal-equations reduction (C2)
   bool normal = false;
   // EqualityHandling::None: Bunch-Kaufman factor (pivots per QP)
@@ -1576,6 +1578,76 @@ int ipmz_batch_copy_state(ipmz_qp* s, int which, double* dst, int64_t ld) {
   if (!s->loaded) return fail(IPMZ_ERR_STATE, "ipmz_batch_copy_state: load or generate the QP first");
   HIP_OK(hipSetDevice(s->ctx->device));
   HIP_OK(qp_gather_state(s->qb, which, dst, ld, s->ctx->stream));
+  return IPMZ_OK;
+}
+
+// (d r / d data)^T w into a caller's blocks (grad.hip): ipmz_batch_load_device's
+// block description and checks with writable blocks, refused like the adjoint
+// pair (newton_multi).  Launches only: no synchronize, and an allocation only
+// when a shared matrix block is first asked for.
+int ipmz_batch_data_vjp(ipmz_qp* s, const double* W, int64_t sW, const ipmz_qp_device_grad* grad) {
+  const std::string who = "ipmz_batch_data_vjp";
+  if (!s || !W || !grad) return fail(IPMZ_ERR_INVALID, who + ": null argument");
+  if (s->normal) return fail(IPMZ_ERR_INVALID, who + ": the normal-equations reduction is enabled (augmented system only)");
+  if (s->mixed) return fail(IPMZ_ERR_INVALID, who + ": mixed precision is enabled (fp64 factors only)");
+  if (s->eqss)
+    return fail(IPMZ_ERR_INVALID, who + ": EqualityHandling::SlackedSlacks / NaiveSlacks keep a permuted, merged view of "
+                                        "the Newton order on the device; not served");
+  if (!s->loaded) return fail(IPMZ_ERR_STATE, who + ": load (and initialize) the QP first");
+  if (s->B > 1 && sW < s->state_len)
+    return fail(IPMZ_ERR_INVALID, who + ": W: QP stride " + std::to_string(sW) + " < state_len");
+  const int n = s->n, m = s->m, p = s->p;
+  // blocks of dimension 0 are ignored whatever they hold
+  QpGradOut o{};
+  o.Q = grad->Q, o.ldq = grad->ldq, o.sQ = grad->sQ;
+  o.c = grad->c, o.sc = grad->sc;
+  o.lx = grad->l_x, o.slx = grad->slx;
+  o.ux = grad->u_x, o.sux = grad->sux;
+  if (m) {
+    o.A = grad->A, o.lda = grad->lda, o.sA = grad->sA;
+    o.lA = grad->l_A, o.slA = grad->slA;
+    o.uA = grad->u_A, o.suA = grad->suA;
+  }
+  if (p) {
+    o.C = grad->C, o.ldc = grad->ldc, o.sC = grad->sC;
+    o.d = grad->d, o.sd = grad->sd;
+  }
+  struct Block {
+    const char* name;
+    const double* ptr;
+    int64_t rows, ld, sq;  // rows 0: a vector of n / m / p elements (ld: its length)
+  };
+  const Block blocks[9] = {{"Q", o.Q, n, o.ldq, o.sQ}, {"A", o.A, m, o.lda, o.sA},    {"C", o.C, p, o.ldc, o.sC},
+                           {"c", o.c, 0, n, o.sc},     {"l_x", o.lx, 0, n, o.slx},    {"u_x", o.ux, 0, n, o.sux},
+                           {"l_A", o.lA, 0, m, o.slA}, {"u_A", o.uA, 0, m, o.suA},    {"d", o.d, 0, p, o.sd}};
+  bool shared_matrix = false;
+  for (const Block& b : blocks) {
+    if (!b.ptr) continue;
+    if (b.rows && b.ld < n)
+      return fail(IPMZ_ERR_INVALID, who + ": " + b.name + ": row stride " + std::to_string(b.ld) + " < n");
+    if (b.ld < 0 || b.sq < 0) return fail(IPMZ_ERR_INVALID, who + ": " + b.name + ": negative stride");
+    const int64_t extent = b.rows ? (b.rows - 1) * b.ld + n : b.ld;
+    if (s->B > 1 && b.sq != 0 && b.sq < extent)
+      return fail(IPMZ_ERR_INVALID, who + ": " + b.name + ": QP stride " + std::to_string(b.sq) +
+                                        " is neither 0 (summed over the batch) nor at least the block's extent " +
+                                        std::to_string(extent));
+    if (b.rows && s->B > 1 && b.sq == 0) shared_matrix = true;
+  }
+  HIP_OK(hipSetDevice(s->ctx->device));
+  int rc = wait_pending_step(s);  // (a forked step still in flight writes the iterate this call reads)
+  if (rc) return rc;
+  if (shared_matrix) {
+    const size_t need = (size_t)vjp_ws(nullptr, qp_grad_part_elems(s->qb)).total;
+    if (need > s->vjpws.bytes) {  // once per solver: the size follows from the shape alone
+      hipStreamCaptureStatus cs = hipStreamCaptureStatusNone;
+      HIP_OK(hipStreamIsCapturing(s->ctx->stream, &cs));
+      if (cs != hipStreamCaptureStatusNone)
+        return fail(IPMZ_ERR_STATE, who + ": the context's stream is capturing a hipGraph and the shared blocks' "
+                                          "workspace is not allocated yet (make one call outside the capture first)");
+      if ((rc = grow(s, s->vjpws, need))) return rc;
+    }
+  }
+  HIP_OK(qp_data_vjp(s->qb, W, s->B > 1 ? sW : 0, o, vjp_ws(s->vjpws.p, 0).part, s->ctx->stream));
   return IPMZ_OK;
 }
 

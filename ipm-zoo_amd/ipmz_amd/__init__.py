@@ -55,7 +55,7 @@ EXPORTS = [
     "ipmz_bk_solve_multi_batch", "ipmz_batch_kkt_solve_bk",
     "ipmz_qp_newton_solve_multi", "ipmz_batch_newton_solve_multi",
     "ipmz_qp_newton_adjoint_multi", "ipmz_batch_newton_adjoint_multi",
-    "ipmz_batch_load_device", "ipmz_batch_copy_state",
+    "ipmz_batch_load_device", "ipmz_batch_copy_state", "ipmz_batch_data_vjp",
 ]
 SOLVE_MULTI_PANEL = 256  # include/ipmz.h IPMZ_SOLVE_MULTI_PANEL: column panel of the blocked multi-rhs solve
 REDUCTION_AUGMENTED, REDUCTION_NORMAL = 0, 1
@@ -97,6 +97,18 @@ class _QPDeviceData(ctypes.Structure):
                 ("C", _VP), ("ldc", _I64), ("sC", _I64), ("c", _VP), ("l_x", _VP), ("u_x", _VP),
                 ("sc", _I64), ("slx", _I64), ("sux", _I64), ("l_A", _VP), ("u_A", _VP), ("slA", _I64), ("suA", _I64),
                 ("d", _VP), ("sd", _I64)]
+
+
+class _QPDeviceGrad(_QPDeviceData):
+    """include/ipmz.h ipmz_qp_device_grad: the same layout, the blocks written (ipmz_batch_data_vjp)."""
+
+
+# load_tensors' names -> (ipmz_qp_device_data pointer, row stride or None, QP stride, rows or None, columns);
+# rows / columns name the solver's dimensions
+_BLOCKS = (("Q", "Q", "ldq", "sQ", "n", "n"), ("A_ineq", "A", "lda", "sA", "m", "n"), ("A_eq", "C", "ldc", "sC", "p", "n"),
+           ("c", "c", None, "sc", None, "n"), ("l_x", "l_x", None, "slx", None, "n"), ("u_x", "u_x", None, "sux", None, "n"),
+           ("l_A_ineq", "l_A", None, "slA", None, "m"), ("u_A_ineq", "u_A", None, "suA", None, "m"),
+           ("b_eq", "d", None, "sd", None, "p"))
 
 
 def _tensor_block(t, batch, rows, cols):
@@ -223,6 +235,7 @@ def _load():
         "ipmz_batch_newton_adjoint_multi": ([_VP, _I, _VP, _I64, _I64, _VP, _I64, _I64, ctypes.POINTER(_I)], _I),
         "ipmz_batch_load_device": ([_VP, ctypes.POINTER(_QPDeviceData)], _I),
         "ipmz_batch_copy_state": ([_VP, _I, _VP, _I64], _I),
+        "ipmz_batch_data_vjp": ([_VP, _VP, _I64, ctypes.POINTER(_QPDeviceGrad)], _I),
     }
     for name, (args, res) in sig.items():
         fn = getattr(lib, name)
@@ -578,11 +591,18 @@ class Optimizer:
         return o
 
     def load(self, data):
+        self._bump()
         keep = [data.Q, data.c, data.A_ineq, data.l_A_ineq, data.u_A_ineq, data.A_eq, data.b_eq, data.l_x, data.u_x]
         keep = [np.ascontiguousarray(a, dtype=np.float64).reshape(-1) if np.size(a) else np.zeros(1) for a in keep]
         _check(lib.ipmz_qp_load_host(self.h, *[_dp(a) for a in keep]), "ipmz_qp_load_host (build_environment)")
 
+    def _bump(self):
+        """The generation counter: every call that moves the iterate or the data bumps it (ipmz_amd.layer's
+        backward refuses to differentiate at another iterate than its forward's)."""
+        self._generation = getattr(self, "_generation", 0) + 1
+
     def generate(self, seed):
+        self._bump()
         _check(lib.ipmz_qp_generate(self.h, seed), "ipmz_qp_generate")
 
     # -- device-resident load and read-back (torch CUDA tensors; nothing passes through host memory) --
@@ -603,6 +623,7 @@ class Optimizer:
         iterate: ipmz_batch_load_device.  Matrices are (batch, rows, n) or (rows, n) shared by every QP, vectors
         (batch, len) or (len,) shared; any row / batch strides (views, .expand), inner stride 1; nothing is copied.
         None keeps the block the solver holds (e.g. load_tensors(c=c2, b_eq=d2) for a parametric re-load)."""
+        self._bump()
         import torch
         batch = lib.ipmz_batch_size(self.h)
         n, m, p = self.n, self.m, self.p
@@ -656,11 +677,57 @@ class Optimizer:
         self.ctx.sync()
         return out[:, :L]
 
+    def data_grad_tensors(self, W, shared=(), symmetrize=False, only=None):
+        """The gradient with respect to the problem data from the cotangent with respect to the residuals:
+        ipmz_batch_data_vjp.  W: a (batch, >= state_len) float64 CUDA tensor, row q the cotangent of QP q in the
+        order of residuals() -- row 0 of newton_adjoint(_all)'s Out.  Returns a dict with load_tensors' names
+        (Q, c, l_x, u_x, A_ineq, l_A_ineq, u_A_ineq, A_eq, b_eq; blocks of dimension 0 omitted), each a fresh
+        tensor: (batch, ...) per QP, or, for the names in `shared`, (...) summed over the batch -- the gradient of
+        a block that load_tensors was given once for every QP.  only: the names wanted (default: all).
+        Q's n^2 entries are independent: gQ = w_x x^T; symmetrize=True returns (gQ + gQ^T) / 2.  Asynchronous on
+        the context's stream, ordered after torch's current stream like load_tensors; when the context runs on
+        another stream, the call returns after ctx.sync()."""
+        import torch
+        batch, L = lib.ipmz_batch_size(self.h), self.state_len
+        if not isinstance(W, torch.Tensor) or W.dtype != torch.float64 or W.dim() != 2 or W.shape[0] != batch or \
+                W.shape[1] < L or (W.shape[1] > 1 and W.stride(1) != 1):
+            raise ValueError(f"W: a float64 ({batch}, >= {L}) tensor with inner stride 1 is needed")
+        self._on_device(W, "W")
+        names = [b[0] for b in _BLOCKS]
+        for k in list(shared) + list(only or ()):
+            if k not in names:
+                raise ValueError(f"unknown block {k!r}: one of {names}")
+        dims = dict(n=self.n, m=self.m, p=self.p)
+        g = _QPDeviceGrad()
+        out = {}
+        for name, ptr, ld, sq, rows, cols in _BLOCKS:
+            r, c = (None if rows is None else dims[rows]), dims[cols]
+            if c == 0 or r == 0 or (only is not None and name not in only):
+                continue
+            inner = (c,) if r is None else (r, c)
+            t = torch.empty(inner if name in shared else (batch,) + inner, dtype=torch.float64, device=W.device)
+            blk = _tensor_block(t, batch, r, c)
+            setattr(g, ptr, blk[0])
+            if ld:
+                setattr(g, ld, blk[1])
+            # (a batch of one has no shared blocks: the library ignores the QP stride there)
+            setattr(g, sq, 0 if name in shared else t.stride(0))
+            out[name] = t
+        self._order_torch_stream(torch)
+        sW = W.stride(0) if batch > 1 else W.shape[1]
+        _check(lib.ipmz_batch_data_vjp(self.h, _VP(W.data_ptr()), sW, ctypes.byref(g)), "ipmz_batch_data_vjp")
+        if not self.ctx.on_stream(torch.cuda.current_stream(self.ctx.device).cuda_stream):
+            self.ctx.sync()
+        if symmetrize and "Q" in out:
+            out["Q"] = 0.5 * (out["Q"] + out["Q"].transpose(-1, -2))
+        return out
+
     def solution_tensor(self):
         """x of every QP, (batch, n): x leads the Newton order in every formulation."""
         return self.state_tensor(0)[:, :self.n]
 
     def step(self, flags=0):
+        self._bump()
         _check(lib.ipmz_qp_step(self.h, flags), "ipmz_qp_step")
 
     def last_step_graph(self):
@@ -690,6 +757,7 @@ class Optimizer:
         _check(lib.ipmz_qp_copy_scalars(self.h, _VP(dst_ptr)), "ipmz_qp_copy_scalars")
 
     def solve(self, max_iter=100):
+        self._bump()
         trace = np.zeros((max_iter + 1, 8))
         it = ctypes.c_int(0)
         _check(lib.ipmz_qp_solve(self.h, max_iter, _dp(trace), ctypes.byref(it)), "ipmz_qp_solve")
@@ -715,6 +783,7 @@ class Optimizer:
         return self._state(3)
 
     def set_vars(self, v):
+        self._bump()
         v = np.ascontiguousarray(v, dtype=np.float64)
         _check(lib.ipmz_qp_set_state(self.h, _dp(v)), "ipmz_qp_set_state")
 
@@ -805,11 +874,13 @@ class Batch(Optimizer):
         self.state_len = lib.ipmz_qp_state_len(h)
 
     def load_one(self, index, data):
+        self._bump()
         keep = [data.Q, data.c, data.A_ineq, data.l_A_ineq, data.u_A_ineq, data.A_eq, data.b_eq, data.l_x, data.u_x]
         keep = [np.ascontiguousarray(a, dtype=np.float64).reshape(-1) if np.size(a) else np.zeros(1) for a in keep]
         _check(lib.ipmz_batch_load_host(self.h, index, *[_dp(a) for a in keep]), "ipmz_batch_load_host")
 
     def initialize(self):
+        self._bump()
         _check(lib.ipmz_batch_initialize(self.h), "ipmz_batch_initialize")
 
     def copy_batch_scalars(self, dst_ptr):
@@ -894,10 +965,12 @@ class Batch(Optimizer):
         return out
 
     def set_state(self, index, v):
+        self._bump()
         v = np.ascontiguousarray(v, dtype=np.float64)
         _check(lib.ipmz_batch_set_state(self.h, index, _dp(v)), "ipmz_batch_set_state")
 
     def solve_all(self, max_iter=100):
+        self._bump()
         it = ctypes.c_int(0)
         nc = ctypes.c_int(0)
         _check(lib.ipmz_batch_solve(self.h, max_iter, ctypes.byref(it), ctypes.byref(nc)), "ipmz_batch_solve")

@@ -1,0 +1,92 @@
+"""A batch of QPs as a differentiable torch operation: solve_qp(solver, Q=..., c=..., ...) -> x.
+
+Forward: load_tensors, solve, the solutions.  Backward: the loss's gradient with respect to x as one cotangent row
+per QP, the adjoint Newton solve at the converged iterate (J^T w = -g, ipmz_*_newton_adjoint_multi) and its
+contraction with d r / d data (ipmz_batch_data_vjp): the implicit-function theorem on the Newton system, all on the
+device.
+"""
+import torch
+
+from . import _BLOCKS, Batch, IpmzError, lib
+
+_NAMES = tuple(b[0] for b in _BLOCKS)
+
+
+def _even(k):
+    return k + (k & 1)
+
+
+class _SolveQP(torch.autograd.Function):
+    @staticmethod
+    def forward(ctx, solver, max_iter, strict, symmetrize, *blocks):
+        given = {k: t.detach() for k, t in zip(_NAMES, blocks) if t is not None}
+        solver.load_tensors(**given)
+        batch = lib.ipmz_batch_size(solver.h)
+        if isinstance(solver, Batch):
+            its, converged = solver.solve_all(max_iter)
+        else:
+            its, trace = solver.solve(max_iter)
+            converged = int(solver.scalars()["converged"] == 1.0)
+        if strict and converged != batch:
+            raise IpmzError(f"solve_qp: {batch - converged} of {batch} QPs did not converge in {max_iter} iterations "
+                            "(strict=True: the gradient is that of the solution map only at a converged solution)")
+        x = solver.solution_tensor().clone()
+        ctx.solver, ctx.symmetrize = solver, symmetrize
+        ctx.generation = solver._generation
+        # an input given once for every QP (a 2-D matrix, a 1-D vector) receives the gradient summed over the batch
+        ctx.shared = tuple(k for k, t in given.items() if t.dim() == (2 if k in ("Q", "A_ineq", "A_eq") else 1))
+        ctx.shapes = {k: tuple(t.shape) for k, t in given.items()}
+        return x
+
+    @staticmethod
+    def backward(ctx, grad_x):
+        s = ctx.solver
+        if s._generation != ctx.generation:
+            raise IpmzError("solve_qp: the solver's iterate or data changed between forward and backward (a load, "
+                            "step, solve or set_vars since); one forward / backward pair is in flight per solver")
+        batch, L, n = lib.ipmz_batch_size(s.h), s.state_len, s.n
+        ld = _even(L)
+        # one cotangent row per QP in the layout of IPMZ_STATE_DAFF: grad_output in the x slot (x leads the Newton
+        # order in every formulation), zeros elsewhere; the adjoint's Out in place
+        G = torch.zeros((batch, ld), dtype=torch.float64, device=grad_x.device)
+        G[:, :n] = grad_x
+        s._order_torch_stream(torch)
+        if isinstance(s, Batch) and batch > 1:
+            s.newton_adjoint_all(G.data_ptr(), G.data_ptr(), 1, ld, ld, ld, ld)
+        else:
+            s.newton_adjoint(G.data_ptr(), G.data_ptr(), 1, ld, ld)
+        wanted = [k for i, k in enumerate(_NAMES) if ctx.needs_input_grad[4 + i] and k in ctx.shapes]
+        grads = s.data_grad_tensors(G, shared=[k for k in ctx.shared if k in wanted], symmetrize=ctx.symmetrize,
+                                    only=wanted) if wanted else {}
+        out = []
+        for k in _NAMES:
+            g = grads.get(k)
+            if g is None and k in wanted:  # a block of dimension 0
+                g = torch.zeros(ctx.shapes[k], dtype=torch.float64, device=grad_x.device)
+            out.append(None if g is None else g.reshape(ctx.shapes[k]))
+        return (None, None, None, None, *out)
+
+
+def solve_qp(solver, *, Q=None, c=None, l_x=None, u_x=None, A_ineq=None, l_A_ineq=None, u_A_ineq=None, A_eq=None,
+             b_eq=None, max_iter=100, strict=True, symmetrize=False):
+    """x* of every QP of `solver` (an Optimizer or a Batch), (batch, n), differentiable with respect to the data.
+
+    The data are float64 CUDA tensors under load_tensors' names and rules: matrices (batch, rows, n) or (rows, n)
+    given once for every QP, vectors (batch, len) or (len,); None keeps the block the solver holds (and has no
+    gradient).  Forward: load_tensors, solve_all / solve (at most max_iter steps), the solutions.  Backward:
+    the adjoint Newton solve at the final iterate, then ipmz_batch_data_vjp; an input given once for every QP
+    receives the gradient summed over the batch, inputs that do not require grad are skipped.
+
+    The gradient is that of the solution map only at a converged, strictly complementary solution: it is the
+    implicit-function theorem on the Newton system at the final iterate with mu held constant, so at an iterate that
+    has not converged, or where a constraint is active with a zero multiplier, it is the derivative of nothing in
+    particular.  strict=True (default) raises IpmzError when any QP did not converge in max_iter steps.
+
+    Q's entries are independent inputs: dL/dQ = w_x x^T, not symmetric.  symmetrize=True returns (gQ + gQ^T) / 2,
+    the gradient for a caller who builds Q symmetric.  Formulations: those the adjoint solve serves (not
+    EQ_SLACKED_SLACKS / EQ_NAIVE_SLACKS); INEQ_SLACKS does not converge (the reference's corrector defect).
+
+    The solver keeps the iterate the backward pass reads: one forward / backward pair is in flight per solver, and
+    backward raises IpmzError when a load, step, solve or set_vars has moved the solver since its forward."""
+    given = dict(Q=Q, c=c, l_x=l_x, u_x=u_x, A_ineq=A_ineq, l_A_ineq=l_A_ineq, u_A_ineq=u_A_ineq, A_eq=A_eq, b_eq=b_eq)
+    return _SolveQP.apply(solver, max_iter, strict, symmetrize, *[given[k] for k in _NAMES])
