@@ -199,9 +199,10 @@ def test_batches(ctx, c):
 
 
 # 4 ---------------------------------------------------------------------------
-def _layout(g, B, Wt, sW, off, pad_ld, pad_sq):
-    """Every block at element offset `off` of a NaN-filled buffer, row stride n + pad_ld, QP stride extent + pad_sq.
-    Returns ({name: (B, ...) gathered block}, every buffer's padding kept its bits)."""
+def _layout(g, B, Wt, sW, off, pad_ld, pad_sq, shared=False):
+    """Every block at element offset `off` of a NaN-filled buffer, row stride n + pad_ld, QP stride extent + pad_sq --
+    or, shared, QP stride 0: one block per buffer, summed over the batch.
+    Returns ({name: (B, ...) gathered block, (...) when shared}, every buffer's padding kept its bits)."""
     d = _dims(g)
     spec, bufs, where = {}, {}, {}
     for name, ptr, ld, sq, rows, cols in I._BLOCKS:
@@ -210,8 +211,8 @@ def _layout(g, B, Wt, sW, off, pad_ld, pad_sq):
             continue
         l = c + pad_ld if r is not None else 0
         extent = (r - 1) * l + c if r is not None else c
-        s = extent + pad_sq
-        host = np.full(off + B * s + 4, NAN)
+        s = 0 if shared else extent + pad_sq
+        host = np.full(off + (extent if shared else B * s) + 4, NAN)
         bufs[name] = (host, _dev(host))
         spec[name] = (bufs[name][1], off, l, s)
         where[name] = (r, c, l, s)
@@ -222,7 +223,7 @@ def _layout(g, B, Wt, sW, off, pad_ld, pad_sq):
         dv = t.cpu().numpy()
         inside = np.zeros(dv.shape, bool)
         blocks = []
-        for qi in range(B):
+        for qi in range(1 if shared else B):
             base = off + qi * s
             if r is None:
                 idx = base + np.arange(c)
@@ -230,12 +231,14 @@ def _layout(g, B, Wt, sW, off, pad_ld, pad_sq):
                 idx = (base + np.arange(r)[:, None] * l + np.arange(c)[None, :])
             inside[idx.reshape(-1)] = True
             blocks.append(dv[idx])
-        out[name] = np.stack(blocks)
+        out[name] = blocks[0] if shared else np.stack(blocks)
         clean = clean and np.array_equal(_bits(dv[~inside]), _bits(host[~inside])) and not np.isnan(dv[inside]).any()
     return out, clean
 
 
-@pytest.mark.parametrize("c", [(48, 16, 8, 3), (13, 5, 3, 2)], ids=("n48", "n13"))
+# n = 131: the element path's c += 64 loop makes three passes and the 16-byte path's c += 128 loop a second one
+# that ends on the odd column's scalar store
+@pytest.mark.parametrize("c", [(48, 16, 8, 3), (13, 5, 3, 2), (131, 5, 3, 2)], ids=("n48", "n13", "n131"))
 def test_layout(ctx, c):
     n, m, p, B = c
     bt = _batch(n, m, p, B, 1000, ctx)
@@ -257,6 +260,31 @@ def test_layout(ctx, c):
     sub = _host(bt.data_grad_tensors(Wt, only=["A_ineq", "l_x"]))
     assert set(sub) == {"A_ineq", "l_x"} and all(_same(sub[k], ref[k]) for k in sub)
     print(f"layout n={n}: 16-byte path, element path and a subset all bitwise equal; padding untouched", flush=True)
+
+
+@pytest.mark.parametrize("c", [(48, 16, 8, 3), (131, 5, 3, 2)], ids=("n48", "n131"))
+def test_layout_shared(ctx, c):
+    """Shared blocks through the raw call: QP stride 0, a row stride other than n (k_grad_shared_sum's
+    dst[(t / n) * ld + t % n]) and a pointer at element offset 0 and 1 of a NaN-filled buffer."""
+    n, m, p, B = c
+    bt = _batch(n, m, p, B, 1000, ctx)
+    bt.step()
+    bt.step()
+    L = bt.state_len
+    Wt = _dev(np.array(dc.cotangents(L, B)))
+    names = dc.present(n, m, p)
+    ref = _host(bt.data_grad_tensors(Wt, shared=names))
+    per = _host(bt.data_grad_tensors(Wt))
+    for off in (0, 1):
+        got, clean = _layout(bt, B, Wt, L, off, 3, 0, shared=True)
+        assert clean, f"offset {off}: row padding, the space before the block and the tail keep their bits"
+        assert set(got) == set(names)
+        for k in names:
+            assert _same(got[k], ref[k]), (off, k)
+    worst = max(dc.rel_err(ref[k], per[k].sum(axis=0)) for k in names)  # (what was compared is the sum over the batch)
+    assert worst <= nc.TOL
+    print(f"shared layout n={n}: row stride n + 3 at offsets 0 and 1 bitwise the contiguous blocks; padding untouched",
+          flush=True)
 
 
 def test_blocks_of_dimension_zero_are_ignored(ctx):

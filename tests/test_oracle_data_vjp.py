@@ -1,12 +1,15 @@
 """What the device tests of ipmz_batch_data_vjp rely on, checked without a GPU: the numpy reference of
 tests/data_vjp_cases.py satisfies the bilinear identity against nc.residuals_numpy (so it is the transpose of the
-residuals' dependence on the data, all nine blocks at once), and the entry point exists and refuses a null solver
-before it looks for a device."""
+residuals' dependence on the data, all nine blocks at once); reference_form satisfies it for every served formulation
+against residuals_form, the numpy restatement of the formulation's shorthand definitions with mu a parameter, and is
+dc.reference bitwise on the default form; and the entry point exists and refuses a null solver before it looks for a
+device."""
 import ctypes
 
 import numpy as np
 import pytest
 
+import batch_form_cases as fc
 import data_vjp_cases as dc
 import newton_multi_cases as nc
 
@@ -47,6 +50,93 @@ def test_every_block_moves_the_identity():
         broken = dict(grads)
         broken[k] = np.zeros_like(grads[k])
         assert dc.bilinear_gap(w, r0, r1, broken, deltas) > 1e3 * dc.bilinear_bound(w, r0, r1), k
+
+
+FORM_SHAPES = [(name, c) for name in dc.FORM_NAMES for c in (fc.S1, (40, 0, 0)) if c[1] or name in dc.M0_FORMS]
+MU = 0.3  # the identity holds at any fixed mu; 0 would hide PenaltyFunction's and Slacks' mu terms
+
+
+def _form_case(name, c, seed):
+    q = nc.qp(*c)
+    L = dc.form_offsets(name, *c)[3]
+    v = np.random.default_rng(seed).uniform(0.5, 2.0, L)  # a random positive iterate
+    return q, L, v
+
+
+def test_form_table_is_every_served_formulation():
+    assert set(dc.FORM_NAMES) == (set(fc.FORMS) - {"eqss", "naiveeq"}) | {"pen_sl"}
+    assert set(dc.M0_FORMS) == (set(fc.S0_FORMS) - {"eqss"}) | {"pen_sl"}
+    assert dc.form_absent("vnone") == ("l_x", "u_x") and dc.form_absent("alo") == ("u_A_ineq",)
+    assert dc.form_absent("box") == dc.form_absent("pen_sl") == ()
+
+
+@pytest.mark.parametrize("name,c", FORM_SHAPES, ids=[f"{n}-{nc.case_id(c)}" for n, c in FORM_SHAPES])
+def test_reference_form_satisfies_the_bilinear_identity(name, c):
+    """reference_form is the transpose of residuals_form's dependence on the data, all blocks at once."""
+    q, L, v = _form_case(name, c, 33)
+    r0 = dc.residuals_form(name, q, v, MU)
+    assert r0.shape == (L,)
+    worst = 0.0
+    for k in range(3):
+        w = dc.cotangents(L, 3)[k]
+        deltas = dc.random_deltas(q, 300 + k)
+        r1 = dc.residuals_form(name, dc.perturbed(q, deltas), v, MU)
+        grads = dc.reference_form(name, *c, v, w)
+        assert set(grads) == set(deltas) == set(dc.present(*c))
+        for kk in dc.form_absent(name):
+            assert kk not in grads or not grads[kk].any(), kk
+        gap, bound = dc.bilinear_gap(w, r0, r1, grads, deltas), dc.bilinear_bound(w, r0, r1)
+        worst = max(worst, gap / bound)
+        assert bound > 0 and gap <= bound, (k, gap, bound)
+    print(f"{name} {nc.case_id(c)}: worst gap / bound {worst:.3e}")
+
+
+@pytest.mark.parametrize("name", dc.FORM_NAMES)
+def test_every_block_of_every_form_moves_the_identity(name):
+    """A reference_form with any one block zeroed (of those the formulation has) misses the identity by far."""
+    c = fc.S1
+    q, L, v = _form_case(name, c, 34)
+    w = dc.cotangents(L)[0]
+    deltas = dc.random_deltas(q, 8)
+    r0, r1 = dc.residuals_form(name, q, v, MU), dc.residuals_form(name, dc.perturbed(q, deltas), v, MU)
+    grads = dc.reference_form(name, *c, v, w)
+    bound = dc.bilinear_bound(w, r0, r1)
+    assert dc.bilinear_gap(w, r0, r1, grads, deltas) <= bound
+    for k in grads:
+        if k in dc.form_absent(name):
+            continue
+        broken = dict(grads)
+        broken[k] = np.zeros_like(grads[k])
+        assert dc.bilinear_gap(w, r0, r1, broken, deltas) > 1e3 * bound, k
+
+
+@pytest.mark.parametrize("name,eq_none", (("box", False), ("none", True)))
+@pytest.mark.parametrize("c", nc.SHAPES, ids=nc.case_id)
+def test_reference_form_is_the_default_reference_bitwise(c, name, eq_none):
+    q, L, v = _form_case(name, c, 35)
+    assert L == nc.offsets(q, eq_none)[3]
+    w = dc.cotangents(L)[0]
+    a, b = dc.reference_form(name, *c, v, w), dc.reference(q, v, w, eq_none)
+    assert set(a) == set(b)
+    for k in a:
+        assert a[k].shape == b[k].shape and np.array_equal(a[k].view(np.int64), b[k].view(np.int64)), k
+    # ... and residuals_form restates nc.residuals_numpy at mu = 0
+    assert np.array_equal(dc.residuals_form(name, q, v, 0.0), nc.residuals_numpy(q, v, eq_none))
+
+
+def test_loop_cases_reach_the_loops():
+    """The batches of dc.LOOP_BATCHES against grad_grid's limits as the sources state them."""
+    import os
+    import re
+    here = os.path.dirname(os.path.abspath(__file__))
+    txt = open(os.path.join(here, "..", "ipm-zoo_amd", "csrc", "grad.hip")).read()
+    gx, gy = re.search(r"gx > (\d+) \? \1 : gx;\s*int64_t gy = (\d+) / gx;", txt).groups()
+    assert (int(gx), int(gy)) == (dc.SUM_GX, dc.GRID_Y)
+    assert re.search(r"constexpr int NT = 256;", txt) and re.search(r"constexpr int VS = 64,", txt)
+    n = dc.LOOP_SHAPE[0]
+    assert max(dc.LOOP_BATCHES) > dc.GRID_Y // -(-n // 4) and max(dc.LOOP_BATCHES) > dc.GRID_Y
+    assert -(-257 // 64) == 5 and 257 in dc.LOOP_BATCHES          # a full group of four plus a tail
+    assert dc.BIG_N ** 2 > dc.SUM_GX * 256 >= 724 ** 2
 
 
 def test_null_solver_is_invalid_without_a_device():
