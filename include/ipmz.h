@@ -70,6 +70,10 @@
  *                                  with respect to the problem data in the strided blocks
  *                                  ipmz_batch_load_device reads (per QP, or summed over the
  *                                  batch for shared blocks)
+ *   ipmz_batch_data_jvp         <- no reference counterpart: the forward-mode counterpart,
+ *                                  tangents of the data (ntan per QP, or one set shared by
+ *                                  the batch) to the residual rows d r_v / d data applied to
+ *                                  them, the input of ipmz_*_newton_solve_multi
  *
  * Conventions
  *   - Plain pointers and sizes only.  "device" pointers are HIP device
@@ -893,6 +897,83 @@ typedef struct ipmz_qp_device_grad {
   int64_t sd;
 } ipmz_qp_device_grad;
 int ipmz_batch_data_vjp(ipmz_qp* qp, const double* W, int64_t sW, const ipmz_qp_device_grad* grad);
+
+/* The first link of a forward pass through a solved QP: tangents of the problem
+ * data in, the tangents of the residual vectors out.  At a fixed iterate and a
+ * fixed mu every r_v is affine in the data, so for tangent t < ntan of QP q
+ *
+ *     R[q][t] = (d r / d theta) D_t,
+ *
+ * the linear part of r in the data evaluated at the tangents, in the layout of
+ * IPMZ_STATE_RES.  With dz = -J^{-1} r_theta dtheta (above) and Dir = -J^{-1} R
+ * of ipmz_*_newton_solve_multi, Dir of this R is the tangent of the whole
+ * Newton state; its leading n entries are dx*:
+ *
+ *     data tangents -> R (this call) -> ipmz_*_newton_solve_multi -> dz.
+ *
+ * In the default form: r_x = dQ x + dc + dA^T lambda_A + dC^T lambda_C;
+ * r_lambda_A = dA x; r_lambda_C = dC x - dd (all three equality handlings);
+ * r_lambda_y = dl_x, r_lambda_z = -du_x, r_lambda_g = dl_A, r_lambda_h = -du_A.
+ * IPMZ_INEQ_SLACKS: the bounds enter multiplied by the duals (r_lambda_y =
+ * -lambda_y dl_x, r_lambda_z = lambda_z du_x, and so for l_A, u_A).
+ * IPMZ_INEQ_NAIVE_SLACKS: r_x has dA^T (lambda_h - lambda_g), r_lambda_g = dl_A
+ * - dA x, r_lambda_h = dA x - du_A.  A bound the formulation does not have
+ * contributes nothing.  mu is a constant of the call, as for the vjp; the n^2
+ * entries of dQ are independent.
+ *
+ * ipmz_qp_device_tangent is ipmz_qp_device_data (blocks, row strides, QP
+ * strides: the rules of ipmz_batch_load_device) plus a tangent stride per
+ * block: tangent t of QP q of block X starts at X + q * sX + t * tX.  Strides in
+ * elements; a row stride is at least n; no stride is negative; blocks of
+ * dimension 0 are ignored whatever they hold; a NULL block is a zero tangent.
+ * With ntan > 1 a tangent stride is at least the block's extent; a non-zero QP
+ * stride is at least (ntan - 1) * tX + extent.  QP stride 0 (batches): ONE set
+ * of ntan tangents shared by every QP -- the tangent of data that
+ * ipmz_batch_load_device shared.  No alignment rule (16-byte loads where the
+ * pointer and all three strides allow them, element by element otherwise, with
+ * equal bits).  Nothing outside the blocks (row padding, the space between
+ * tangents and QPs) is read.
+ *
+ * R (device): row (q, t) at R + q * sR + t * ldr receives all L =
+ * ipmz_qp_state_len doubles; slots no datum enters (r_s, r_p, the
+ * complementarity rows of the SlackedSlacks and NaiveSlacks forms) are written
+ * as zeros.  R[q][t][L .. ldr) and everything between ntan * ldr and sR keep
+ * their bits.  R, ldr and sR obey the rules of ipmz_batch_newton_solve_multi's
+ * R, so that the output feeds that call directly, in place if the caller
+ * likes: ldr >= L and even; sR >= ntan * ldr and even; R 16-byte aligned.  A
+ * solver of one QP ignores the QP strides and sR.  ntan == 0 is a no-op.
+ *
+ * Per-QP tangent matrices are one bandwidth-bound pass that reads every element
+ * once (dA serves dA x and dA^T lambda from the same load); shared tangent
+ * matrices are products on fp64 MFMA with the batch as a tile dimension.  The
+ * products go through a workspace of the solver (batch * ntan segments; per
+ * given matrix block the row products' partials, one per tile of up to 512
+ * columns, and for A and C the column products' partials, one per chunk of 8 to
+ * 32 rows; one partial each for shared blocks: csrc/jvp.hip), allocated on first
+ * use, grown for the largest need seen, freed with the solver; one last launch
+ * then writes every element of R exactly once.  Stream-ordered
+ * launches only, no cross-workgroup waiting, no atomics; the order in which the
+ * terms of every element are summed is fixed by (n, m, p) alone: a row's
+ * result does not depend on the other rows, a QP's not on the other QPs, equal
+ * inputs give equal bits.
+ *
+ * Asynchronous on the context's stream, no synchronize; the iterate, the
+ * step's slots, the scalars, the kept KKT matrix, a captured step graph and all
+ * later steps are unchanged, bitwise: the call reads the iterate and the
+ * tangents only.
+ *
+ * Served and refused exactly like ipmz_batch_data_vjp: IPMZ_ERR_INVALID for a
+ * null qp, tan or R, bad strides or alignment of R, ntan < 0,
+ * IPMZ_EQ_SLACKED_SLACKS / IPMZ_EQ_NAIVE_SLACKS, an enabled normal-equations
+ * reduction or mixed precision; IPMZ_ERR_STATE before a load, between a load
+ * and ipmz_batch_initialize, and when the workspace would have to be allocated
+ * while the context's stream is capturing; IPMZ_ERR_NOMEM when it cannot be
+ * had. */
+typedef struct ipmz_qp_device_tangent {
+  ipmz_qp_device_data d;  /* blocks, row strides, QP strides: the rules of ipmz_batch_load_device */
+  int64_t tQ, tA, tC, tc, tlx, tux, tlA, tuA, td;  /* tangent strides, in elements */
+} ipmz_qp_device_tangent;
+int ipmz_batch_data_jvp(ipmz_qp* qp, int ntan, const ipmz_qp_device_tangent* tan, double* R, int64_t ldr, int64_t sR);
 
 /* Phase timing (HIP events on the context stream; eager launches only).
  * ms: host array of IPMZ_PH_COUNT floats, cumulative since enable. */

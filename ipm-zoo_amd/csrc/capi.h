@@ -195,6 +195,20 @@ inline VjpWs vjp_ws(char* base, int64_t elems) {
   return w;
 }
 
+// ipmz_batch_data_jvp's matrix products: one segment per row (q, t)
+// (jvp.hip; elems = batch * ntan * qp_jvp_plan(...).seg)
+struct JvpWs {
+  double* prod = nullptr;
+  int64_t total = 0;
+};
+inline JvpWs jvp_ws(char* base, int64_t elems) {
+  JvpWs w;
+  Carver c{base};
+  w.prod = c.take<double>(elems);
+  w.total = c.off;
+  return w;
+}
+
 // the workspace whose sticky error words the next ipmz_ctx_sync checks (pe:
 // a panel factor's, may be null; se: a persistent solve's)
 inline void watch(ipmz_ctx* ctx, const unsigned* pe, const unsigned* se) {

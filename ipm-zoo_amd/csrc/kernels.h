@@ -613,4 +613,42 @@ int64_t qp_grad_part_elems(const QPBatch& qb);
 hipError_t qp_data_vjp(const QPBatch& qb, const double* W, int64_t sW, const QpGradOut& o, double* part,
                        hipStream_t st);
 
+// jvp.hip --------------------------------------------------------------------
+// A caller's tangents of the problem data in device memory
+// (ipmz_qp_device_tangent with the blocks this call does not take -- null, or of
+// dimension 0 -- null): QpIoData's description plus a tangent stride per block;
+// tangent t of QP z of block X starts at X + z sX + t tX.  A QP stride of 0
+// (batches) is one set of tangents shared by every QP.
+struct QpTanIn {
+  const double *Q, *A, *C;
+  int64_t ldq, sQ, tQ, lda, sA, tA, ldc, sC, tC;
+  const double *c, *lx, *ux, *lA, *uA, *d;
+  int64_t sc, tc, slx, tlx, sux, tux, slA, tlA, suA, tuA, sd, td;
+};
+// gridDim.y of the launches that loop over the rows (q, t) of R
+#define IPMZ_JVP_ROWS_GY 16384
+// Where one matrix block's products lie in a row's segment of the workspace,
+// and how they were cut (jvp.hip's header: the summation order).  mode 0: no
+// such block, 1: per-QP tangents, 2: shared.  Row products (dM x): nct partials
+// of `rows` doubles at off_row; column products (dM^T y, A and C only): nchunk
+// partials of n doubles at off_col (chunks of rch rows).
+struct JvpMat {
+  int mode, rch, nchunk, nct;
+  int64_t off_row, off_col;
+};
+struct JvpPlan {
+  JvpMat mat[3];  // Q, A, C
+  int64_t seg;    // doubles per row (q, t); the workspace holds batch * ntan segments
+};
+// a function of the shape, of which blocks are given and of which are shared -- not of ntan or the batch size
+JvpPlan qp_jvp_plan(const QPBatch& qb, const QpTanIn& in);
+// column pairs per lane of k_jvp_matrix's column tile (128 of them columns each), by n
+int jvp_pairs(int n);
+// row (z, t) of R (at R + z sR + t ldr, the layout of IPMZ_STATE_RES, all
+// state_len elements) <- (d r / d data) applied to tangent t of QP z; ws: the
+// workspace above (may be null when no matrix block is given).  Stream-ordered
+// launches, no atomics; reads the iterate and the tangents only
+hipError_t qp_data_jvp(const QPBatch& qb, int ntan, const QpTanIn& in, double* R, int64_t ldr, int64_t sR, double* ws,
+                       hipStream_t st);
+
 }  // namespace ipmz

@@ -58,6 +58,8 @@ struct ipmz_qp {
   GrowBuf nmws;
   // ipmz_batch_data_vjp: the shared matrix blocks' partial products (vjp_ws), when one is first asked for
   GrowBuf vjpws;
+  // ipmz_batch_data_jvp: the matrix products of every row (jvp_ws), for the largest need seen
+  GrowBuf jvpws;
   // normal-equations reduction (C2)
   bool normal = false;
   // EqualityHandling::None: Bunch-Kaufman factor (pivots per QP)
@@ -1648,6 +1650,90 @@ int ipmz_batch_data_vjp(ipmz_qp* s, const double* W, int64_t sW, const ipmz_qp_d
     }
   }
   HIP_OK(qp_data_vjp(s->qb, W, s->B > 1 ? sW : 0, o, vjp_ws(s->vjpws.p, 0).part, s->ctx->stream));
+  return IPMZ_OK;
+}
+
+// (d r / d data) applied to ntan tangents of the data per QP (jvp.hip): the
+// block description and checks of the call above with a tangent stride per
+// block, R checked as ipmz_batch_newton_solve_multi checks its R.  Launches
+// only: no synchronize, and an allocation only when the matrix products need
+// more workspace than any call before.
+int ipmz_batch_data_jvp(ipmz_qp* s, int ntan, const ipmz_qp_device_tangent* tan, double* R, int64_t ldr, int64_t sR) {
+  const std::string who = "ipmz_batch_data_jvp";
+  if (!s || !tan || !R) return fail(IPMZ_ERR_INVALID, who + ": null argument");
+  if (s->normal) return fail(IPMZ_ERR_INVALID, who + ": the normal-equations reduction is enabled (augmented system only)");
+  if (s->mixed) return fail(IPMZ_ERR_INVALID, who + ": mixed precision is enabled (fp64 factors only)");
+  if (s->eqss)
+    return fail(IPMZ_ERR_INVALID, who + ": EqualityHandling::SlackedSlacks / NaiveSlacks keep a permuted, merged view of "
+                                        "the Newton order on the device; not served");
+  if (!s->loaded) return fail(IPMZ_ERR_STATE, who + ": load (and initialize) the QP first");
+  if (ntan < 0) return fail(IPMZ_ERR_INVALID, who + ": ntan < 0");
+  if (ldr < s->state_len || (ldr & 1))
+    return fail(IPMZ_ERR_INVALID, who + ": R: row stride " + std::to_string(ldr) + " must be >= state_len and even");
+  if (s->B > 1 && (sR < (int64_t)ntan * ldr || (sR & 1)))
+    return fail(IPMZ_ERR_INVALID, who + ": R: QP stride " + std::to_string(sR) + " must be >= ntan * row stride and even");
+  if ((uintptr_t)R & 15) return fail(IPMZ_ERR_INVALID, who + ": R must be 16-byte aligned");
+  const int n = s->n, m = s->m, p = s->p;
+  const ipmz_qp_device_data& d = tan->d;
+  // blocks of dimension 0 are ignored whatever they hold
+  QpTanIn in{};
+  in.Q = d.Q, in.ldq = d.ldq, in.sQ = d.sQ, in.tQ = tan->tQ;
+  in.c = d.c, in.sc = d.sc, in.tc = tan->tc;
+  in.lx = d.l_x, in.slx = d.slx, in.tlx = tan->tlx;
+  in.ux = d.u_x, in.sux = d.sux, in.tux = tan->tux;
+  if (m) {
+    in.A = d.A, in.lda = d.lda, in.sA = d.sA, in.tA = tan->tA;
+    in.lA = d.l_A, in.slA = d.slA, in.tlA = tan->tlA;
+    in.uA = d.u_A, in.suA = d.suA, in.tuA = tan->tuA;
+  }
+  if (p) {
+    in.C = d.C, in.ldc = d.ldc, in.sC = d.sC, in.tC = tan->tC;
+    in.d = d.d, in.sd = d.sd, in.td = tan->td;
+  }
+  struct Block {
+    const char* name;
+    const double* ptr;
+    int64_t rows, ld, sq, tq;  // rows 0: a vector of n / m / p elements (ld: its length)
+  };
+  const Block blocks[9] = {{"Q", in.Q, n, in.ldq, in.sQ, in.tQ},      {"A", in.A, m, in.lda, in.sA, in.tA},
+                           {"C", in.C, p, in.ldc, in.sC, in.tC},      {"c", in.c, 0, n, in.sc, in.tc},
+                           {"l_x", in.lx, 0, n, in.slx, in.tlx},      {"u_x", in.ux, 0, n, in.sux, in.tux},
+                           {"l_A", in.lA, 0, m, in.slA, in.tlA},      {"u_A", in.uA, 0, m, in.suA, in.tuA},
+                           {"d", in.d, 0, p, in.sd, in.td}};
+  for (const Block& b : blocks) {
+    if (!b.ptr) continue;
+    if (b.rows && b.ld < n)
+      return fail(IPMZ_ERR_INVALID, who + ": " + b.name + ": row stride " + std::to_string(b.ld) + " < n");
+    // (a solver of one QP ignores the QP strides, a call with one tangent the tangent strides)
+    if (b.ld < 0 || (s->B > 1 && b.sq < 0) || (ntan > 1 && b.tq < 0))
+      return fail(IPMZ_ERR_INVALID, who + ": " + b.name + ": negative stride");
+    const int64_t extent = b.rows ? (b.rows - 1) * b.ld + n : b.ld;
+    if (ntan > 1 && b.tq < extent)
+      return fail(IPMZ_ERR_INVALID, who + ": " + b.name + ": tangent stride " + std::to_string(b.tq) +
+                                        " is less than the block's extent " + std::to_string(extent));
+    const int64_t all = (ntan > 1 ? (int64_t)(ntan - 1) * b.tq : 0) + extent;
+    if (s->B > 1 && b.sq != 0 && b.sq < all)
+      return fail(IPMZ_ERR_INVALID, who + ": " + b.name + ": QP stride " + std::to_string(b.sq) +
+                                        " is neither 0 (shared) nor at least the extent of the QP's tangents " +
+                                        std::to_string(all));
+  }
+  if (ntan == 0) return IPMZ_OK;
+  if (s->B == 1) in.sQ = in.sA = in.sC = in.sc = in.slx = in.sux = in.slA = in.suA = in.sd = 0;
+  HIP_OK(hipSetDevice(s->ctx->device));
+  int rc = wait_pending_step(s);  // (a forked step still in flight writes the iterate this call reads)
+  if (rc) return rc;
+  const int64_t elems = (int64_t)s->B * ntan * qp_jvp_plan(s->qb, in).seg;
+  const size_t need = (size_t)jvp_ws(nullptr, elems).total;
+  if (need > s->jvpws.bytes) {
+    hipStreamCaptureStatus cs = hipStreamCaptureStatusNone;
+    HIP_OK(hipStreamIsCapturing(s->ctx->stream, &cs));
+    if (cs != hipStreamCaptureStatusNone)
+      return fail(IPMZ_ERR_STATE, who + ": the context's stream is capturing a hipGraph and the products' workspace is "
+                                        "too small for this call (make one such call outside the capture first)");
+    // (launches of earlier calls may still read the old buffer: hipFree waits for the device)
+    if ((rc = grow(s, s->jvpws, need))) return rc;
+  }
+  HIP_OK(qp_data_jvp(s->qb, ntan, in, R, ldr, s->B > 1 ? sR : 0, jvp_ws(s->jvpws.p, 0).prod, s->ctx->stream));
   return IPMZ_OK;
 }
 

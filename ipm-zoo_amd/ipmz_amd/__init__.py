@@ -55,7 +55,7 @@ EXPORTS = [
     "ipmz_bk_solve_multi_batch", "ipmz_batch_kkt_solve_bk",
     "ipmz_qp_newton_solve_multi", "ipmz_batch_newton_solve_multi",
     "ipmz_qp_newton_adjoint_multi", "ipmz_batch_newton_adjoint_multi",
-    "ipmz_batch_load_device", "ipmz_batch_copy_state", "ipmz_batch_data_vjp",
+    "ipmz_batch_load_device", "ipmz_batch_copy_state", "ipmz_batch_data_vjp", "ipmz_batch_data_jvp",
 ]
 SOLVE_MULTI_PANEL = 256  # include/ipmz.h IPMZ_SOLVE_MULTI_PANEL: column panel of the blocked multi-rhs solve
 REDUCTION_AUGMENTED, REDUCTION_NORMAL = 0, 1
@@ -103,6 +103,11 @@ class _QPDeviceGrad(_QPDeviceData):
     """include/ipmz.h ipmz_qp_device_grad: the same layout, the blocks written (ipmz_batch_data_vjp)."""
 
 
+class _QPDeviceTangent(ctypes.Structure):
+    """include/ipmz.h ipmz_qp_device_tangent: the blocks plus a tangent stride each (ipmz_batch_data_jvp)."""
+    _fields_ = [("d", _QPDeviceData)] + [(k, _I64) for k in ("tQ", "tA", "tC", "tc", "tlx", "tux", "tlA", "tuA", "td")]
+
+
 # load_tensors' names -> (ipmz_qp_device_data pointer, row stride or None, QP stride, rows or None, columns);
 # rows / columns name the solver's dimensions
 _BLOCKS = (("Q", "Q", "ldq", "sQ", "n", "n"), ("A_ineq", "A", "lda", "sA", "m", "n"), ("A_eq", "C", "ldc", "sC", "p", "n"),
@@ -137,6 +142,32 @@ def _tensor_block(t, batch, rows, cols):
     # (the stride of a dimension of size 1 means nothing: a single row is given the row length)
     ld = 0 if rows is None else (strides[0] if rows > 1 else max(strides[0], cols))
     return t.data_ptr(), ld, sq
+
+
+def _tangent_block(t, batch, rows, cols):
+    """A torch tensor as one block of ipmz_qp_device_tangent: (data_ptr, row stride, QP stride, tangent stride,
+    ntan), strides in elements.  _tensor_block's rules with a tangent dimension after the batch's: matrices
+    (batch, ntan, rows, cols) per QP or (ntan, rows, cols) shared by every QP, vectors (batch, ntan, cols) or
+    (ntan, cols).  Nothing is copied."""
+    import torch
+    name = "matrix" if rows is not None else "vector"
+    if not isinstance(t, torch.Tensor) or t.dtype != torch.float64:
+        raise ValueError(f"{name} tangent: a float64 torch tensor is needed, got {getattr(t, 'dtype', type(t))}")
+    inner = (cols,) if rows is None else (rows, cols)
+    shape = tuple(t.shape)
+    k = len(inner)
+    if len(shape) == k + 2 and shape[0] == batch and shape[2:] == inner:
+        sq = t.stride(0) if batch > 1 else 0
+        ntan, tq, strides = shape[1], t.stride(1), t.stride()[2:]
+    elif len(shape) == k + 1 and shape[1:] == inner:
+        sq = 0
+        ntan, tq, strides = shape[0], t.stride(0), t.stride()[1:]
+    else:
+        raise ValueError(f"{name} tangent: shape {shape} is neither {(batch, 'ntan') + inner} nor {('ntan',) + inner}")
+    if cols > 1 and strides[-1] != 1:
+        raise ValueError(f"{name} tangent: inner stride {strides[-1]}, must be 1 (elements of a row adjacent)")
+    ld = 0 if rows is None else (strides[0] if rows > 1 else max(strides[0], cols))
+    return t.data_ptr(), ld, sq, (tq if ntan > 1 else 0), ntan
 
 
 def _load():
@@ -236,6 +267,7 @@ def _load():
         "ipmz_batch_load_device": ([_VP, ctypes.POINTER(_QPDeviceData)], _I),
         "ipmz_batch_copy_state": ([_VP, _I, _VP, _I64], _I),
         "ipmz_batch_data_vjp": ([_VP, _VP, _I64, ctypes.POINTER(_QPDeviceGrad)], _I),
+        "ipmz_batch_data_jvp": ([_VP, _I, ctypes.POINTER(_QPDeviceTangent), _VP, _I64, _I64], _I),
     }
     for name, (args, res) in sig.items():
         fn = getattr(lib, name)
@@ -720,6 +752,70 @@ class Optimizer:
             self.ctx.sync()
         if symmetrize and "Q" in out:
             out["Q"] = 0.5 * (out["Q"] + out["Q"].transpose(-1, -2))
+        return out
+
+    def data_jvp_tensors(self, tangents, out=None):
+        """The tangents of the residual vectors from tangents of the problem data: ipmz_batch_data_jvp, the
+        forward-mode counterpart of data_grad_tensors.  tangents: a dict under load_tensors' names of float64 CUDA
+        tensors with a tangent dimension after the batch's -- matrices (batch, ntan, rows, n) per QP or
+        (ntan, rows, n) shared by every QP (the tangent of a block load_tensors was given once), vectors
+        (batch, ntan, len) or (ntan, len); inner stride 1, any outer strides, nothing copied.  A missing name (or
+        None) is a zero tangent, blocks of dimension 0 are ignored; all given tensors agree on ntan (ValueError).
+        Returns R, (batch, ntan, even(state_len)): row (q, t) in the order of residuals(), the block
+        newton_solve / newton_solve_all take as it is (nrhs = ntan, ldr = R.stride(1), sR = R.stride(0)).  out:
+        such a tensor to write into (16-byte aligned, inner stride 1, even strides; columns from state_len on keep
+        their bits).  mu is a constant of the call.  Asynchronous on the context's stream, ordered after torch's
+        current stream like load_tensors; when the context runs on another stream, the call returns after
+        ctx.sync()."""
+        import torch
+        batch, L = lib.ipmz_batch_size(self.h), self.state_len
+        names = [b[0] for b in _BLOCKS]
+        for k in tangents:
+            if k not in names:
+                raise ValueError(f"unknown block {k!r}: one of {names}")
+        dims = dict(n=self.n, m=self.m, p=self.p)
+        tan = _QPDeviceTangent()
+        tstride = dict(Q="tQ", A="tA", C="tC", c="tc", l_x="tlx", u_x="tux", l_A="tlA", u_A="tuA", d="td")
+        ntan, keep = None, []
+        for name, ptr, ld, sq, rows, cols in _BLOCKS:
+            t = tangents.get(name)
+            if t is None:
+                continue
+            r, c = (None if rows is None else dims[rows]), dims[cols]
+            if not isinstance(t, torch.Tensor):
+                raise ValueError(f"{name}: a torch tensor is needed")
+            self._on_device(t, name)
+            blk = _tangent_block(t, batch, r, c)
+            if ntan is not None and blk[4] != ntan:
+                raise ValueError(f"{name}: {blk[4]} tangents, the blocks before it have {ntan}")
+            ntan = blk[4]
+            if c == 0 or r == 0:
+                continue
+            keep.append(t)
+            setattr(tan.d, ptr, blk[0])
+            if ld:
+                setattr(tan.d, ld, blk[1])
+            setattr(tan.d, sq, blk[2])
+            setattr(tan, tstride[ptr], blk[3])
+        if ntan is None:
+            raise ValueError("data_jvp_tensors: no tangent given (ntan is taken from the tensors)")
+        ldr = L + (L & 1)
+        if out is None:
+            out = torch.empty((batch, ntan, ldr), dtype=torch.float64, device=f"cuda:{self.ctx.device}")
+        else:
+            self._on_device(out, "out")
+            if out.dtype != torch.float64 or out.dim() != 3 or tuple(out.shape[:2]) != (batch, ntan) or \
+                    out.shape[2] < L or (out.shape[2] > 1 and out.stride(2) != 1):
+                raise ValueError(f"out: a float64 ({batch}, {ntan}, >= {L}) tensor with inner stride 1 is needed")
+        # (the stride of a dimension of size 1 means nothing)
+        ld_out = out.stride(1) if ntan > 1 else out.shape[2] + (out.shape[2] & 1)
+        s_out = out.stride(0) if batch > 1 else ntan * ld_out
+        self._order_torch_stream(torch)
+        _check(lib.ipmz_batch_data_jvp(self.h, ntan, ctypes.byref(tan), _VP(out.data_ptr()), ld_out, s_out),
+               "ipmz_batch_data_jvp")
+        if not self.ctx.on_stream(torch.cuda.current_stream(self.ctx.device).cuda_stream):
+            self.ctx.sync()
+        del keep
         return out
 
     def solution_tensor(self):

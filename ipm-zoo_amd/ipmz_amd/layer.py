@@ -3,7 +3,8 @@
 Forward: load_tensors, solve, the solutions.  Backward: the loss's gradient with respect to x as one cotangent row
 per QP, the adjoint Newton solve at the converged iterate (J^T w = -g, ipmz_*_newton_adjoint_multi) and its
 contraction with d r / d data (ipmz_batch_data_vjp): the implicit-function theorem on the Newton system, all on the
-device.
+device.  Forward mode (solution_jvp, and solve_qp under torch.autograd.forward_ad): tangents of the data to the
+residual rows (ipmz_batch_data_jvp), then the Newton solve of all rows from one factor (ipmz_*_newton_solve_multi).
 """
 import torch
 
@@ -65,6 +66,53 @@ class _SolveQP(torch.autograd.Function):
                 g = torch.zeros(ctx.shapes[k], dtype=torch.float64, device=grad_x.device)
             out.append(None if g is None else g.reshape(ctx.shapes[k]))
         return (None, None, None, None, *out)
+
+    @staticmethod
+    def jvp(ctx, _solver, _max_iter, _strict, _symmetrize, *tangents):
+        # torch.autograd.forward_ad: one tangent per dual input (ntan = 1); the tangent of an input given once for
+        # every QP is a shared tangent.  The generation check and strict are forward's and backward's
+        s = ctx.solver
+        if s._generation != ctx.generation:
+            raise IpmzError("solve_qp: the solver's iterate or data changed between forward and jvp (a load, step, "
+                            "solve or set_vars since); one forward / jvp pair is in flight per solver")
+        batch = lib.ipmz_batch_size(s.h)
+        given = {}
+        for k, t in zip(_NAMES, tangents):
+            if t is None or k not in ctx.shapes:
+                continue
+            t = t.detach().reshape(ctx.shapes[k])
+            given[k] = t.unsqueeze(0 if k in ctx.shared else 1)
+        if not given:
+            return torch.zeros((batch, s.n), dtype=torch.float64, device=f"cuda:{s.ctx.device}")
+        return solution_jvp(s, **given)[0][:, 0].clone()
+
+
+def solution_jvp(solver, **tangents):
+    """(dx, dz): the tangents of the solution and of the whole Newton state of every QP of `solver` (an Optimizer
+    or a Batch) along tangents of its data, at the solver's current iterate.
+
+    tangents: float64 CUDA tensors under load_tensors' names with a tangent dimension after the batch's, as
+    Optimizer.data_jvp_tensors takes them: matrices (batch, ntan, rows, n) or (ntan, rows, n) for data given once
+    for every QP, vectors (batch, ntan, len) or (ntan, len); missing names are zero tangents.  The chain is
+    data tangents -> R = (d r / d data) D (ipmz_batch_data_jvp) -> the Newton solve of all ntan rows from one
+    factor, in place (ipmz_*_newton_solve_multi): dz = -J^{-1} R.  Returns dx, the (batch, ntan, n) view of dz's
+    leading entries (x leads the Newton order in every formulation), and dz, (batch, ntan, state_len).  The
+    solver's iterate and generation counter do not move.
+
+    As for solve_qp's gradient: this is the derivative of the solution map only at a converged, strictly
+    complementary solution -- the implicit-function theorem on the Newton system at the current iterate with mu
+    held constant.  At an iterate that has not converged, or where a constraint is active with a zero multiplier,
+    it is the derivative of nothing in particular."""
+    s = solver
+    batch, L = lib.ipmz_batch_size(s.h), s.state_len
+    R = s.data_jvp_tensors(tangents)
+    ntan, ld = R.shape[1], R.stride(1) if R.shape[1] > 1 else R.shape[2]
+    if isinstance(s, Batch) and batch > 1:
+        s.newton_solve_all(R.data_ptr(), R.data_ptr(), ntan, ld, ntan * ld, ld, ntan * ld)
+    else:
+        s.newton_solve(R.data_ptr(), R.data_ptr(), ntan, ld, ld)
+    dz = R[:, :, :L]
+    return dz[:, :, :s.n], dz
 
 
 def solve_qp(solver, *, Q=None, c=None, l_x=None, u_x=None, A_ineq=None, l_A_ineq=None, u_A_ineq=None, A_eq=None,
