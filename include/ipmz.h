@@ -763,6 +763,14 @@ int ipmz_batch_kkt_solve_bk(ipmz_qp* qp, int nrhs, double* B, int64_t ldb, int64
  * the other QPs (given the same kernel selection), equal inputs give equal
  * bits.
  *
+ * Accuracy: the eliminated slack / dual pairs are back-substituted slack
+ * first, each from its own row of the Newton system (dg = ds - r_lg, then
+ * dl_g from row g), so those rows are met to a few units of roundoff
+ * componentwise for any residual row, at a late iterate too.  The step itself
+ * keeps the reference's order (dual first), which is as accurate for the
+ * iterate's own residual only; a row equal to that residual therefore agrees
+ * with the step's direction to rounding, not bit for bit.
+ *
  * IPMZ_ERR_INVALID: an enabled normal-equations reduction or mixed precision;
  * IPMZ_EQ_SLACKED_SLACKS / IPMZ_EQ_NAIVE_SLACKS (their public state is a
  * permuted, merged view of the step's slots; ipmz_batch_copy_state applies that

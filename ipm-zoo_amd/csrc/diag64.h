@@ -153,8 +153,16 @@ __device__ __forceinline__ void colpass16_spec(double* M, double* dsh, int p, in
 // and w are final one step earlier), and the zero rule is applied to the
 // reciprocal (1 / 1e-8 selected after the rcp, the test beside it):
 // readlane -> fma -> rcp -> NEWTON x (2 fma) -> select.  Other columns as in
-// colpass16_spec.  Rounding differs from it at the 1e-16 level (the product
-// order of the column-(k+1) update).
+// colpass16_spec.  Rounding differs from it in the product order of the
+// column-(k+1) update and, for NEWTON = 1, in the reciprocal's last bits.
+// Measured on pivots spread over 1e-20 .. 1e20 (tests/test_gpu_graded_pivots.py,
+// which pins both: componentwise backward error max |K - L D L^T| / |L||D||L^T|,
+// u = 2^-53, bound 2 (N + 1) u; worst over N = 200 .. 2560): NEWTON = 1 29.3 u,
+// NEWTON = 2 29.3 u, colpass16_spec 29.3 u, the CPU reference 62.2 u -- per
+// order they differ by at most 6 u (N = 300: 22.6 / 16.8 / 16.8 u) -- and each
+// of the three is bitwise equivariant under power-of-two scaling.  NEWTON = 0
+// (v_rcp_f64 alone) leaves 3e8 u and fails that test, and so does a zero test
+// with a threshold (fabs(x) < 1e-15) in place of x == 0.0.
 template <int NEWTON>
 __device__ __forceinline__ void colpass16_short(double* M, double* dsh, int p, int lane) {
   const int row = 16 * p + lane;

@@ -78,7 +78,13 @@ __device__ unsigned long long g_hstamp[IPMZ_CHAIN_STAMP_BLOCKS][4];
 #define CSTAMP(jb, i) CSTAMP_T(0, jb, i)
 // the chain's column pass (diag64.h): 4 = colpass16_short<1>, the shorter
 // per-pivot chain (in-panel block 20.0 -> 19.5-19.7 us, kbench chainclk
-// N = 2560, profiles/r06_s/chain_cpv_ab.txt); 1 = colpass16_spec
+// N = 2560, profiles/r06_s/chain_cpv_ab.txt); 3 = colpass16_short<2>;
+// 1 = colpass16_spec.  One Newton step on v_rcp_f64 is enough: on pivots
+// spread over 1e-20 .. 1e20 the three forms give the same componentwise
+// backward error (worst 29.3 u each against a bound of 5122 u at N = 2560,
+// solves 7.2 u) and are bitwise scale-equivariant; none (colpass16_short<0>)
+// leaves 3e8 u.  tests/test_gpu_graded_pivots.py pins this (its docstring
+// has the figures of all three builds).
 #ifndef IPMZ_DIAG_CPV
 #define IPMZ_DIAG_CPV 4
 #endif
