@@ -10,21 +10,13 @@
 #include <climits>
 
 #include "common.h"
+#include "data_terms.h"
 #include "kernels.h"
 
 namespace ipmz {
 
 namespace {
-constexpr int NT = 256;
-
-// a grid of at most ~4096 workgroups: x over one QP's `per` work items (grid-stride), y over the QPs (looped)
-dim3 io_grid(int64_t per, int B) {
-  int64_t gx = (per + NT - 1) / NT;
-  gx = gx < 1 ? 1 : gx > 2048 ? 2048 : gx;
-  int64_t gy = 4096 / gx;
-  gy = gy < 1 ? 1 : gy > B ? B : gy;
-  return dim3((unsigned)gx, (unsigned)gy);
-}
+constexpr int NT = GRID_NT;  // (block_grid's workgroups)
 
 __device__ __forceinline__ unsigned long long wave_min_u64(unsigned long long v) {
   for (int off = 32; off > 0; off >>= 1) {
@@ -41,16 +33,16 @@ __device__ __forceinline__ unsigned long long wave_min_u64(unsigned long long v)
 // does not supply is the one the solver holds; a pair with neither side
 // supplied is not an item (nx / na = 0).  The smallest key of a violated item
 // wins whatever the schedule: one atomicMin per wave that saw one.
-__global__ void __launch_bounds__(NT) k_io_validate(const QPDev* __restrict__ qs, QpIoData in, int B, int nx, int na,
+__global__ void __launch_bounds__(NT) k_io_validate(const QPDev* __restrict__ qs, QpBlocksIn in, int B, int nx, int na,
                                                     unsigned long long* __restrict__ verdict) {
   const int per = nx + na;
   unsigned long long key = IPMZ_IO_VALID;
   for (int z = blockIdx.y; z < B; z += gridDim.y) {
     const QPDev& q = qs[z];
-    const double* lx = in.lx ? in.lx + (int64_t)z * in.slx : q.lx;
-    const double* ux = in.ux ? in.ux + (int64_t)z * in.sux : q.ux;
-    const double* lA = in.lA ? in.lA + (int64_t)z * in.slA : q.lA;
-    const double* uA = in.uA ? in.uA + (int64_t)z * in.suA : q.uA;
+    const double* lx = in.p[DB_LX] ? in.p[DB_LX] + (int64_t)z * in.sq[DB_LX] : q.lx;
+    const double* ux = in.p[DB_UX] ? in.p[DB_UX] + (int64_t)z * in.sq[DB_UX] : q.ux;
+    const double* lA = in.p[DB_LA] ? in.p[DB_LA] + (int64_t)z * in.sq[DB_LA] : q.lA;
+    const double* uA = in.p[DB_UA] ? in.p[DB_UA] + (int64_t)z * in.sq[DB_UA] : q.uA;
     for (int t = blockIdx.x * NT + threadIdx.x; t < per; t += gridDim.x * NT) {
       bool bad;
       int kind, k;
@@ -71,11 +63,11 @@ __global__ void __launch_bounds__(NT) k_io_validate(const QPDev* __restrict__ qs
   if ((threadIdx.x & 63) == 0 && key != IPMZ_IO_VALID) atomicMin(verdict, key);
 }
 
-hipError_t qp_io_validate(const QPBatch& qb, const QpIoData& in, unsigned long long* verdict, hipStream_t st) {
-  const int nx = (in.lx || in.ux) ? qb.h.n : 0, na = (in.lA || in.uA) ? qb.h.m_usr : 0;
+hipError_t qp_io_validate(const QPBatch& qb, const QpBlocksIn& in, unsigned long long* verdict, hipStream_t st) {
+  const int nx = (in.p[DB_LX] || in.p[DB_UX]) ? qb.h.n : 0, na = (in.p[DB_LA] || in.p[DB_UA]) ? qb.h.m_usr : 0;
   hipError_t e = hipMemsetAsync(verdict, 0xff, sizeof(unsigned long long), st);  // IPMZ_IO_VALID
   if (e != hipSuccess || nx + na == 0) return e;
-  hipLaunchKernelGGL(k_io_validate, io_grid(nx + na, qb.B), dim3(NT), 0, st, qb.d, in, qb.B, nx, na, verdict);
+  hipLaunchKernelGGL(k_io_validate, block_grid(nx + na, qb.B), dim3(NT), 0, st, qb.d, in, qb.B, nx, na, verdict);
   return hipGetLastError();
 }
 
@@ -122,22 +114,22 @@ __global__ void __launch_bounds__(NT) k_io_pack_matrix(const QPDev* __restrict__
 
 // The vector blocks in one launch: c, l_x, u_x (n), l_A, u_A (m_usr), d
 // (p_usr); with eqss the equality rows m_usr.. of l_A and u_A receive d too.
-__global__ void __launch_bounds__(NT) k_io_pack_vectors(const QPDev* __restrict__ qs, QpIoData in, int B) {
+__global__ void __launch_bounds__(NT) k_io_pack_vectors(const QPDev* __restrict__ qs, QpBlocksIn in, int B) {
   const int n = qs[0].n, m = qs[0].m_usr, p = qs[0].p_usr;
   for (int z = blockIdx.y; z < B; z += gridDim.y) {
     const QPDev& q = qs[z];
     for (int t = blockIdx.x * NT + threadIdx.x; t < n || t < m || t < p; t += gridDim.x * NT) {
       if (t < n) {
-        if (in.c) const_cast<double*>(q.c)[t] = in.c[(int64_t)z * in.sc + t];
-        if (in.lx) const_cast<double*>(q.lx)[t] = in.lx[(int64_t)z * in.slx + t];
-        if (in.ux) const_cast<double*>(q.ux)[t] = in.ux[(int64_t)z * in.sux + t];
+        if (in.p[DB_C]) const_cast<double*>(q.c)[t] = in.p[DB_C][(int64_t)z * in.sq[DB_C] + t];
+        if (in.p[DB_LX]) const_cast<double*>(q.lx)[t] = in.p[DB_LX][(int64_t)z * in.sq[DB_LX] + t];
+        if (in.p[DB_UX]) const_cast<double*>(q.ux)[t] = in.p[DB_UX][(int64_t)z * in.sq[DB_UX] + t];
       }
       if (t < m) {
-        if (in.lA) const_cast<double*>(q.lA)[t] = in.lA[(int64_t)z * in.slA + t];
-        if (in.uA) const_cast<double*>(q.uA)[t] = in.uA[(int64_t)z * in.suA + t];
+        if (in.p[DB_LA]) const_cast<double*>(q.lA)[t] = in.p[DB_LA][(int64_t)z * in.sq[DB_LA] + t];
+        if (in.p[DB_UA]) const_cast<double*>(q.uA)[t] = in.p[DB_UA][(int64_t)z * in.sq[DB_UA] + t];
       }
-      if (t < p && in.d) {
-        const double v = in.d[(int64_t)z * in.sd + t];
+      if (t < p && in.p[DB_D]) {
+        const double v = in.p[DB_D][(int64_t)z * in.sq[DB_D] + t];
         const_cast<double*>(q.d)[t] = v;
         if (q.eqss) const_cast<double*>(q.lA)[m + t] = const_cast<double*>(q.uA)[m + t] = v;
       }
@@ -145,27 +137,27 @@ __global__ void __launch_bounds__(NT) k_io_pack_vectors(const QPDev* __restrict_
   }
 }
 
-static bool io_vec_ok(const double* p, int64_t ld, int64_t sq) { return !((uintptr_t)p & 15) && !(ld & 1) && !(sq & 1); }
-
-hipError_t qp_io_pack(const QPBatch& qb, const QpIoData& in, hipStream_t st) {
+hipError_t qp_io_pack(const QPBatch& qb, const QpBlocksIn& in, hipStream_t st) {
   const QPDev& h = qb.h;
-  const struct {
-    const double* p;
-    int64_t ld, sq;
-    int rows;
-  } mats[3] = {{in.Q, in.ldq, in.sQ, h.n}, {in.A, in.lda, in.sA, h.m_usr}, {in.C, in.ldc, in.sC, h.p_usr}};
-  for (int w = 0; w < 3; ++w) {
-    if (!mats[w].p || mats[w].rows == 0) continue;
-    if (io_vec_ok(mats[w].p, mats[w].ld, mats[w].sq))
-      hipLaunchKernelGGL(k_io_pack_matrix<true>, io_grid((int64_t)mats[w].rows * ((h.n + 1) / 2), qb.B), dim3(NT), 0, st,
-                         qb.d, mats[w].p, mats[w].ld, mats[w].sq, mats[w].rows, w, qb.B);
+  const int dims[3] = {h.n, h.m_usr, h.p_usr};  // (the data's rows: the equality-slack handlings run C's as A's)
+  bool vectors = false;
+  for (int w = 0; w < DB_COUNT; ++w) {
+    if (!in.p[w]) continue;
+    if (!DATA_BLOCKS[w].matrix) {
+      vectors = true;
+      continue;
+    }
+    const int rows = dims[DATA_BLOCKS[w].dim];
+    if (vec16_ok(in.p[w], in.ld[w], in.sq[w]))
+      hipLaunchKernelGGL(k_io_pack_matrix<true>, block_grid((int64_t)rows * ((h.n + 1) / 2), qb.B), dim3(NT), 0, st, qb.d,
+                         in.p[w], in.ld[w], in.sq[w], rows, w, qb.B);
     else
-      hipLaunchKernelGGL(k_io_pack_matrix<false>, io_grid((int64_t)mats[w].rows * h.n, qb.B), dim3(NT), 0, st, qb.d,
-                         mats[w].p, mats[w].ld, mats[w].sq, mats[w].rows, w, qb.B);
+      hipLaunchKernelGGL(k_io_pack_matrix<false>, block_grid((int64_t)rows * h.n, qb.B), dim3(NT), 0, st, qb.d, in.p[w],
+                         in.ld[w], in.sq[w], rows, w, qb.B);
   }
-  if (in.c || in.lx || in.ux || in.lA || in.uA || in.d) {
-    const int mx = h.n > h.m_usr ? (h.n > h.p_usr ? h.n : h.p_usr) : (h.m_usr > h.p_usr ? h.m_usr : h.p_usr);
-    hipLaunchKernelGGL(k_io_pack_vectors, io_grid(mx, qb.B), dim3(NT), 0, st, qb.d, in, qb.B);
+  if (vectors) {
+    const int mp = dims[1] > dims[2] ? dims[1] : dims[2];
+    hipLaunchKernelGGL(k_io_pack_vectors, block_grid(h.n > mp ? h.n : mp, qb.B), dim3(NT), 0, st, qb.d, in, qb.B);
   }
   return hipGetLastError();
 }
@@ -190,7 +182,7 @@ __global__ void __launch_bounds__(NT) k_io_gather_state(const QPDev* __restrict_
 }
 
 hipError_t qp_gather_state(const QPBatch& qb, int which, double* dst, int64_t ld, hipStream_t st) {
-  hipLaunchKernelGGL(k_io_gather_state, io_grid(qb.h.state_len, qb.B), dim3(NT), 0, st, qb.d, which, dst, ld, qb.B);
+  hipLaunchKernelGGL(k_io_gather_state, block_grid(qb.h.state_len, qb.B), dim3(NT), 0, st, qb.d, which, dst, ld, qb.B);
   return hipGetLastError();
 }
 

@@ -6,13 +6,12 @@
 //
 // Every r_v of residual_elem (newton.hip) is affine in the data, so R is r's
 // linear part in the data evaluated at the tangents.  The vector tangents enter
-// one element each (vec_tangent_row below: the coefficients grad.hip's
-// vec_grad_elem transposes); the three matrices enter through their products
-// with the iterate,
+// one element each (vec_term, data_terms.h: the terms grad.hip transposes); the
+// three matrices enter through their products with the iterate,
 //
 //     dQ x,   dA x,   dA^T a_dual,   dC x,   dC^T lambda_C
 //
-// (a_dual = lambda_A, or lambda_h - lambda_g for NaiveSlacks: jvp_dual below).
+// (a_dual = lambda_A, or lambda_h - lambda_g for NaiveSlacks: data_dual, data_terms.h).
 //
 // Two kinds of launches, stream-ordered, no atomics, nothing waits on another
 // workgroup:
@@ -49,6 +48,7 @@
 //                   row loop: batch * ntan > ROWS_GY; element loop: max(n, m,
 //                   p) > 256 * VGX (VGX = 2048) -- out of reach
 #include "common.h"
+#include "data_terms.h"
 #include "kernels.h"
 
 namespace ipmz {
@@ -59,19 +59,6 @@ constexpr int NW = NT / 64;
 constexpr int ROWS_GY = IPMZ_JVP_ROWS_GY;  // gridDim.y of the launches that loop over the rows (q, t)
 constexpr int VGX = 2048;
 constexpr int NJ = 4;  // 16-QP tiles of one wave's strip (they share the tangent operand)
-
-enum { J_Q = 0, J_A = 1, J_A_NAIVE = 2, J_C = 3 };
-
-// the vector the transposed product multiplies, element i: r_x has + (A^T*lambda_A), + (A^T*(lambda_h - lambda_g))
-// for NaiveSlacks (newton.hip a_dual), + (C^T*lambda_C)
-template <int MODE>
-__device__ __forceinline__ double jvp_dual(const QPDev& q, int i) {
-  if (MODE == J_A) return q.v[LA][i];
-  if (MODE == J_A_NAIVE) return q.v[LH][i] + (-q.v[LG][i]);
-  return q.v[LC][i];
-}
-
-__device__ __forceinline__ int64_t slot_off(const QPDev& q0, int slot) { return q0.r[slot] - q0.r[0]; }
 
 __device__ __forceinline__ const double* tan_at(const double* p, int64_t sq, int64_t tq, int z, int t) {
   return p ? p + (int64_t)z * sq + (int64_t)t * tq : nullptr;
@@ -84,7 +71,7 @@ __device__ __forceinline__ const double* tan_at(const double* p, int64_t sq, int
 // NP columns, lane l on the pairs 128 k + 2 l (consecutive lanes on
 // consecutive 16 bytes); a wave takes rows w, w + 4, ... of the chunk two at a
 // time (both rows' loads in flight together).  Row i's partial dot with x over
-// the tile -> ws row part [tile][i]; MODE != J_Q: the chunk's column sums
+// the tile -> ws row part [tile][i]; MODE != DM_Q: the chunk's column sums
 // against the dual, per lane, the four waves' sums added in wave order through
 // LDS -> ws column part [chunk][j].  VEC: 16-byte loads of whole pairs (the
 // host checked pointer and strides, n >= 2); the last element of an odd n is
@@ -152,14 +139,14 @@ __global__ void __launch_bounds__(NT) k_jvp_matrix(const QPDev* __restrict__ qs,
         for (int k = 0; k < 2 * NP; ++k) s += e[u][k] * xv[k];
         s = wave_sum(s);
         if (lane == 0) w[pm.off_row + (int64_t)ct * rows + iu] = s;
-        if (MODE != J_Q) {
-          const double y = jvp_dual<MODE>(q, iu);
+        if (MODE != DM_Q) {
+          const double y = data_dual<MODE>(q, iu);
 #pragma unroll
           for (int k = 0; k < 2 * NP; ++k) col[k] += e[u][k] * y;
         }
       }
     }
-    if (MODE != J_Q) {
+    if (MODE != DM_Q) {
       if (wave > 0) {
 #pragma unroll
         for (int k = 0; k < 2 * NP; ++k) sh[wave - 1][128 * (k >> 1) + 2 * lane + (k & 1)] = col[k];
@@ -215,14 +202,14 @@ __global__ void __launch_bounds__(NT) k_jvp_shared(const QPDev* __restrict__ qs,
   const int kk = tid & (KC - 1), r0 = tid / KC;
   constexpr int NR = SB * KC / NT;  // 8 rows per thread
   const double* ya[NR];
-  const double* yb[NR];  // (J_A_NAIVE: lambda_g)
+  const double* yb[NR];  // (DM_A_NAIVE: lambda_g)
   bool zok[NR];
 #pragma unroll
   for (int r = 0; r < NR; ++r) {
     const int z = z0 + r0 + (NT / KC) * r;
     zok[r] = z < B;
     const QPDev& q = qs[zok[r] ? z : z0];
-    ya[r] = !TRANS ? q.v[X] : MODE == J_A ? q.v[LA] : MODE == J_A_NAIVE ? q.v[LH] : q.v[LC];
+    ya[r] = !TRANS ? q.v[X] : MODE == DM_A ? q.v[LA] : MODE == DM_A_NAIVE ? q.v[LH] : q.v[LC];
     yb[r] = q.v[LG];
   }
   MF::acc_t acc[NJ];
@@ -235,7 +222,7 @@ __global__ void __launch_bounds__(NT) k_jvp_shared(const QPDev* __restrict__ qs,
 #pragma unroll
     for (int r = 0; r < NR; ++r) {
       double y = ya[r][kc];
-      if (TRANS && MODE == J_A_NAIVE) y = y + (-yb[r][kc]);
+      if (TRANS && MODE == DM_A_NAIVE) y = y + (-yb[r][kc]);
       yv[r] = (kok && zok[r]) ? y : 0.0;
     }
     if (!TRANS) {
@@ -282,19 +269,16 @@ __global__ void __launch_bounds__(NT) k_jvp_shared(const QPDev* __restrict__ qs,
 // Launch 2: every element of every row (q, t) of R, exactly once -- the vector
 // tangents' terms plus the products, each a sum of its partials in their
 // order, added in the order Q, A, C (file header).  Element e of the n, m and p
-// blocks at once (update_rows), the coefficients of residual_elem's data
-// terms: r_x = (c + ...); (l_x + y - x), (x + z - u_x), (l_A + g - s | (A*x)),
-// (h + s | (A*x) - u_A); Slacks ((X - L_x)*lambda_y), ((U_x - X)*lambda_z),
-// ((S - L_A)*lambda_g), ((U_A - S)*lambda_h); every r_lambda_C has (C*x) - d.
-// r_s, r_p, the complementarity rows of the slacked forms and a row no given
-// tangent enters: 0.  Per-QP and shared vector tangents differ by the QP
-// stride only.
+// blocks at once (update_rows); every data term is data_terms.h's (vec_term of
+// the tangent's element; the row each product enters).  r_s, r_p, the
+// complementarity rows of the slacked forms and a row no given tangent enters:
+// 0.  Per-QP and shared vector tangents differ by the QP stride only.
 __device__ __forceinline__ double part_sum(const double* __restrict__ p, int count, int64_t stride, int idx) {
   double s = p[idx];
   for (int k = 1; k < count; ++k) s += p[(int64_t)k * stride + idx];
   return s;
 }
-__global__ void __launch_bounds__(NT) k_jvp_rows(const QPDev* __restrict__ qs, QpTanIn in, JvpPlan pl, int ntan, int B,
+__global__ void __launch_bounds__(NT) k_jvp_rows(const QPDev* __restrict__ qs, QpBlocksIn in, JvpPlan pl, int ntan, int B,
                                                  const double* __restrict__ ws, double* __restrict__ R, int64_t ldr,
                                                  int64_t sR) {
   const QPDev& q0 = qs[0];
@@ -307,25 +291,25 @@ __global__ void __launch_bounds__(NT) k_jvp_rows(const QPDev* __restrict__ qs, Q
     const QPDev& q = qs[z];
     double* __restrict__ r = R + (int64_t)z * sR + (int64_t)t * ldr;
     const double* __restrict__ w = ws + zt * pl.seg;
-    const double* dc = tan_at(in.c, in.sc, in.tc, z, t);
-    const double* dlx = tan_at(in.lx, in.slx, in.tlx, z, t);
-    const double* dux = tan_at(in.ux, in.sux, in.tux, z, t);
-    const double* dlA = tan_at(in.lA, in.slA, in.tlA, z, t);
-    const double* duA = tan_at(in.uA, in.suA, in.tuA, z, t);
-    const double* dd = tan_at(in.d, in.sd, in.td, z, t);
+    const double* dc = tan_at(in.p[DB_C], in.sq[DB_C], in.tq[DB_C], z, t);
+    const double* dlx = tan_at(in.p[DB_LX], in.sq[DB_LX], in.tq[DB_LX], z, t);
+    const double* dux = tan_at(in.p[DB_UX], in.sq[DB_UX], in.tq[DB_UX], z, t);
+    const double* dlA = tan_at(in.p[DB_LA], in.sq[DB_LA], in.tq[DB_LA], z, t);
+    const double* duA = tan_at(in.p[DB_UA], in.sq[DB_UA], in.tq[DB_UA], z, t);
+    const double* dd = tan_at(in.p[DB_D], in.sq[DB_D], in.tq[DB_D], z, t);
     for (int e = blockIdx.x * NT + threadIdx.x; e < mx; e += gridDim.x * NT) {
       if (e < n) {
-        double s = dc ? dc[e] : 0.0;
+        double s = dc ? vec_term<0>(q0, q, e, dc[e]) : 0.0;
         if (mq.mode) s = s + part_sum(w + mq.off_row, mq.nct, n, e);
         if (ma.mode) s = s + part_sum(w + ma.off_col, ma.nchunk, n, e);
         if (mc.mode) s = s + part_sum(w + mc.off_col, mc.nchunk, n, e);
         r[e] = s;
         if (q0.vlo) {
-          r[slot_off(q0, LY) + e] = !dlx ? 0.0 : q0.slacks ? -(q.v[LY][e] * dlx[e]) : dlx[e];
+          r[slot_off(q0, LY) + e] = dlx ? vec_term<1>(q0, q, e, dlx[e]) : 0.0;
           if (!q0.slacks) r[slot_off(q0, Y) + e] = 0.0;
         }
         if (q0.vup) {
-          r[slot_off(q0, LZ) + e] = !dux ? 0.0 : q0.slacks ? q.v[LZ][e] * dux[e] : -dux[e];
+          r[slot_off(q0, LZ) + e] = dux ? vec_term<2>(q0, q, e, dux[e]) : 0.0;
           if (!q0.slacks) r[slot_off(q0, Z) + e] = 0.0;
         }
       }
@@ -333,18 +317,18 @@ __global__ void __launch_bounds__(NT) k_jvp_rows(const QPDev* __restrict__ qs, Q
         const double ax = ma.mode ? part_sum(w + ma.off_row, ma.nct, m, e) : 0.0;
         if (!q0.naive) r[slot_off(q0, LA) + e] = ax, r[slot_off(q0, S) + e] = 0.0;  // ((A*x) - s)
         if (q0.alo) {
-          const double v = !dlA ? 0.0 : q0.slacks ? -(q.v[LG][e] * dlA[e]) : dlA[e];
+          const double v = dlA ? vec_term<3>(q0, q, e, dlA[e]) : 0.0;
           r[slot_off(q0, LG) + e] = (q0.naive && ma.mode) ? v + (-ax) : v;  // (l_A + g - (A*x))
           if (!q0.slacks) r[slot_off(q0, G) + e] = 0.0;
         }
         if (q0.aup) {
-          const double v = !duA ? 0.0 : q0.slacks ? q.v[LH][e] * duA[e] : -duA[e];
+          const double v = duA ? vec_term<4>(q0, q, e, duA[e]) : 0.0;
           r[slot_off(q0, LH) + e] = (q0.naive && ma.mode) ? v + ax : v;  // (h + (A*x) - u_A)
           if (!q0.slacks) r[slot_off(q0, H) + e] = 0.0;
         }
       }
       if (e < p) {
-        const double v = dd ? -dd[e] : 0.0;  // ((C*x) ... - d) in all three equality handlings
+        const double v = dd ? vec_term<5>(q0, q, e, dd[e]) : 0.0;  // ((C*x) ... - d)
         r[slot_off(q0, LC) + e] = mc.mode ? part_sum(w + mc.off_row, mc.nct, p, e) + v : v;
         if (!(q0.eqnone || q0.eqpen)) r[slot_off(q0, P) + e] = 0.0;
       }
@@ -355,17 +339,15 @@ __global__ void __launch_bounds__(NT) k_jvp_rows(const QPDev* __restrict__ qs, Q
 // ---------------------------------------------------------------------------
 int jvp_pairs(int n) { return n <= 128 ? 1 : n <= 256 ? 2 : 4; }
 
-JvpPlan qp_jvp_plan(const QPBatch& qb, const QpTanIn& in) {
+JvpPlan qp_jvp_plan(const QPBatch& qb, const QpBlocksIn& in) {
   const QPDev& h = qb.h;
   JvpPlan pl{};
-  const double* ptr[3] = {in.Q, in.A, in.C};
-  const int64_t sq[3] = {in.sQ, in.sA, in.sC};
-  const int rows[3] = {h.n, h.m, h.p};
+  const int rows[DB_MATS] = {h.n, h.m, h.p};
   int64_t off = 0;
-  for (int w = 0; w < 3; ++w) {
+  for (int w = 0; w < DB_MATS; ++w) {
     JvpMat& mt = pl.mat[w];
-    if (!ptr[w] || rows[w] == 0) continue;
-    if (qb.B > 1 && sq[w] == 0) {
+    if (!in.p[w] || rows[w] == 0) continue;
+    if (qb.B > 1 && in.sq[w] == 0) {
       mt.mode = 2, mt.rch = rows[w], mt.nchunk = 1, mt.nct = 1;
     } else {
       mt.mode = 1;
@@ -380,10 +362,6 @@ JvpPlan qp_jvp_plan(const QPBatch& qb, const QpTanIn& in) {
   }
   pl.seg = off;
   return pl;
-}
-
-static bool jvp_vec_ok(const double* p, int64_t ld, int64_t sq, int64_t tq, int n) {
-  return n >= 2 && !((uintptr_t)p & 15) && !(ld & 1) && !(sq & 1) && !(tq & 1);
 }
 
 template <bool VEC, int MODE>
@@ -406,53 +384,41 @@ static void launch_shared(bool trans, dim3 grid, hipStream_t st, const QPDev* qs
     hipLaunchKernelGGL((k_jvp_shared<MODE, false>), grid, dim3(NT), 0, st, qs, T, ld, tq, rows, ntan, B, ws, seg, off);
 }
 
-hipError_t qp_data_jvp(const QPBatch& qb, int ntan, const QpTanIn& in, double* R, int64_t ldr, int64_t sR, double* ws,
+hipError_t qp_data_jvp(const QPBatch& qb, int ntan, const QpBlocksIn& in, double* R, int64_t ldr, int64_t sR, double* ws,
                        hipStream_t st) {
   const QPDev& h = qb.h;
   const int B = qb.B;
   const JvpPlan pl = qp_jvp_plan(qb, in);
   const int64_t total = (int64_t)B * ntan;
   const unsigned gy = (unsigned)(total < ROWS_GY ? total : ROWS_GY);
-  const struct {
-    const double* p;
-    int64_t ld, sq, tq;
-    int rows, mode;
-  } mats[3] = {{in.Q, in.ldq, in.sQ, in.tQ, h.n, J_Q},
-               {in.A, in.lda, in.sA, in.tA, h.m, h.naive ? J_A_NAIVE : J_A},
-               {in.C, in.ldc, in.sC, in.tC, h.p, J_C}};
-  for (int w = 0; w < 3; ++w) {
+  const int dims[3] = {h.n, h.m, h.p};
+  for (int w = 0; w < DB_MATS; ++w) {
     const JvpMat& pm = pl.mat[w];
     if (!pm.mode) continue;
-    const int rows = mats[w].rows, mode = mats[w].mode;
+    const int rows = dims[DATA_BLOCKS[w].dim], mode = data_mode(w, h);
     if (pm.mode == 2) {  // shared: the batch is a tile dimension
       const int nstrip = (B + SB - 1) / SB;
       for (int tr = 0; tr < (w ? 2 : 1); ++tr) {
         const int ntile = ((tr ? h.n : rows) + SB - 1) / SB;
         const dim3 grid((unsigned)(ntile * nstrip), (unsigned)ntan);
         const int64_t off = tr ? pm.off_col : pm.off_row;
-#define IPMZ_JVP_SHARED(M) launch_shared<M>(tr != 0, grid, st, qb.d, mats[w].p, mats[w].ld, mats[w].tq, rows, ntan, B, ws, pl.seg, off)
-        if (mode == J_Q) IPMZ_JVP_SHARED(J_Q);
-        else if (mode == J_A) IPMZ_JVP_SHARED(J_A);
-        else if (mode == J_A_NAIVE) IPMZ_JVP_SHARED(J_A_NAIVE);
-        else IPMZ_JVP_SHARED(J_C);
-#undef IPMZ_JVP_SHARED
+        with_data_mode(mode, [&](auto M) {
+          launch_shared<decltype(M)::value>(tr != 0, grid, st, qb.d, in.p[w], in.ld[w], in.tq[w], rows, ntan, B, ws, pl.seg,
+                                            off);
+        });
       }
       continue;
     }
-    const int64_t sq = B > 1 ? mats[w].sq : 0;
+    const int64_t sq = B > 1 ? in.sq[w] : 0;
     const dim3 grid((unsigned)(pm.nchunk * pm.nct), gy);
-    const bool vec = jvp_vec_ok(mats[w].p, mats[w].ld, sq, ntan > 1 ? mats[w].tq : 0, h.n);
+    // 16-byte loads of whole pairs (a call with one tangent does not use the tangent stride)
+    const bool vec = h.n >= 2 && vec16_ok(in.p[w], in.ld[w], sq) && !(ntan > 1 && (in.tq[w] & 1));
     const int np = jvp_pairs(h.n);
-#define IPMZ_JVP_MATRIX(M)                                                                                              \
-  do {                                                                                                                  \
-    if (vec) launch_matrix<true, M>(np, grid, st, qb.d, mats[w].p, mats[w].ld, sq, mats[w].tq, rows, ntan, B, pm, ws, pl.seg); \
-    else launch_matrix<false, M>(np, grid, st, qb.d, mats[w].p, mats[w].ld, sq, mats[w].tq, rows, ntan, B, pm, ws, pl.seg);    \
-  } while (0)
-    if (mode == J_Q) IPMZ_JVP_MATRIX(J_Q);
-    else if (mode == J_A) IPMZ_JVP_MATRIX(J_A);
-    else if (mode == J_A_NAIVE) IPMZ_JVP_MATRIX(J_A_NAIVE);
-    else IPMZ_JVP_MATRIX(J_C);
-#undef IPMZ_JVP_MATRIX
+    with_data_mode(mode, [&](auto M) {
+      constexpr int MODE = decltype(M)::value;
+      if (vec) launch_matrix<true, MODE>(np, grid, st, qb.d, in.p[w], in.ld[w], sq, in.tq[w], rows, ntan, B, pm, ws, pl.seg);
+      else launch_matrix<false, MODE>(np, grid, st, qb.d, in.p[w], in.ld[w], sq, in.tq[w], rows, ntan, B, pm, ws, pl.seg);
+    });
   }
   int64_t gx = (update_rows(h) + NT - 1) / NT;
   gx = gx > VGX ? VGX : gx;

@@ -562,17 +562,38 @@ hipError_t qp_fused_solves(const QPBatch& qb, const double* K, int64_t ld, int N
                            double* b, int64_t sK, int64_t sD, int64_t sL, int64_t sb, int freeze, hipStream_t st);
 hipError_t qp_fused_eval(const QPBatch& qb, hipStream_t st);
 
-// io.hip ---------------------------------------------------------------------
-// A caller's problem data in device memory (ipmz_qp_device_data with the
-// blocks this call does not take -- not supplied, or of dimension 0 -- null):
-// matrices with a row stride and a QP stride, vectors with a QP stride, in
-// elements; a QP stride of 0 is one block shared by every QP.
-struct QpIoData {
-  const double *Q, *A, *C;
-  int64_t ldq, sQ, lda, sA, ldc, sC;
-  const double *c, *lx, *ux, *lA, *uA, *d;
-  int64_t sc, slx, sux, slA, suA, sd;
+// io.hip, grad.hip, jvp.hip ---------------------------------------------------
+// The nine blocks of a QP's data as a caller hands them over in device memory (ipmz_qp_device_data, _grad and
+// _tangent of the public header), described once for the load, the gradient and the tangents: this index, one row
+// of DATA_BLOCKS per block, and one descriptor type.  HELD_*: ipmz_qp::held, a bit per block the solver holds.
+enum DataBlock { DB_Q = 0, DB_A, DB_CEQ, DB_C, DB_LX, DB_UX, DB_LA, DB_UA, DB_D, DB_COUNT, DB_MATS = DB_C };
+enum : unsigned {
+  HELD_Q = 1, HELD_C = 2, HELD_A = 4, HELD_LA = 8, HELD_UA = 16, HELD_CEQ = 32, HELD_D = 64, HELD_LX = 128,
+  HELD_UX = 256, HELD_ALL = 511
 };
+struct DataBlockInfo {
+  const char* name;  // as the messages print it
+  bool matrix;       // rows of n elements with a row stride; else a vector
+  int dim;           // which of the solver's dimensions (0 / 1 / 2: n / m / p) gives its rows, or a vector's length
+  unsigned held;
+};
+constexpr DataBlockInfo DATA_BLOCKS[DB_COUNT] = {
+    {"Q", true, 0, HELD_Q},      {"A", true, 1, HELD_A},      {"C", true, 2, HELD_CEQ},
+    {"c", false, 0, HELD_C},     {"l_x", false, 0, HELD_LX},  {"u_x", false, 0, HELD_UX},
+    {"l_A", false, 1, HELD_LA},  {"u_A", false, 1, HELD_UA},  {"d", false, 2, HELD_D}};
+// The blocks of one call (those it does not take -- null, not wanted, or of dimension 0 -- null): block k of QP z,
+// tangent t starts at p[k] + z sq[k] + t tq[k], row i of a matrix ld[k] elements further each; strides in elements.
+// A QP stride of 0 (batches) is one block for every QP: shared data or tangents, a gradient summed over the batch.
+// T: const double for the load and the tangents, double for the gradient; tq: the tangents only (else 0).
+// A kernel indexes the members with literal or fully unrolled constants only: a by-value kernel argument indexed
+// at run time is copied to scratch.
+template <class T>
+struct QpBlocks {
+  T* p[DB_COUNT];
+  int64_t sq[DB_COUNT], tq[DB_COUNT], ld[DB_MATS];
+};
+typedef QpBlocks<const double> QpBlocksIn;
+typedef QpBlocks<double> QpBlocksOut;
 // The bound check's verdict word: IPMZ_IO_VALID, or the smallest key of a
 // violated bound in the order (QP, l_x < u_x before l_A <= u_A, index)
 constexpr unsigned long long IPMZ_IO_VALID = ~0ull;
@@ -582,25 +603,15 @@ constexpr unsigned long long io_key(int qp, int kind, int k) {
 // build_environment's check (!(l_x < u_x), !(l_A <= u_A): NaN is a violation)
 // of the bound pairs of which `in` supplies a side, the other side being the
 // solver's; resets and fills *verdict (device).  Independent of scheduling.
-hipError_t qp_io_validate(const QPBatch& qb, const QpIoData& in, unsigned long long* verdict, hipStream_t st);
+hipError_t qp_io_validate(const QPBatch& qb, const QpBlocksIn& in, unsigned long long* verdict, hipStream_t st);
 // every supplied block into the solver's storage: exactly the elements the
 // host load writes (columns [n, ldn) and the space between QPs keep their bits)
-hipError_t qp_io_pack(const QPBatch& qb, const QpIoData& in, hipStream_t st);
+hipError_t qp_io_pack(const QPBatch& qb, const QpBlocksIn& in, hipStream_t st);
 // row z of dst (device, row stride ld >= state_len) <- QP z's state `which`
 // (IPMZ_STATE_*) in the reference's Newton order; one launch, no allocation
 hipError_t qp_gather_state(const QPBatch& qb, int which, double* dst, int64_t ld, hipStream_t st);
 
 // grad.hip -------------------------------------------------------------------
-// A caller's gradient blocks in device memory (ipmz_qp_device_grad with the
-// blocks this call does not write -- not wanted, or of dimension 0 -- null):
-// QpIoData's description with writable blocks.  A QP stride of 0 (batches) is
-// one block that receives the sum over the QPs.
-struct QpGradOut {
-  double *Q, *A, *C;
-  int64_t ldq, sQ, lda, sA, ldc, sC;
-  double *c, *lx, *ux, *lA, *uA, *d;
-  int64_t sc, slx, sux, slA, suA, sd;
-};
 // QPs per chunk of the shared matrix blocks' sum over the batch: every chunk's
 // partial product is one tile set of the workspace, summed in chunk order
 #define IPMZ_VJP_KCHUNK 64
@@ -610,21 +621,10 @@ int64_t qp_grad_part_elems(const QPBatch& qb);
 // IPMZ_STATE_RES, into the blocks of o; part: the workspace above, read and
 // written only when a matrix block is shared (may be null otherwise).
 // Stream-ordered launches, no atomics; reads the iterate and W only
-hipError_t qp_data_vjp(const QPBatch& qb, const double* W, int64_t sW, const QpGradOut& o, double* part,
+hipError_t qp_data_vjp(const QPBatch& qb, const double* W, int64_t sW, const QpBlocksOut& o, double* part,
                        hipStream_t st);
 
 // jvp.hip --------------------------------------------------------------------
-// A caller's tangents of the problem data in device memory
-// (ipmz_qp_device_tangent with the blocks this call does not take -- null, or of
-// dimension 0 -- null): QpIoData's description plus a tangent stride per block;
-// tangent t of QP z of block X starts at X + z sX + t tX.  A QP stride of 0
-// (batches) is one set of tangents shared by every QP.
-struct QpTanIn {
-  const double *Q, *A, *C;
-  int64_t ldq, sQ, tQ, lda, sA, tA, ldc, sC, tC;
-  const double *c, *lx, *ux, *lA, *uA, *d;
-  int64_t sc, tc, slx, tlx, sux, tux, slA, tlA, suA, tuA, sd, td;
-};
 // gridDim.y of the launches that loop over the rows (q, t) of R
 #define IPMZ_JVP_ROWS_GY 16384
 // Where one matrix block's products lie in a row's segment of the workspace,
@@ -641,14 +641,14 @@ struct JvpPlan {
   int64_t seg;    // doubles per row (q, t); the workspace holds batch * ntan segments
 };
 // a function of the shape, of which blocks are given and of which are shared -- not of ntan or the batch size
-JvpPlan qp_jvp_plan(const QPBatch& qb, const QpTanIn& in);
+JvpPlan qp_jvp_plan(const QPBatch& qb, const QpBlocksIn& in);
 // column pairs per lane of k_jvp_matrix's column tile (128 of them columns each), by n
 int jvp_pairs(int n);
 // row (z, t) of R (at R + z sR + t ldr, the layout of IPMZ_STATE_RES, all
 // state_len elements) <- (d r / d data) applied to tangent t of QP z; ws: the
 // workspace above (may be null when no matrix block is given).  Stream-ordered
 // launches, no atomics; reads the iterate and the tangents only
-hipError_t qp_data_jvp(const QPBatch& qb, int ntan, const QpTanIn& in, double* R, int64_t ldr, int64_t sR, double* ws,
+hipError_t qp_data_jvp(const QPBatch& qb, int ntan, const QpBlocksIn& in, double* R, int64_t ldr, int64_t sR, double* ws,
                        hipStream_t st);
 
 }  // namespace ipmz

@@ -19,6 +19,7 @@
 #include <type_traits>
 
 #include "common.h"
+#include "data_terms.h"  // a_dual: the vector A^T multiplies in r_x
 #include "kernels.h"
 #include "sync.h"
 #include "trsv_small.h"
@@ -219,12 +220,6 @@ __global__ __launch_bounds__(NT) void k_matvec_rows(const QPDev* __restrict__ qs
   if (row >= rows) return;
   const double s = row_dot(M + (int64_t)row * q.ldn, x, cols, lane);
   if (lane == 0) out[row] = s;
-}
-
-// the vector A^T multiplies in r_x: lambda_A, or (lambda_h - lambda_g) for
-// NaiveSlacks ("(A^T * (lambda_h - lambda_g))", formulations.txt)
-__device__ __forceinline__ double a_dual(const QPDev& q, int i) {
-  return q.naive ? q.v[LH][i] + (-q.v[LG][i]) : q.v[LA][i];
 }
 
 // A^T lambda_A -> ATl, C^T lambda_C -> CTl: column blocks of NT x row chunks

@@ -160,11 +160,92 @@ int grow(ipmz_qp* s, GrowBuf& b, size_t bytes, bool zero = false) {
   return fail(IPMZ_ERR_NOMEM, "device allocation failed");
 }
 
-// ipmz_qp::held
-enum : unsigned {
-  HELD_Q = 1, HELD_C = 2, HELD_A = 4, HELD_LA = 8, HELD_UA = 16, HELD_CEQ = 32, HELD_D = 64, HELD_LX = 128,
-  HELD_UX = 256, HELD_ALL = 511
+// grow() for a call that only enqueues and so may run inside a caller's graph capture, where nothing can be
+// allocated: IPMZ_ERR_STATE then, `why` ending the message.  (Launches of earlier calls may still read the old
+// buffer: hipFree waits for the device.)
+int grow_unless_capturing(ipmz_qp* s, GrowBuf& b, size_t need, const std::string& who, const char* why) {
+  if (need <= b.bytes) return IPMZ_OK;
+  hipStreamCaptureStatus cs = hipStreamCaptureStatusNone;
+  HIP_OK(hipStreamIsCapturing(s->ctx->stream, &cs));
+  if (cs != hipStreamCaptureStatusNone)
+    return fail(IPMZ_ERR_STATE, who + ": the context's stream is capturing a hipGraph and " + why);
+  return grow(s, b, need);
+}
+
+// The calls that serve the augmented fp64 systems in the Newton order only (newton_multi, ipmz_batch_data_vjp,
+// ipmz_batch_data_jvp) refuse everything else first, in this order
+int refuse_unless_newton_order(const ipmz_qp* s, const std::string& who) {
+  if (s->normal) return fail(IPMZ_ERR_INVALID, who + ": the normal-equations reduction is enabled (augmented system only)");
+  if (s->mixed) return fail(IPMZ_ERR_INVALID, who + ": mixed precision is enabled (fp64 factors only)");
+  if (s->eqss)
+    return fail(IPMZ_ERR_INVALID, who + ": EqualityHandling::SlackedSlacks / NaiveSlacks keep a permuted, merged view of "
+                                        "the Newton order on the device; not served");
+  if (!s->loaded) return fail(IPMZ_ERR_STATE, who + ": load (and initialize) the QP first");
+  return IPMZ_OK;
+}
+
+// A caller's ipmz_qp_device_data (ipmz_qp_device_grad has its layout; tq: ipmz_qp_device_tangent's strides in the
+// table's order, or null) as the kernels' descriptor.  dims: n, m, p as the call counts them -- the load the data's
+// rows (m_usr, p_usr), the other two the step's.  Blocks of dimension 0 are ignored whatever they hold.
+static_assert(sizeof(ipmz_qp_device_grad) == sizeof(ipmz_qp_device_data), "one layout");
+template <class T>
+QpBlocks<T> data_blocks(const ipmz_qp_device_data& d, const int64_t* tq, const int (&dims)[3]) {
+  const double* const ptr[DB_COUNT] = {d.Q, d.A, d.C, d.c, d.l_x, d.u_x, d.l_A, d.u_A, d.d};
+  const int64_t ld[DB_MATS] = {d.ldq, d.lda, d.ldc};
+  const int64_t sq[DB_COUNT] = {d.sQ, d.sA, d.sC, d.sc, d.slx, d.sux, d.slA, d.suA, d.sd};
+  QpBlocks<T> b{};
+  for (int k = 0; k < DB_COUNT; ++k) {
+    if (!dims[DATA_BLOCKS[k].dim]) continue;
+    b.p[k] = const_cast<T*>(ptr[k]);
+    if (k < DB_MATS) b.ld[k] = ld[k];
+    b.sq[k] = sq[k];
+    if (tq) b.tq[k] = tq[k];
+  }
+  return b;
+}
+
+// What differs between the three calls' checks of their blocks -- and nothing else does
+struct BlockRules {
+  const char* zero_means;  // a QP stride of 0, as the message says it: "shared", "summed over the batch"
+  int ntan;                // tangents per QP; < 0: the call has no tangent strides (the load, the gradient)
+  bool one_qp_ignores_sq;  // a solver of one QP does not look at its QP strides (the tangents); the load and the
+                           // gradient refuse a negative one even there
+  bool one_tangent_ignores_tq;  // a call with at most one tangent does not look at its tangent strides
 };
+struct BlockFacts {
+  unsigned supplied;   // the HELD_* bits of the blocks given
+  bool shared_matrix;  // a matrix block has QP stride 0 in a batch
+};
+// Every given block of b in the table's order: the row stride at least n, no negative stride, the tangent stride at
+// least the block's extent, the QP stride 0 or at least the extent of the QP's block (of all its tangents)
+template <class T>
+int check_blocks(const ipmz_qp* s, const std::string& who, const QpBlocks<T>& b, const int (&dims)[3],
+                 const BlockRules& r, BlockFacts* facts) {
+  const int64_t n = dims[0];
+  const bool tangents = r.ntan >= 0, use_tq = tangents && !(r.one_tangent_ignores_tq && r.ntan <= 1);
+  *facts = BlockFacts{0, false};
+  for (int k = 0; k < DB_COUNT; ++k) {
+    if (!b.p[k]) continue;
+    const DataBlockInfo& info = DATA_BLOCKS[k];
+    const std::string name = who + ": " + info.name;
+    facts->supplied |= info.held;
+    const int64_t rows = dims[info.dim], ld = info.matrix ? b.ld[k] : rows, sq = b.sq[k], tq = b.tq[k];
+    if (info.matrix && ld < n) return fail(IPMZ_ERR_INVALID, name + ": row stride " + std::to_string(ld) + " < n");
+    if (ld < 0 || (sq < 0 && !(r.one_qp_ignores_sq && s->B == 1)) || (use_tq && tq < 0))
+      return fail(IPMZ_ERR_INVALID, name + ": negative stride");
+    const int64_t extent = info.matrix ? (rows - 1) * ld + n : ld;
+    if (use_tq && tq < extent)
+      return fail(IPMZ_ERR_INVALID, name + ": tangent stride " + std::to_string(tq) +
+                                        " is less than the block's extent " + std::to_string(extent));
+    const int64_t all = (use_tq ? (int64_t)(r.ntan - 1) * tq : 0) + extent;
+    if (s->B > 1 && sq != 0 && sq < all)
+      return fail(IPMZ_ERR_INVALID,
+                  name + ": QP stride " + std::to_string(sq) + " is neither 0 (" + r.zero_means + ") nor at least " +
+                      (tangents ? "the extent of the QP's tangents " : "the block's extent ") + std::to_string(all));
+    if (info.matrix && s->B > 1 && sq == 0) facts->shared_matrix = true;
+  }
+  return IPMZ_OK;
+}
 
 void drop_graph(ipmz_qp* s) {
   if (s->gexec) hipGraphExecDestroy(s->gexec);
@@ -1210,12 +1291,8 @@ int ipmz_qp_kkt_solve_bk(ipmz_qp* s, int nrhs, double* B, int64_t ldb) {
 static int newton_multi(ipmz_qp* s, const char* who, bool adjoint, int nrhs, const double* R, int64_t ldr, int64_t sR,
                         double* Dir, int64_t ldd, int64_t sD, double* alpha, int* info) {
   const std::string w(who);
-  if (s->normal) return fail(IPMZ_ERR_INVALID, w + ": the normal-equations reduction is enabled (augmented system only)");
-  if (s->mixed) return fail(IPMZ_ERR_INVALID, w + ": mixed precision is enabled (fp64 factors only)");
-  if (s->eqss)
-    return fail(IPMZ_ERR_INVALID, w + ": EqualityHandling::SlackedSlacks / NaiveSlacks keep a permuted, merged view of "
-                                      "the Newton order on the device; not served");
-  int rc = check_rhs_block(s, w, nrhs, adjoint ? "G" : "R", R, ldr, sR, s->state_len, "state_len");
+  int rc = refuse_unless_newton_order(s, w);
+  if (!rc) rc = check_rhs_block(s, w, nrhs, adjoint ? "G" : "R", R, ldr, sR, s->state_len, "state_len");
   if (!rc) rc = check_rhs_block(s, w, nrhs, adjoint ? "Out" : "Dir", Dir, ldd, sD, s->state_len, "state_len");
   if (rc) return rc;
   HIP_OK(hipSetDevice(s->ctx->device));
@@ -1507,49 +1584,16 @@ int ipmz_batch_set_factor_kernel(ipmz_qp* s, int kernel) {
 int ipmz_batch_load_device(ipmz_qp* s, const ipmz_qp_device_data* data) {
   const std::string who = "ipmz_batch_load_device";
   if (!s || !data) return fail(IPMZ_ERR_INVALID, who + ": null argument");
-  const int n = s->n, m = s->m_usr, p = s->p_usr;
-  // blocks of dimension 0 are ignored whatever they hold
-  QpIoData in{};
-  in.Q = data->Q, in.ldq = data->ldq, in.sQ = data->sQ;
-  in.c = data->c, in.sc = data->sc;
-  in.lx = data->l_x, in.slx = data->slx;
-  in.ux = data->u_x, in.sux = data->sux;
-  if (m) {
-    in.A = data->A, in.lda = data->lda, in.sA = data->sA;
-    in.lA = data->l_A, in.slA = data->slA;
-    in.uA = data->u_A, in.suA = data->suA;
-  }
-  if (p) {
-    in.C = data->C, in.ldc = data->ldc, in.sC = data->sC;
-    in.d = data->d, in.sd = data->sd;
-  }
-  struct Block {
-    const char* name;
-    const double* ptr;
-    int64_t rows, ld, sq;  // rows 0: a vector of n / m / p elements (ld: its length)
-    unsigned bit;
-  };
-  const Block blocks[9] = {{"Q", in.Q, n, in.ldq, in.sQ, HELD_Q},        {"A", in.A, m, in.lda, in.sA, HELD_A},
-                           {"C", in.C, p, in.ldc, in.sC, HELD_CEQ},      {"c", in.c, 0, n, in.sc, HELD_C},
-                           {"l_x", in.lx, 0, n, in.slx, HELD_LX},        {"u_x", in.ux, 0, n, in.sux, HELD_UX},
-                           {"l_A", in.lA, 0, m, in.slA, HELD_LA},        {"u_A", in.uA, 0, m, in.suA, HELD_UA},
-                           {"d", in.d, 0, p, in.sd, HELD_D}};
-  unsigned supplied = 0, absent = (m ? 0 : HELD_A | HELD_LA | HELD_UA) | (p ? 0 : HELD_CEQ | HELD_D);
-  for (const Block& b : blocks) {
-    if (!b.ptr) continue;
-    supplied |= b.bit;
-    if (b.rows && b.ld < n)
-      return fail(IPMZ_ERR_INVALID, who + ": " + b.name + ": row stride " + std::to_string(b.ld) + " < n");
-    if (b.ld < 0 || b.sq < 0) return fail(IPMZ_ERR_INVALID, who + ": " + b.name + ": negative stride");
-    const int64_t extent = b.rows ? (b.rows - 1) * b.ld + n : b.ld;
-    if (s->B > 1 && b.sq != 0 && b.sq < extent)
-      return fail(IPMZ_ERR_INVALID, who + ": " + b.name + ": QP stride " + std::to_string(b.sq) +
-                                        " is neither 0 (shared) nor at least the block's extent " + std::to_string(extent));
-  }
+  const int dims[3] = {s->n, s->m_usr, s->p_usr};
+  const QpBlocksIn in = data_blocks<const double>(*data, nullptr, dims);
+  BlockFacts facts;
+  if (int rc = check_blocks(s, who, in, dims, BlockRules{"shared", -1, false, false}, &facts)) return rc;
+  const unsigned supplied = facts.supplied;
+  const unsigned absent = (dims[1] ? 0 : HELD_A | HELD_LA | HELD_UA) | (dims[2] ? 0 : HELD_CEQ | HELD_D);
   if (const unsigned missing = HELD_ALL & ~(supplied | absent | s->held)) {
     std::string names;
-    for (const Block& b : blocks)
-      if (missing & b.bit) names += std::string(names.empty() ? "" : ", ") + b.name;
+    for (const DataBlockInfo& b : DATA_BLOCKS)
+      if (missing & b.held) names += std::string(names.empty() ? "" : ", ") + b.name;
     return fail(IPMZ_ERR_STATE, who + ": not supplied and never loaded or generated: " + names);
   }
   HIP_OK(hipSetDevice(s->ctx->device));
@@ -1590,64 +1634,21 @@ int ipmz_batch_copy_state(ipmz_qp* s, int which, double* dst, int64_t ld) {
 int ipmz_batch_data_vjp(ipmz_qp* s, const double* W, int64_t sW, const ipmz_qp_device_grad* grad) {
   const std::string who = "ipmz_batch_data_vjp";
   if (!s || !W || !grad) return fail(IPMZ_ERR_INVALID, who + ": null argument");
-  if (s->normal) return fail(IPMZ_ERR_INVALID, who + ": the normal-equations reduction is enabled (augmented system only)");
-  if (s->mixed) return fail(IPMZ_ERR_INVALID, who + ": mixed precision is enabled (fp64 factors only)");
-  if (s->eqss)
-    return fail(IPMZ_ERR_INVALID, who + ": EqualityHandling::SlackedSlacks / NaiveSlacks keep a permuted, merged view of "
-                                        "the Newton order on the device; not served");
-  if (!s->loaded) return fail(IPMZ_ERR_STATE, who + ": load (and initialize) the QP first");
+  int rc = refuse_unless_newton_order(s, who);
+  if (rc) return rc;
   if (s->B > 1 && sW < s->state_len)
     return fail(IPMZ_ERR_INVALID, who + ": W: QP stride " + std::to_string(sW) + " < state_len");
-  const int n = s->n, m = s->m, p = s->p;
-  // blocks of dimension 0 are ignored whatever they hold
-  QpGradOut o{};
-  o.Q = grad->Q, o.ldq = grad->ldq, o.sQ = grad->sQ;
-  o.c = grad->c, o.sc = grad->sc;
-  o.lx = grad->l_x, o.slx = grad->slx;
-  o.ux = grad->u_x, o.sux = grad->sux;
-  if (m) {
-    o.A = grad->A, o.lda = grad->lda, o.sA = grad->sA;
-    o.lA = grad->l_A, o.slA = grad->slA;
-    o.uA = grad->u_A, o.suA = grad->suA;
-  }
-  if (p) {
-    o.C = grad->C, o.ldc = grad->ldc, o.sC = grad->sC;
-    o.d = grad->d, o.sd = grad->sd;
-  }
-  struct Block {
-    const char* name;
-    const double* ptr;
-    int64_t rows, ld, sq;  // rows 0: a vector of n / m / p elements (ld: its length)
-  };
-  const Block blocks[9] = {{"Q", o.Q, n, o.ldq, o.sQ}, {"A", o.A, m, o.lda, o.sA},    {"C", o.C, p, o.ldc, o.sC},
-                           {"c", o.c, 0, n, o.sc},     {"l_x", o.lx, 0, n, o.slx},    {"u_x", o.ux, 0, n, o.sux},
-                           {"l_A", o.lA, 0, m, o.slA}, {"u_A", o.uA, 0, m, o.suA},    {"d", o.d, 0, p, o.sd}};
-  bool shared_matrix = false;
-  for (const Block& b : blocks) {
-    if (!b.ptr) continue;
-    if (b.rows && b.ld < n)
-      return fail(IPMZ_ERR_INVALID, who + ": " + b.name + ": row stride " + std::to_string(b.ld) + " < n");
-    if (b.ld < 0 || b.sq < 0) return fail(IPMZ_ERR_INVALID, who + ": " + b.name + ": negative stride");
-    const int64_t extent = b.rows ? (b.rows - 1) * b.ld + n : b.ld;
-    if (s->B > 1 && b.sq != 0 && b.sq < extent)
-      return fail(IPMZ_ERR_INVALID, who + ": " + b.name + ": QP stride " + std::to_string(b.sq) +
-                                        " is neither 0 (summed over the batch) nor at least the block's extent " +
-                                        std::to_string(extent));
-    if (b.rows && s->B > 1 && b.sq == 0) shared_matrix = true;
-  }
+  const int dims[3] = {s->n, s->m, s->p};
+  const QpBlocksOut o = data_blocks<double>(reinterpret_cast<const ipmz_qp_device_data&>(*grad), nullptr, dims);
+  BlockFacts facts;
+  if ((rc = check_blocks(s, who, o, dims, BlockRules{"summed over the batch", -1, false, false}, &facts))) return rc;
   HIP_OK(hipSetDevice(s->ctx->device));
-  int rc = wait_pending_step(s);  // (a forked step still in flight writes the iterate this call reads)
-  if (rc) return rc;
-  if (shared_matrix) {
+  if ((rc = wait_pending_step(s))) return rc;  // (a forked step still in flight writes the iterate this call reads)
+  if (facts.shared_matrix) {  // once per solver: the size follows from the shape alone
     const size_t need = (size_t)vjp_ws(nullptr, qp_grad_part_elems(s->qb)).total;
-    if (need > s->vjpws.bytes) {  // once per solver: the size follows from the shape alone
-      hipStreamCaptureStatus cs = hipStreamCaptureStatusNone;
-      HIP_OK(hipStreamIsCapturing(s->ctx->stream, &cs));
-      if (cs != hipStreamCaptureStatusNone)
-        return fail(IPMZ_ERR_STATE, who + ": the context's stream is capturing a hipGraph and the shared blocks' "
-                                          "workspace is not allocated yet (make one call outside the capture first)");
-      if ((rc = grow(s, s->vjpws, need))) return rc;
-    }
+    if ((rc = grow_unless_capturing(s, s->vjpws, need, who, "the shared blocks' workspace is not allocated yet (make "
+                                                            "one call outside the capture first)")))
+      return rc;
   }
   HIP_OK(qp_data_vjp(s->qb, W, s->B > 1 ? sW : 0, o, vjp_ws(s->vjpws.p, 0).part, s->ctx->stream));
   return IPMZ_OK;
@@ -1661,78 +1662,30 @@ int ipmz_batch_data_vjp(ipmz_qp* s, const double* W, int64_t sW, const ipmz_qp_d
 int ipmz_batch_data_jvp(ipmz_qp* s, int ntan, const ipmz_qp_device_tangent* tan, double* R, int64_t ldr, int64_t sR) {
   const std::string who = "ipmz_batch_data_jvp";
   if (!s || !tan || !R) return fail(IPMZ_ERR_INVALID, who + ": null argument");
-  if (s->normal) return fail(IPMZ_ERR_INVALID, who + ": the normal-equations reduction is enabled (augmented system only)");
-  if (s->mixed) return fail(IPMZ_ERR_INVALID, who + ": mixed precision is enabled (fp64 factors only)");
-  if (s->eqss)
-    return fail(IPMZ_ERR_INVALID, who + ": EqualityHandling::SlackedSlacks / NaiveSlacks keep a permuted, merged view of "
-                                        "the Newton order on the device; not served");
-  if (!s->loaded) return fail(IPMZ_ERR_STATE, who + ": load (and initialize) the QP first");
+  int rc = refuse_unless_newton_order(s, who);
+  if (rc) return rc;
   if (ntan < 0) return fail(IPMZ_ERR_INVALID, who + ": ntan < 0");
   if (ldr < s->state_len || (ldr & 1))
     return fail(IPMZ_ERR_INVALID, who + ": R: row stride " + std::to_string(ldr) + " must be >= state_len and even");
   if (s->B > 1 && (sR < (int64_t)ntan * ldr || (sR & 1)))
     return fail(IPMZ_ERR_INVALID, who + ": R: QP stride " + std::to_string(sR) + " must be >= ntan * row stride and even");
   if ((uintptr_t)R & 15) return fail(IPMZ_ERR_INVALID, who + ": R must be 16-byte aligned");
-  const int n = s->n, m = s->m, p = s->p;
-  const ipmz_qp_device_data& d = tan->d;
-  // blocks of dimension 0 are ignored whatever they hold
-  QpTanIn in{};
-  in.Q = d.Q, in.ldq = d.ldq, in.sQ = d.sQ, in.tQ = tan->tQ;
-  in.c = d.c, in.sc = d.sc, in.tc = tan->tc;
-  in.lx = d.l_x, in.slx = d.slx, in.tlx = tan->tlx;
-  in.ux = d.u_x, in.sux = d.sux, in.tux = tan->tux;
-  if (m) {
-    in.A = d.A, in.lda = d.lda, in.sA = d.sA, in.tA = tan->tA;
-    in.lA = d.l_A, in.slA = d.slA, in.tlA = tan->tlA;
-    in.uA = d.u_A, in.suA = d.suA, in.tuA = tan->tuA;
-  }
-  if (p) {
-    in.C = d.C, in.ldc = d.ldc, in.sC = d.sC, in.tC = tan->tC;
-    in.d = d.d, in.sd = d.sd, in.td = tan->td;
-  }
-  struct Block {
-    const char* name;
-    const double* ptr;
-    int64_t rows, ld, sq, tq;  // rows 0: a vector of n / m / p elements (ld: its length)
-  };
-  const Block blocks[9] = {{"Q", in.Q, n, in.ldq, in.sQ, in.tQ},      {"A", in.A, m, in.lda, in.sA, in.tA},
-                           {"C", in.C, p, in.ldc, in.sC, in.tC},      {"c", in.c, 0, n, in.sc, in.tc},
-                           {"l_x", in.lx, 0, n, in.slx, in.tlx},      {"u_x", in.ux, 0, n, in.sux, in.tux},
-                           {"l_A", in.lA, 0, m, in.slA, in.tlA},      {"u_A", in.uA, 0, m, in.suA, in.tuA},
-                           {"d", in.d, 0, p, in.sd, in.td}};
-  for (const Block& b : blocks) {
-    if (!b.ptr) continue;
-    if (b.rows && b.ld < n)
-      return fail(IPMZ_ERR_INVALID, who + ": " + b.name + ": row stride " + std::to_string(b.ld) + " < n");
-    // (a solver of one QP ignores the QP strides, a call with one tangent the tangent strides)
-    if (b.ld < 0 || (s->B > 1 && b.sq < 0) || (ntan > 1 && b.tq < 0))
-      return fail(IPMZ_ERR_INVALID, who + ": " + b.name + ": negative stride");
-    const int64_t extent = b.rows ? (b.rows - 1) * b.ld + n : b.ld;
-    if (ntan > 1 && b.tq < extent)
-      return fail(IPMZ_ERR_INVALID, who + ": " + b.name + ": tangent stride " + std::to_string(b.tq) +
-                                        " is less than the block's extent " + std::to_string(extent));
-    const int64_t all = (ntan > 1 ? (int64_t)(ntan - 1) * b.tq : 0) + extent;
-    if (s->B > 1 && b.sq != 0 && b.sq < all)
-      return fail(IPMZ_ERR_INVALID, who + ": " + b.name + ": QP stride " + std::to_string(b.sq) +
-                                        " is neither 0 (shared) nor at least the extent of the QP's tangents " +
-                                        std::to_string(all));
-  }
+  const int dims[3] = {s->n, s->m, s->p};
+  const int64_t tq[DB_COUNT] = {tan->tQ, tan->tA, tan->tC, tan->tc, tan->tlx, tan->tux, tan->tlA, tan->tuA, tan->td};
+  QpBlocksIn in = data_blocks<const double>(tan->d, tq, dims);
+  BlockFacts facts;
+  // (a solver of one QP ignores the QP strides, a call with one tangent the tangent strides)
+  if ((rc = check_blocks(s, who, in, dims, BlockRules{"shared", ntan, true, true}, &facts))) return rc;
   if (ntan == 0) return IPMZ_OK;
-  if (s->B == 1) in.sQ = in.sA = in.sC = in.sc = in.slx = in.sux = in.slA = in.suA = in.sd = 0;
+  if (s->B == 1)
+    for (int64_t& sq : in.sq) sq = 0;
   HIP_OK(hipSetDevice(s->ctx->device));
-  int rc = wait_pending_step(s);  // (a forked step still in flight writes the iterate this call reads)
-  if (rc) return rc;
+  if ((rc = wait_pending_step(s))) return rc;  // (a forked step still in flight writes the iterate this call reads)
   const int64_t elems = (int64_t)s->B * ntan * qp_jvp_plan(s->qb, in).seg;
-  const size_t need = (size_t)jvp_ws(nullptr, elems).total;
-  if (need > s->jvpws.bytes) {
-    hipStreamCaptureStatus cs = hipStreamCaptureStatusNone;
-    HIP_OK(hipStreamIsCapturing(s->ctx->stream, &cs));
-    if (cs != hipStreamCaptureStatusNone)
-      return fail(IPMZ_ERR_STATE, who + ": the context's stream is capturing a hipGraph and the products' workspace is "
-                                        "too small for this call (make one such call outside the capture first)");
-    // (launches of earlier calls may still read the old buffer: hipFree waits for the device)
-    if ((rc = grow(s, s->jvpws, need))) return rc;
-  }
+  if ((rc = grow_unless_capturing(s, s->jvpws, (size_t)jvp_ws(nullptr, elems).total, who,
+                                  "the products' workspace is too small for this call (make one such call outside "
+                                  "the capture first)")))
+    return rc;
   HIP_OK(qp_data_jvp(s->qb, ntan, in, R, ldr, s->B > 1 ? sR : 0, jvp_ws(s->jvpws.p, 0).prod, s->ctx->stream));
   return IPMZ_OK;
 }

@@ -109,65 +109,56 @@ class _QPDeviceTangent(ctypes.Structure):
 
 
 # load_tensors' names -> (ipmz_qp_device_data pointer, row stride or None, QP stride, rows or None, columns);
-# rows / columns name the solver's dimensions
+# rows / columns name the solver's dimensions.  The order is csrc/kernels.h DATA_BLOCKS'; ipmz_qp_device_tangent's
+# tangent stride of block X is its QP stride's name sX with a t (_set_block)
 _BLOCKS = (("Q", "Q", "ldq", "sQ", "n", "n"), ("A_ineq", "A", "lda", "sA", "m", "n"), ("A_eq", "C", "ldc", "sC", "p", "n"),
            ("c", "c", None, "sc", None, "n"), ("l_x", "l_x", None, "slx", None, "n"), ("u_x", "u_x", None, "sux", None, "n"),
            ("l_A_ineq", "l_A", None, "slA", None, "m"), ("u_A_ineq", "u_A", None, "suA", None, "m"),
            ("b_eq", "d", None, "sd", None, "p"))
 
 
-def _tensor_block(t, batch, rows, cols):
+def _tensor_block(t, batch, rows, cols, tangent=False):
     """A torch tensor as one block of ipmz_qp_device_data: (data_ptr, row stride, QP stride), strides in elements.
 
     rows is None for a vector block -- t of shape (batch, cols), or (cols,) shared by every QP -- else the block is
     a matrix: (batch, rows, cols), or (rows, cols) shared.  A shared block, and one expanded along the batch
     dimension (batch stride 0), has QP stride 0.  Nothing is copied: the strides go to the kernel as they are.
+    tangent: one block of ipmz_qp_device_tangent -- the same rules with a tangent dimension after the batch's,
+    (batch, ntan, ...) per QP or (ntan, ...) shared -- as (data_ptr, row stride, QP stride, tangent stride, ntan).
     ValueError for a dtype other than float64, another shape, or an inner stride other than 1."""
     import torch
-    name = "matrix" if rows is not None else "vector"
+    name, what = "matrix" if rows is not None else "vector", "tangent" if tangent else "block"
     if not isinstance(t, torch.Tensor) or t.dtype != torch.float64:
-        raise ValueError(f"{name} block: a float64 torch tensor is needed, got {getattr(t, 'dtype', type(t))}")
+        raise ValueError(f"{name} {what}: a float64 torch tensor is needed, got {getattr(t, 'dtype', type(t))}")
     inner = (cols,) if rows is None else (rows, cols)
     shape = tuple(t.shape)
-    if shape == (batch,) + inner:
-        sq = t.stride(0) if batch > 1 else 0
-        strides = t.stride()[1:]
-    elif shape == inner:
-        sq = 0
-        strides = t.stride()
-    else:
-        raise ValueError(f"{name} block: shape {shape} is neither {(batch,) + inner} nor {inner}")
+    lead = len(shape) - len(inner)  # the dimensions before the block's: [batch][ntan]
+    per_qp = lead == tangent + 1
+    if not (per_qp or lead == tangent) or shape[lead:] != inner or (per_qp and shape[0] != batch):
+        tan = ("ntan",) if tangent else ()
+        raise ValueError(f"{name} {what}: shape {shape} is neither {(batch,) + tan + inner} nor {tan + inner}")
+    strides = t.stride()
+    sq = strides[0] if per_qp and batch > 1 else 0
     if cols > 1 and strides[-1] != 1:
-        raise ValueError(f"{name} block: inner stride {strides[-1]}, must be 1 (elements of a row adjacent)")
+        raise ValueError(f"{name} {what}: inner stride {strides[-1]}, must be 1 (elements of a row adjacent)")
     # (the stride of a dimension of size 1 means nothing: a single row is given the row length)
-    ld = 0 if rows is None else (strides[0] if rows > 1 else max(strides[0], cols))
-    return t.data_ptr(), ld, sq
+    ld = 0 if rows is None else (strides[lead] if rows > 1 else max(strides[lead], cols))
+    if not tangent:
+        return t.data_ptr(), ld, sq
+    ntan = shape[lead - 1]
+    return t.data_ptr(), ld, sq, (strides[lead - 1] if ntan > 1 else 0), ntan
 
 
-def _tangent_block(t, batch, rows, cols):
-    """A torch tensor as one block of ipmz_qp_device_tangent: (data_ptr, row stride, QP stride, tangent stride,
-    ntan), strides in elements.  _tensor_block's rules with a tangent dimension after the batch's: matrices
-    (batch, ntan, rows, cols) per QP or (ntan, rows, cols) shared by every QP, vectors (batch, ntan, cols) or
-    (ntan, cols).  Nothing is copied."""
-    import torch
-    name = "matrix" if rows is not None else "vector"
-    if not isinstance(t, torch.Tensor) or t.dtype != torch.float64:
-        raise ValueError(f"{name} tangent: a float64 torch tensor is needed, got {getattr(t, 'dtype', type(t))}")
-    inner = (cols,) if rows is None else (rows, cols)
-    shape = tuple(t.shape)
-    k = len(inner)
-    if len(shape) == k + 2 and shape[0] == batch and shape[2:] == inner:
-        sq = t.stride(0) if batch > 1 else 0
-        ntan, tq, strides = shape[1], t.stride(1), t.stride()[2:]
-    elif len(shape) == k + 1 and shape[1:] == inner:
-        sq = 0
-        ntan, tq, strides = shape[0], t.stride(0), t.stride()[1:]
-    else:
-        raise ValueError(f"{name} tangent: shape {shape} is neither {(batch, 'ntan') + inner} nor {('ntan',) + inner}")
-    if cols > 1 and strides[-1] != 1:
-        raise ValueError(f"{name} tangent: inner stride {strides[-1]}, must be 1 (elements of a row adjacent)")
-    ld = 0 if rows is None else (strides[0] if rows > 1 else max(strides[0], cols))
-    return t.data_ptr(), ld, sq, (tq if ntan > 1 else 0), ntan
+def _set_block(d, fields, blk, tan=None):
+    """One block -- fields: its row of _BLOCKS, blk: _tensor_block's tuple -- into the ipmz_qp_device_data d, and
+    its tangent stride into tan: block X's tangent stride tX is its QP stride sX renamed."""
+    _, ptr, ld, sq, _, _ = fields
+    setattr(d, ptr, blk[0])
+    if ld:
+        setattr(d, ld, blk[1])
+    setattr(d, sq, blk[2])
+    if tan is not None:
+        setattr(tan, "t" + sq[1:], blk[3])
 
 
 def _load():
@@ -658,35 +649,20 @@ class Optimizer:
         self._bump()
         import torch
         batch = lib.ipmz_batch_size(self.h)
-        n, m, p = self.n, self.m, self.p
+        dims = dict(n=self.n, m=self.m, p=self.p)
+        given = dict(Q=Q, c=c, l_x=l_x, u_x=u_x, A_ineq=A_ineq, l_A_ineq=l_A_ineq, u_A_ineq=u_A_ineq, A_eq=A_eq, b_eq=b_eq)
         d = _QPDeviceData()
-        keep = []  # the tensors stay referenced until the call returns
-
-        def put(t, name, rows, cols, ptr, ld, sq):
-            if t is None or cols == 0 or rows == 0:
-                return
+        for fields in _BLOCKS:  # (`given` keeps the tensors referenced until the call returns)
+            name, _, _, _, rows, cols = fields
+            t, r, k = given[name], (None if rows is None else dims[rows]), dims[cols]
+            if t is None or k == 0 or r == 0:
+                continue
             if not isinstance(t, torch.Tensor):
                 raise ValueError(f"{name}: a torch tensor is needed")
             self._on_device(t, name)
-            blk = _tensor_block(t, batch, rows, cols)
-            keep.append(t)
-            setattr(d, ptr, blk[0])
-            if ld:
-                setattr(d, ld, blk[1])
-            setattr(d, sq, blk[2])
-
-        put(Q, "Q", n, n, "Q", "ldq", "sQ")
-        put(A_ineq, "A_ineq", m, n, "A", "lda", "sA")
-        put(A_eq, "A_eq", p, n, "C", "ldc", "sC")
-        put(c, "c", None, n, "c", None, "sc")
-        put(l_x, "l_x", None, n, "l_x", None, "slx")
-        put(u_x, "u_x", None, n, "u_x", None, "sux")
-        put(l_A_ineq, "l_A_ineq", None, m, "l_A", None, "slA")
-        put(u_A_ineq, "u_A_ineq", None, m, "u_A", None, "suA")
-        put(b_eq, "b_eq", None, p, "d", None, "sd")
+            _set_block(d, fields, _tensor_block(t, batch, r, k))
         self._order_torch_stream(torch)
         _check(lib.ipmz_batch_load_device(self.h, ctypes.byref(d)), "ipmz_batch_load_device")
-        del keep
 
     def state_tensor(self, which=0, out=None):
         """The state `which` (0 iterate, 1 affine direction, 2 direction, 3 residuals) of every QP as a
@@ -732,18 +708,15 @@ class Optimizer:
         dims = dict(n=self.n, m=self.m, p=self.p)
         g = _QPDeviceGrad()
         out = {}
-        for name, ptr, ld, sq, rows, cols in _BLOCKS:
+        for fields in _BLOCKS:
+            name, _, _, _, rows, cols = fields
             r, c = (None if rows is None else dims[rows]), dims[cols]
             if c == 0 or r == 0 or (only is not None and name not in only):
                 continue
             inner = (c,) if r is None else (r, c)
             t = torch.empty(inner if name in shared else (batch,) + inner, dtype=torch.float64, device=W.device)
-            blk = _tensor_block(t, batch, r, c)
-            setattr(g, ptr, blk[0])
-            if ld:
-                setattr(g, ld, blk[1])
             # (a batch of one has no shared blocks: the library ignores the QP stride there)
-            setattr(g, sq, 0 if name in shared else t.stride(0))
+            _set_block(g, fields, _tensor_block(t, batch, r, c)[:2] + (0 if name in shared else t.stride(0),))
             out[name] = t
         self._order_torch_stream(torch)
         sW = W.stride(0) if batch > 1 else W.shape[1]
@@ -775,9 +748,9 @@ class Optimizer:
                 raise ValueError(f"unknown block {k!r}: one of {names}")
         dims = dict(n=self.n, m=self.m, p=self.p)
         tan = _QPDeviceTangent()
-        tstride = dict(Q="tQ", A="tA", C="tC", c="tc", l_x="tlx", u_x="tux", l_A="tlA", u_A="tuA", d="td")
-        ntan, keep = None, []
-        for name, ptr, ld, sq, rows, cols in _BLOCKS:
+        ntan = None
+        for fields in _BLOCKS:
+            name, _, _, _, rows, cols = fields
             t = tangents.get(name)
             if t is None:
                 continue
@@ -785,18 +758,12 @@ class Optimizer:
             if not isinstance(t, torch.Tensor):
                 raise ValueError(f"{name}: a torch tensor is needed")
             self._on_device(t, name)
-            blk = _tangent_block(t, batch, r, c)
+            blk = _tensor_block(t, batch, r, c, tangent=True)
             if ntan is not None and blk[4] != ntan:
                 raise ValueError(f"{name}: {blk[4]} tangents, the blocks before it have {ntan}")
             ntan = blk[4]
-            if c == 0 or r == 0:
-                continue
-            keep.append(t)
-            setattr(tan.d, ptr, blk[0])
-            if ld:
-                setattr(tan.d, ld, blk[1])
-            setattr(tan.d, sq, blk[2])
-            setattr(tan, tstride[ptr], blk[3])
+            if c != 0 and r != 0:
+                _set_block(tan.d, fields, blk, tan)
         if ntan is None:
             raise ValueError("data_jvp_tensors: no tangent given (ntan is taken from the tensors)")
         ldr = L + (L & 1)
@@ -815,7 +782,6 @@ class Optimizer:
                "ipmz_batch_data_jvp")
         if not self.ctx.on_stream(torch.cuda.current_stream(self.ctx.device).cuda_stream):
             self.ctx.sync()
-        del keep
         return out
 
     def solution_tensor(self):

@@ -125,13 +125,15 @@ def test_reference_form_is_the_default_reference_bitwise(c, name, eq_none):
 
 
 def test_loop_cases_reach_the_loops():
-    """The batches of dc.LOOP_BATCHES against grad_grid's limits as the sources state them."""
+    """The batches of dc.LOOP_BATCHES against the limits of grad.hip's grids (block_grid, data_terms.h) as the
+    sources state them."""
     import os
     import re
-    here = os.path.dirname(os.path.abspath(__file__))
-    txt = open(os.path.join(here, "..", "ipm-zoo_amd", "csrc", "grad.hip")).read()
-    gx, gy = re.search(r"gx > (\d+) \? \1 : gx;\s*int64_t gy = (\d+) / gx;", txt).groups()
+    csrc = os.path.join(os.path.dirname(os.path.abspath(__file__)), "..", "ipm-zoo_amd", "csrc")
+    txt, grid = open(os.path.join(csrc, "grad.hip")).read(), open(os.path.join(csrc, "data_terms.h")).read()
+    gx, gy = re.search(r"gx > (\d+) \? \1 : gx;\s*int64_t gy = (\d+) / gx;", grid).groups()
     assert (int(gx), int(gy)) == (dc.SUM_GX, dc.GRID_Y)
+    assert "block_grid(" in txt and re.search(r"constexpr int GRID_NT = 256;", grid) and "NT == GRID_NT" in txt
     assert re.search(r"constexpr int NT = 256;", txt) and re.search(r"constexpr int VS = 64,", txt)
     n = dc.LOOP_SHAPE[0]
     assert max(dc.LOOP_BATCHES) > dc.GRID_Y // -(-n // 4) and max(dc.LOOP_BATCHES) > dc.GRID_Y
@@ -157,3 +159,27 @@ def test_chunk_size_matches_the_sources():
     txt = open(os.path.join(here, "..", "ipm-zoo_amd", "csrc", "kernels.h")).read()
     assert int(re.search(r"#define IPMZ_VJP_KCHUNK (\d+)", txt).group(1)) == dc.KCHUNK
     assert {dc.KCHUNK - 1, dc.KCHUNK, dc.KCHUNK + 1} <= {c[3] for c in dc.BATCH_CASES}
+
+
+def test_the_data_blocks_are_described_once():
+    """The nine blocks, the dual A^T multiplies and the grid of the data calls each have one statement: the spellings
+    of the copies that csrc/kernels.h DATA_BLOCKS and csrc/data_terms.h replaced occur nowhere."""
+    import glob
+    import os
+    import re
+    root = os.path.join(os.path.dirname(os.path.abspath(__file__)), "..", "ipm-zoo_amd")
+    src = {os.path.basename(f): open(f).read() for f in glob.glob(os.path.join(root, "csrc", "*"))}
+    everything = "\n".join(src.values())
+    for old in ("QpIoData", "QpGradOut", "QpTanIn", "grad_grid", "io_grid", "jvp_dual", "grad_vec_ok", "IPMZ_GRAD_",
+                "IPMZ_JVP_MATRIX", "IPMZ_JVP_SHARED"):
+        assert old not in everything, old
+    table = re.findall(r"DATA_BLOCKS\[DB_COUNT\] = \{(.*?)\};", src["kernels.h"], re.S)
+    assert len(table) == 1 and everything.count("DATA_BLOCKS[DB_COUNT] = {") == 1
+    rows = re.findall(r'\{"(\w+)", (true|false), ([012]), HELD_\w+\}', table[0])
+    assert [r[0] for r in rows] == ["Q", "A", "C", "c", "l_x", "u_x", "l_A", "u_A", "d"]
+    assert [r[1:] for r in rows] == [("true", "0"), ("true", "1"), ("true", "2"), ("false", "0"), ("false", "0"),
+                                     ("false", "0"), ("false", "1"), ("false", "1"), ("false", "2")]
+    assert "blocks[9]" not in src["qp.cpp"]
+    assert len(re.findall(r"double a_dual\(", everything)) == 1
+    assert everything.count("q.v[LH][i] + (-q.v[LG][i])") == 1
+    assert "_tangent_block" not in open(os.path.join(root, "ipmz_amd", "__init__.py")).read()
