@@ -70,6 +70,8 @@
  *                                  with respect to the problem data in the strided blocks
  *                                  ipmz_batch_load_device reads (per QP, or summed over the
  *                                  batch for shared blocks)
+ *   ipmz_batch_data_vjp_multi   <- the same for a block of cotangent rows per QP (the adjoint
+ *                                  pair's nrhs rows): reverse-mode Jacobians in one call
  *   ipmz_batch_data_jvp         <- no reference counterpart: the forward-mode counterpart,
  *                                  tangents of the data (ntan per QP, or one set shared by
  *                                  the batch) to the residual rows d r_v / d data applied to
@@ -905,6 +907,58 @@ typedef struct ipmz_qp_device_grad {
   int64_t sd;
 } ipmz_qp_device_grad;
 int ipmz_batch_data_vjp(ipmz_qp* qp, const double* W, int64_t sW, const ipmz_qp_device_grad* grad);
+
+/* The call above for a block of ncot cotangent rows per QP: the last link of
+ * a reverse-mode Jacobian, ipmz_*_newton_adjoint_multi's nrhs rows contracted
+ * with d r / d data in one call instead of a host loop over the rows.
+ *
+ * W (device): row r of QP q at W + q * sW + r * ldw, ipmz_qp_state_len doubles
+ * in the layout of IPMZ_STATE_RES -- the adjoint pair's Out with ldw = ldo and
+ * sW = sO.  ldw >= state_len; on batches sW >= (ncot - 1) * ldw + state_len.  A
+ * solver of one QP ignores sW.  No alignment rule for W.
+ *
+ * ipmz_qp_device_grad_multi is ipmz_qp_device_grad (blocks, row strides, QP
+ * strides) plus a cotangent-row stride per block: row r of QP q of block X
+ * starts at X + q * sX + r * tX.  The rules are ipmz_qp_device_tangent's with
+ * writable blocks: strides in elements; a NULL block is not wanted; blocks of
+ * dimension 0 are ignored whatever they hold; a row stride is at least n; no
+ * stride is negative; with ncot > 1 a cotangent-row stride is at least the
+ * block's extent and a non-zero QP stride at least (ncot - 1) * tX + extent (a
+ * call with one row does not look at tX); no alignment rule (16-byte stores
+ * where the pointer and all three strides allow them, element by element
+ * otherwise, with equal bits).  Nothing outside the blocks (row padding, the
+ * space between rows and QPs) is written.  QP stride 0 (batches): ncot blocks,
+ * block r receiving the sum over all QPs of row r's gradient.
+ *
+ * Row contract: every row's blocks are bitwise what ipmz_batch_data_vjp writes
+ * for that row alone (W + r * ldw, sW), per QP and shared; the summation order
+ * of a shared block is the one stated above -- chunks of 64 QPs, groups of
+ * four in QP order, chunks in chunk order, the 64 ranges for vectors -- fixed
+ * by the batch size alone, whatever ncot.  No atomics, no cross-workgroup
+ * waiting.  In a shared matrix block x and the iterate's dual do not depend on
+ * the row: a wave keeps them in registers over a group of 4 rows.
+ *
+ * Workspace: the shared matrix blocks' partials pass through the workspace of
+ * ipmz_batch_data_vjp in slabs of 16 rows, one slab after the other on the
+ * stream: ceil(batch / 64) * min(ncot, 16) * max(n, m, p) * n doubles, grown
+ * for the largest need seen, never linear in ncot.
+ *
+ * ncot == 0 is a no-op.  Asynchronous on the context's stream, no synchronize;
+ * the iterate, the step's slots, the scalars, the kept KKT matrix, a captured
+ * step graph and all later steps are unchanged, bitwise.
+ *
+ * Served and refused like ipmz_batch_data_vjp: IPMZ_ERR_INVALID for a null qp,
+ * W or grad, ncot < 0, bad strides, IPMZ_EQ_SLACKED_SLACKS /
+ * IPMZ_EQ_NAIVE_SLACKS, an enabled normal-equations reduction or mixed
+ * precision; IPMZ_ERR_STATE before a load, between a load and
+ * ipmz_batch_initialize, and when the workspace would have to grow while the
+ * context's stream is capturing; IPMZ_ERR_NOMEM when it cannot be had. */
+typedef struct ipmz_qp_device_grad_multi {
+  ipmz_qp_device_grad g;                           /* blocks, row strides, QP strides */
+  int64_t tQ, tA, tC, tc, tlx, tux, tlA, tuA, td;  /* cotangent-row strides, in elements */
+} ipmz_qp_device_grad_multi;
+int ipmz_batch_data_vjp_multi(ipmz_qp* qp, int ncot, const double* W, int64_t ldw, int64_t sW,
+                              const ipmz_qp_device_grad_multi* grad);
 
 /* The first link of a forward pass through a solved QP: tangents of the problem
  * data in, the tangents of the residual vectors out.  At a fixed iterate and a

@@ -181,8 +181,9 @@ inline BkBatchWs bk_batch_ws(char* base, int N, int batch) {
   return w;
 }
 
-// ipmz_batch_data_vjp's shared matrix blocks: the chunks' partial products
-// (grad.hip; elems = qp_grad_part_elems of the batch)
+// ipmz_batch_data_vjp's and ipmz_batch_data_vjp_multi's shared matrix blocks:
+// the chunks' partial products of one slab of cotangent rows (grad.hip; elems =
+// qp_grad_part_elems of the batch and the call's row count)
 struct VjpWs {
   double* part = nullptr;
   int64_t total = 0;

@@ -615,14 +615,21 @@ hipError_t qp_gather_state(const QPBatch& qb, int which, double* dst, int64_t ld
 // QPs per chunk of the shared matrix blocks' sum over the batch: every chunk's
 // partial product is one tile set of the workspace, summed in chunk order
 #define IPMZ_VJP_KCHUNK 64
-// elements of that workspace: ceil(B / IPMZ_VJP_KCHUNK) x max(n, m, p) x n (one matrix block at a time)
-int64_t qp_grad_part_elems(const QPBatch& qb);
-// (d r / d data)^T w of every QP, w = the row at W + z sW in the layout of
-// IPMZ_STATE_RES, into the blocks of o; part: the workspace above, read and
-// written only when a matrix block is shared (may be null otherwise).
-// Stream-ordered launches, no atomics; reads the iterate and W only
-hipError_t qp_data_vjp(const QPBatch& qb, const double* W, int64_t sW, const QpBlocksOut& o, double* part,
-                       hipStream_t st);
+// cotangent rows per QP whose partials the workspace holds at a time (ipmz_batch_data_vjp_multi): the rows of a call
+// pass through it in slabs of this many, one slab after the other on the stream
+#define IPMZ_VJP_SLAB 16
+// elements of that workspace for a call with ncot rows per QP: ceil(B / IPMZ_VJP_KCHUNK) x min(ncot, IPMZ_VJP_SLAB)
+// x max(n, m, p) x n (one matrix block and one slab at a time)
+int64_t qp_grad_part_elems(const QPBatch& qb, int ncot = 1);
+// (d r / d data)^T w of every QP and each of its ncot cotangent rows, w = the
+// row at W + z sW + r ldw in the layout of IPMZ_STATE_RES, into the blocks of
+// o (row r of QP z of block k at p[k] + z sq[k] + r tq[k]; one row: ldw and tq
+// are not looked at); part: the workspace above, read and written only when a
+// matrix block is shared (may be null otherwise).  Every row's result has the
+// bits of a call with that row alone.  Stream-ordered launches, no atomics;
+// reads the iterate and W only
+hipError_t qp_data_vjp(const QPBatch& qb, int ncot, const double* W, int64_t ldw, int64_t sW, const QpBlocksOut& o,
+                       double* part, hipStream_t st);
 
 // jvp.hip --------------------------------------------------------------------
 // gridDim.y of the launches that loop over the rows (q, t) of R

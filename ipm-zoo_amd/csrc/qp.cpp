@@ -56,7 +56,8 @@ struct ipmz_qp {
   // ipmz_*_newton_solve_multi / ipmz_*_newton_adjoint_multi: the reduced right-hand sides, B x nrhs x round_up(N, 2)
   // doubles, for the largest nrhs seen
   GrowBuf nmws;
-  // ipmz_batch_data_vjp: the shared matrix blocks' partial products (vjp_ws), when one is first asked for
+  // ipmz_batch_data_vjp(_multi): the shared matrix blocks' partial products (vjp_ws), when one is first asked for,
+  // grown for the largest slab of cotangent rows seen
   GrowBuf vjpws;
   // ipmz_batch_data_jvp: the matrix products of every row (jvp_ws), for the largest need seen
   GrowBuf jvpws;
@@ -1650,7 +1651,39 @@ int ipmz_batch_data_vjp(ipmz_qp* s, const double* W, int64_t sW, const ipmz_qp_d
                                                             "one call outside the capture first)")))
       return rc;
   }
-  HIP_OK(qp_data_vjp(s->qb, W, s->B > 1 ? sW : 0, o, vjp_ws(s->vjpws.p, 0).part, s->ctx->stream));
+  HIP_OK(qp_data_vjp(s->qb, 1, W, 0, s->B > 1 ? sW : 0, o, vjp_ws(s->vjpws.p, 0).part, s->ctx->stream));
+  return IPMZ_OK;
+}
+
+// The call above for ncot cotangent rows per QP: W's rows checked as the adjoint
+// pair checks its Out, the blocks as ipmz_batch_data_jvp checks its tangents (a
+// row stride per block), with the gradient's rule for a solver of one QP.  The
+// workspace holds a slab of IPMZ_VJP_SLAB rows' partials, never all of them.
+int ipmz_batch_data_vjp_multi(ipmz_qp* s, int ncot, const double* W, int64_t ldw, int64_t sW,
+                              const ipmz_qp_device_grad_multi* grad) {
+  const std::string who = "ipmz_batch_data_vjp_multi";
+  if (!s || !W || !grad) return fail(IPMZ_ERR_INVALID, who + ": null argument");
+  int rc = refuse_unless_newton_order(s, who);
+  if (rc) return rc;
+  if (ncot < 0) return fail(IPMZ_ERR_INVALID, who + ": ncot < 0");
+  if (ldw < s->state_len) return fail(IPMZ_ERR_INVALID, who + ": W: row stride " + std::to_string(ldw) + " < state_len");
+  if (s->B > 1 && ncot > 0 && sW < (int64_t)(ncot - 1) * ldw + s->state_len)
+    return fail(IPMZ_ERR_INVALID, who + ": W: QP stride " + std::to_string(sW) + " < (ncot - 1) * row stride + state_len");
+  const int dims[3] = {s->n, s->m, s->p};
+  const int64_t tq[DB_COUNT] = {grad->tQ, grad->tA, grad->tC, grad->tc, grad->tlx, grad->tux, grad->tlA, grad->tuA, grad->td};
+  const QpBlocksOut o = data_blocks<double>(reinterpret_cast<const ipmz_qp_device_data&>(grad->g), tq, dims);
+  BlockFacts facts;
+  if ((rc = check_blocks(s, who, o, dims, BlockRules{"summed over the batch", ncot, false, true}, &facts))) return rc;
+  if (ncot == 0) return IPMZ_OK;
+  HIP_OK(hipSetDevice(s->ctx->device));
+  if ((rc = wait_pending_step(s))) return rc;  // (a forked step still in flight writes the iterate this call reads)
+  if (facts.shared_matrix) {
+    const size_t need = (size_t)vjp_ws(nullptr, qp_grad_part_elems(s->qb, ncot)).total;
+    if ((rc = grow_unless_capturing(s, s->vjpws, need, who, "the shared blocks' workspace is too small for this call "
+                                                            "(make one such call outside the capture first)")))
+      return rc;
+  }
+  HIP_OK(qp_data_vjp(s->qb, ncot, W, ldw, s->B > 1 ? sW : 0, o, vjp_ws(s->vjpws.p, 0).part, s->ctx->stream));
   return IPMZ_OK;
 }
 

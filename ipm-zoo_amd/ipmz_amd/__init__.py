@@ -56,6 +56,7 @@ EXPORTS = [
     "ipmz_qp_newton_solve_multi", "ipmz_batch_newton_solve_multi",
     "ipmz_qp_newton_adjoint_multi", "ipmz_batch_newton_adjoint_multi",
     "ipmz_batch_load_device", "ipmz_batch_copy_state", "ipmz_batch_data_vjp", "ipmz_batch_data_jvp",
+    "ipmz_batch_data_vjp_multi",
 ]
 SOLVE_MULTI_PANEL = 256  # include/ipmz.h IPMZ_SOLVE_MULTI_PANEL: column panel of the blocked multi-rhs solve
 REDUCTION_AUGMENTED, REDUCTION_NORMAL = 0, 1
@@ -101,6 +102,12 @@ class _QPDeviceData(ctypes.Structure):
 
 class _QPDeviceGrad(_QPDeviceData):
     """include/ipmz.h ipmz_qp_device_grad: the same layout, the blocks written (ipmz_batch_data_vjp)."""
+
+
+class _QPDeviceGradMulti(ctypes.Structure):
+    """include/ipmz.h ipmz_qp_device_grad_multi: the blocks plus a cotangent-row stride each
+    (ipmz_batch_data_vjp_multi)."""
+    _fields_ = [("g", _QPDeviceGrad)] + [(k, _I64) for k in ("tQ", "tA", "tC", "tc", "tlx", "tux", "tlA", "tuA", "td")]
 
 
 class _QPDeviceTangent(ctypes.Structure):
@@ -259,6 +266,7 @@ def _load():
         "ipmz_batch_copy_state": ([_VP, _I, _VP, _I64], _I),
         "ipmz_batch_data_vjp": ([_VP, _VP, _I64, ctypes.POINTER(_QPDeviceGrad)], _I),
         "ipmz_batch_data_jvp": ([_VP, _I, ctypes.POINTER(_QPDeviceTangent), _VP, _I64, _I64], _I),
+        "ipmz_batch_data_vjp_multi": ([_VP, _I, _VP, _I64, _I64, ctypes.POINTER(_QPDeviceGradMulti)], _I),
     }
     for name, (args, res) in sig.items():
         fn = getattr(lib, name)
@@ -721,6 +729,53 @@ class Optimizer:
         self._order_torch_stream(torch)
         sW = W.stride(0) if batch > 1 else W.shape[1]
         _check(lib.ipmz_batch_data_vjp(self.h, _VP(W.data_ptr()), sW, ctypes.byref(g)), "ipmz_batch_data_vjp")
+        if not self.ctx.on_stream(torch.cuda.current_stream(self.ctx.device).cuda_stream):
+            self.ctx.sync()
+        if symmetrize and "Q" in out:
+            out["Q"] = 0.5 * (out["Q"] + out["Q"].transpose(-1, -2))
+        return out
+
+    def data_grad_tensors_multi(self, W, shared=(), symmetrize=False, only=None):
+        """data_grad_tensors for a block of cotangent rows per QP: ipmz_batch_data_vjp_multi.  W: a
+        (batch, ncot, >= state_len) float64 CUDA tensor with inner stride 1, row (q, r) cotangent r of QP q in the
+        order of residuals() -- newton_adjoint(_all)'s Out of nrhs = ncot rows as it is.  Returns a dict with
+        load_tensors' names (blocks of dimension 0 omitted), each a fresh tensor: (batch, ncot, ...) per QP, or,
+        for the names in `shared`, (ncot, ...), row r summed over the batch.  Row r of every block has the bits
+        data_grad_tensors gives for W[:, r] alone.  only, symmetrize and the stream ordering: as in
+        data_grad_tensors."""
+        import torch
+        batch, L = lib.ipmz_batch_size(self.h), self.state_len
+        if not isinstance(W, torch.Tensor) or W.dtype != torch.float64 or W.dim() != 3 or W.shape[0] != batch or \
+                W.shape[2] < L or (W.shape[2] > 1 and W.stride(2) != 1):
+            raise ValueError(f"W: a float64 ({batch}, ncot, >= {L}) tensor with inner stride 1 is needed")
+        self._on_device(W, "W")
+        ncot = W.shape[1]
+        names = [b[0] for b in _BLOCKS]
+        for k in list(shared) + list(only or ()):
+            if k not in names:
+                raise ValueError(f"unknown block {k!r}: one of {names}")
+        dims = dict(n=self.n, m=self.m, p=self.p)
+        g = _QPDeviceGradMulti()
+        out = {}
+        for fields in _BLOCKS:
+            name, _, _, _, rows, cols = fields
+            r, c = (None if rows is None else dims[rows]), dims[cols]
+            if c == 0 or r == 0 or (only is not None and name not in only):
+                continue
+            inner = (c,) if r is None else (r, c)
+            t = torch.empty((ncot,) + inner if name in shared else (batch, ncot) + inner, dtype=torch.float64,
+                            device=W.device)
+            # (a batch of one has no shared blocks: the library ignores the QP stride there)
+            _set_block(g.g, fields, _tensor_block(t, batch, r, c, tangent=True), g)
+            out[name] = t
+        if ncot == 0:  # (nothing to write, and an empty W has no address to hand over)
+            return out
+        self._order_torch_stream(torch)
+        # (the stride of a dimension of size 1 means nothing)
+        ldw = W.stride(1) if ncot > 1 else W.shape[2]
+        sW = W.stride(0) if batch > 1 else max(ncot, 1) * ldw
+        _check(lib.ipmz_batch_data_vjp_multi(self.h, ncot, _VP(W.data_ptr()), ldw, sW, ctypes.byref(g)),
+               "ipmz_batch_data_vjp_multi")
         if not self.ctx.on_stream(torch.cuda.current_stream(self.ctx.device).cuda_stream):
             self.ctx.sync()
         if symmetrize and "Q" in out:

@@ -5,6 +5,8 @@ per QP, the adjoint Newton solve at the converged iterate (J^T w = -g, ipmz_*_ne
 contraction with d r / d data (ipmz_batch_data_vjp): the implicit-function theorem on the Newton system, all on the
 device.  Forward mode (solution_jvp, and solve_qp under torch.autograd.forward_ad): tangents of the data to the
 residual rows (ipmz_batch_data_jvp), then the Newton solve of all rows from one factor (ipmz_*_newton_solve_multi).
+Reverse mode for a block of cotangents per QP (solution_vjp, solution_jacobian): one adjoint solve of all rows from
+one factor, then their contraction with d r / d data in one call (ipmz_batch_data_vjp_multi).
 """
 import torch
 
@@ -113,6 +115,54 @@ def solution_jvp(solver, **tangents):
         s.newton_solve(R.data_ptr(), R.data_ptr(), ntan, ld, ld)
     dz = R[:, :, :L]
     return dz[:, :, :s.n], dz
+
+
+def solution_vjp(solver, G, *, shared=(), only=None, symmetrize=False):
+    """(grads, W): cotangents of the solution of every QP of `solver` (an Optimizer or a Batch) pulled back to its
+    data, ncot rows per QP from one factor, at the solver's current iterate: the reverse counterpart of
+    solution_jvp.
+
+    G: a float64 CUDA tensor, (batch, ncot, n) -- cotangents of x* -- or (batch, ncot, state_len) -- cotangents of
+    the whole Newton state, duals included (the adjoint takes any g).  The chain is: G into an even-stride buffer
+    -> the adjoint Newton solve of all ncot rows in place, J^T w = -g (ipmz_*_newton_adjoint_multi, nrhs = ncot)
+    -> its contraction with d r / d data (ipmz_batch_data_vjp_multi).  Returns grads, Optimizer.
+    data_grad_tensors_multi's dict -- (batch, ncot, ...) per QP, (ncot, ...) summed over the batch for the names in
+    `shared`; only, symmetrize as there -- and W, the (batch, ncot, state_len) view of the residual cotangents.
+    The solver's iterate and generation counter do not move.
+
+    As for solve_qp's gradient: this is the derivative of the solution map only at a converged, strictly
+    complementary solution -- the implicit-function theorem on the Newton system at the current iterate with mu
+    held constant.  At an iterate that has not converged, or where a constraint is active with a zero multiplier,
+    it is the derivative of nothing in particular."""
+    s = solver
+    batch, L, n = lib.ipmz_batch_size(s.h), s.state_len, s.n
+    if not isinstance(G, torch.Tensor) or G.dtype != torch.float64 or G.dim() != 3 or G.shape[0] != batch or \
+            G.shape[2] not in (n, L):
+        raise ValueError(f"G: a float64 ({batch}, ncot, {n}) or ({batch}, ncot, {L}) tensor is needed, got "
+                         f"{getattr(G, 'dtype', type(G))} {tuple(getattr(G, 'shape', ()))}")
+    s._on_device(G, "G")
+    ncot, ld = G.shape[1], _even(L)
+    buf = torch.zeros((batch, ncot, ld), dtype=torch.float64, device=G.device)
+    buf[:, :, :G.shape[2]] = G
+    if ncot:
+        s._order_torch_stream(torch)
+        if isinstance(s, Batch) and batch > 1:
+            s.newton_adjoint_all(buf.data_ptr(), buf.data_ptr(), ncot, ld, ncot * ld, ld, ncot * ld)
+        else:
+            s.newton_adjoint(buf.data_ptr(), buf.data_ptr(), ncot, ld, ld)
+    grads = s.data_grad_tensors_multi(buf, shared=shared, symmetrize=symmetrize, only=only)
+    return grads, buf[:, :, :L]
+
+
+def solution_jacobian(solver, *, shared=(), only=None):
+    """(grads, W) of solution_vjp with G the n unit rows for every QP: grads[name][q, i] is d x_i* / d name of QP q
+    (for the names in `shared`, grads[name][i] is the sum over the QPs), the whole reverse-mode Jacobian of the
+    solution from one factor.  solution_vjp's caveat holds: a converged, strictly complementary iterate, mu held
+    constant."""
+    s = solver
+    batch, n = lib.ipmz_batch_size(s.h), s.n
+    G = torch.eye(n, dtype=torch.float64, device=f"cuda:{s.ctx.device}").expand(batch, n, n)
+    return solution_vjp(s, G, shared=shared, only=only)
 
 
 def solve_qp(solver, *, Q=None, c=None, l_x=None, u_x=None, A_ineq=None, l_A_ineq=None, u_A_ineq=None, A_eq=None,
