@@ -44,6 +44,10 @@
  *                                  batch from device memory (strided blocks, shared or per
  *                                  QP, validated and copied by kernels), and the state of
  *                                  every QP in the reference's Newton order to device memory
+ *   ipmz_batch_set_state_device
+ *                               <- no reference counterpart: the iterate of a whole batch
+ *                                  set from such rows in device memory (a warm start),
+ *                                  pushed into the interior and checked by kernels
  *   ipmz_qp_create + ipmz_qp_load_host
  *                               <- NumericalOptimization::build_environment
  *                                  (EnvironmentBuilder.h:19-20, EnvironmentBuilder.cpp:7-76)
@@ -621,6 +625,54 @@ int ipmz_batch_load_device(ipmz_qp* qp, const ipmz_qp_device_data* data);
  * into a caller's graph capture.  IPMZ_ERR_INVALID for a bad `which`, a null
  * dst or ld < state_len; IPMZ_ERR_STATE before a load. */
 int ipmz_batch_copy_state(ipmz_qp* qp, int which, double* dst_device, int64_t ld);
+/* The warm start: ipmz_batch_set_state of the whole batch from device memory,
+ * the inverse of ipmz_batch_copy_state(qp, IPMZ_STATE_VARS, ..).  Row q of src
+ * (device, at src + q * ld, ld >= ipmz_qp_state_len) holds QP q's iterate in the
+ * reference's Newton order; for IPMZ_EQ_SLACKED_SLACKS / IPMZ_EQ_NAIVE_SLACKS
+ * the kernel scatters it through the inverse of that call's permutation.  No
+ * alignment rule; src[q][state_len .. ld) is never read; a solver of one QP
+ * reads row 0.
+ *
+ * take (device, batch ints; NULL: every QP): QP q is overwritten only if
+ * take[q] != 0, and the rows of the others are never read.
+ *
+ * floor >= 0, the interior push: every component v of a taken row in a slot
+ * the step length keeps non-negative -- lambda_y, lambda_z, lambda_g,
+ * lambda_h, and y, z, g, h where they are Newton variables -- becomes
+ * v < floor ? floor : v, before any check; 0 changes nothing in a row the
+ * check passes (a negative component becomes 0, a violation all the same).
+ * x, s and the free duals are never pushed.  (A converged iterate lies on the boundary:
+ * complementary pairs have one side near 0, and a Newton step from there is
+ * short.  A warm start normally wants floor > 0.)
+ *
+ * The check, over the pushed rows of every taken QP: a NaN anywhere, !(v > 0)
+ * in one of those slots, and -- IPMZ_INEQ_SLACKS, and every formulation with
+ * m == 0, where the step length holds x and s inside explicit bounds --
+ * !(l_x < x < u_x), !(l_A < s < u_A) against the data the solver holds.  One
+ * kernel and one synchronize for its verdict.  A violation returns
+ * IPMZ_ERR_INVALID with a message naming the QP and the index within its row
+ * of the first one in the order (QP, index), whatever the kernel's schedule;
+ * NOTHING is written.  IPMZ_SET_STATE_UNCHECKED: no check and no synchronize
+ * -- stream-ordered launches only, no allocation, so the call may be enqueued
+ * into a caller's graph capture; what an iterate outside the interior does to
+ * the following steps is then the caller's affair.
+ *
+ * Then the taken rows are scattered and every QP is evaluated, as
+ * ipmz_batch_set_state does: for a taken QP the iterate, the residuals and the
+ * scalar block are bitwise what ipmz_batch_set_state(qp, q, the pushed row)
+ * leaves, the others keep their iterate.  The directions, the last step's
+ * scalars, the kept KKT matrix, the restart snapshot, a captured step graph
+ * and the blocking stay as they are.  The checked form returns with the
+ * launches enqueued, not synchronized.
+ *
+ * IPMZ_ERR_INVALID also for a null qp or src, ld < state_len, an unknown flag
+ * bit, a negative or non-finite floor, and floor > 0 with IPMZ_INEQ_SLACKS
+ * (that formulation's positivity is x - l_x etc., not a slot).  IPMZ_ERR_STATE
+ * before a load or between a load and ipmz_batch_initialize, and, for the
+ * checked form only, while the context's stream is capturing. */
+#define IPMZ_SET_STATE_UNCHECKED 1
+int ipmz_batch_set_state_device(ipmz_qp* qp, const double* src, int64_t ld, const int32_t* take, double floor,
+                                int flags);
 /* Enqueue a device-to-device copy of all batch * IPMZ_SC_COUNT scalars
  * (QP-major) to dst (device): the input of the cross-GPU convergence summary. */
 int ipmz_batch_copy_scalars(ipmz_qp* qp, double* dst_device);

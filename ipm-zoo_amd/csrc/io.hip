@@ -2,9 +2,11 @@
 // (ipmz_batch_load_device, ipmz_batch_copy_state): build_environment's bound
 // check over every QP of a caller's strided device blocks, the copy of those
 // blocks into the storage the QPDev descriptors name, and the state vectors
-// of every QP into the rows of one matrix in the reference's Newton order.
+// of every QP into the rows of one matrix in the reference's Newton order --
+// and back (ipmz_batch_set_state_device): the rows of such a matrix, pushed
+// into the interior and checked, into the iterates.
 //
-// All three are plain loads and stores, HBM-bound.  The QP index is a looped
+// All of them are plain loads and stores, HBM-bound.  The QP index is a looped
 // grid dimension (any batch size), every offset is 64-bit, and consecutive
 // threads take consecutive elements of a row.
 #include <climits>
@@ -183,6 +185,118 @@ __global__ void __launch_bounds__(NT) k_io_gather_state(const QPDev* __restrict_
 
 hipError_t qp_gather_state(const QPBatch& qb, int which, double* dst, int64_t ld, hipStream_t st) {
   hipLaunchKernelGGL(k_io_gather_state, block_grid(qb.h.state_len, qb.B), dim3(NT), 0, st, qb.d, which, dst, ld, qb.B);
+  return hipGetLastError();
+}
+
+// ---------------------------------------------------------------------------
+// The warm start (ipmz_batch_set_state_device): the gather's inverse, with the
+// interior push and, in a kernel of its own, the check of what ratio_elem
+// (newton.hip) needs of an iterate.  Both walk the rows the same way and share
+// warm_elem: component k of a caller's row -> the step-vector index j it goes
+// to, its value after the push, and whether the iterate may not hold it.
+namespace {
+// the slot step-vector index j lies in and the index i within it: the last
+// slot in the vector's order (slot_in_order) that starts at or before j --
+// the absent ones, of length 0, start where the next present one does
+__device__ __forceinline__ int state_slot(const QPDev& q, int64_t j, int& i) {
+  int slot = X;
+  int64_t off = 0;
+#pragma unroll
+  for (int k = 1; k < NSLOT; ++k) {
+    const int sl = slot_in_order(q.naive, k);
+    const int64_t o = q.v[sl] - q.v[X];
+    if (o <= j) slot = sl, off = o;
+  }
+  i = (int)(j - off);
+  return slot;
+}
+
+__device__ __forceinline__ double warm_elem(const QPDev& q, const double* __restrict__ row, int64_t k, double floor,
+                                            int64_t& j, bool& bad) {
+  j = q.eqss ? eqss_source(k, q) : k;
+  int i;
+  const int slot = state_slot(q, j, i);
+  double v = row[k];
+  if (nonneg_slot(slot)) {
+    v = v < floor ? floor : v;
+    bad = !(v > 0.0);  // (a NaN passes the push and fails here)
+  } else if (explicit_bounds(q) && slot == X) {
+    bad = !(q.lx[i] < v && v < q.ux[i]);
+  } else if (explicit_bounds(q) && slot == S) {
+    bad = !(q.lA[i] < v && v < q.uA[i]);
+  } else {
+    bad = v != v;
+  }
+  return v;
+}
+}  // namespace
+
+// The thread index runs over the SOURCE row, the caller's order: the loads of
+// a wave are consecutive whatever the row's alignment and stride, a row that
+// is not taken and the padding of one that is are never touched, and the
+// check's key is the index the caller knows.  The stores are the permuted
+// side, but eqss_source maps the row piecewise by translation (at most nine
+// pieces: x / the duals, four of each equality-slack block, the rest), so
+// they are consecutive too except in the waves that straddle a piece's end --
+// the gather's argument with load and store exchanged.  Indexing the
+// destination instead would need the inverse map stated a second time and
+// gain nothing: one side is cut at the piece ends either way.
+__global__ void __launch_bounds__(NT) k_io_scatter_state(const QPDev* __restrict__ qs, const double* __restrict__ src,
+                                                         int64_t ld, const int32_t* __restrict__ take, double floor,
+                                                         int B) {
+  const int64_t L = qs[0].state_len;
+  for (int z = blockIdx.y; z < B; z += gridDim.y) {
+    if (take && !take[z]) continue;
+    const QPDev& q = qs[z];
+    const double* row = src + (int64_t)z * ld;
+    double* dst = q.v[X];
+    for (int64_t k = blockIdx.x * (int64_t)NT + threadIdx.x; k < L; k += (int64_t)gridDim.x * NT) {
+      int64_t j;
+      bool bad;
+      const double v = warm_elem(q, row, k, floor, j, bad);
+      dst[j] = v;
+    }
+  }
+}
+
+hipError_t qp_scatter_state(const QPBatch& qb, const double* src, int64_t ld, const int32_t* take, double floor,
+                            hipStream_t st) {
+  hipLaunchKernelGGL(k_io_scatter_state, block_grid(qb.h.state_len, qb.B), dim3(NT), 0, st, qb.d, src, ld, take, floor,
+                     qb.B);
+  return hipGetLastError();
+}
+
+// The smallest key z * state_len + k of a violation wins whatever the
+// schedule: one atomicMin per wave that saw one (as k_io_validate).
+__global__ void __launch_bounds__(NT) k_io_scatter_validate(const QPDev* __restrict__ qs, const double* __restrict__ src,
+                                                            int64_t ld, const int32_t* __restrict__ take, double floor,
+                                                            int B, unsigned long long* __restrict__ verdict) {
+  const int64_t L = qs[0].state_len;
+  unsigned long long key = IPMZ_IO_VALID;
+  for (int z = blockIdx.y; z < B; z += gridDim.y) {
+    if (take && !take[z]) continue;
+    const QPDev& q = qs[z];
+    const double* row = src + (int64_t)z * ld;
+    for (int64_t k = blockIdx.x * (int64_t)NT + threadIdx.x; k < L; k += (int64_t)gridDim.x * NT) {
+      int64_t j;
+      bool bad;
+      warm_elem(q, row, k, floor, j, bad);
+      if (bad) {
+        const unsigned long long cand = (unsigned long long)z * (unsigned long long)L + (unsigned long long)k;
+        key = cand < key ? cand : key;
+      }
+    }
+  }
+  key = wave_min_u64(key);
+  if ((threadIdx.x & 63) == 0 && key != IPMZ_IO_VALID) atomicMin(verdict, key);
+}
+
+hipError_t qp_scatter_validate(const QPBatch& qb, const double* src, int64_t ld, const int32_t* take, double floor,
+                               unsigned long long* verdict, hipStream_t st) {
+  hipError_t e = hipMemsetAsync(verdict, 0xff, sizeof(unsigned long long), st);  // IPMZ_IO_VALID
+  if (e != hipSuccess) return e;
+  hipLaunchKernelGGL(k_io_scatter_validate, block_grid(qb.h.state_len, qb.B), dim3(NT), 0, st, qb.d, src, ld, take,
+                     floor, qb.B, verdict);
   return hipGetLastError();
 }
 

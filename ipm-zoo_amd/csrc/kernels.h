@@ -498,6 +498,19 @@ __host__ __device__ __forceinline__ int64_t eqss_source(int64_t k, const QPDev& 
   return k;  // y, z
 }
 
+// The order the slots lie in within one contiguous step vector (qp.cpp carve: v[X] is its base and the slot pointers
+// ascend in this order, absent slots having length 0): the enum's, except that NaiveSlacks puts its duals lambda_g,
+// lambda_h ahead of lambda_C (formulations.txt).
+__host__ __device__ __forceinline__ int slot_in_order(bool naive, int k) {
+  constexpr int naive_order[NSLOT] = {X, LG, LH, LC, P, LY, LZ, G, H, Y, Z, LA, S};
+  return naive ? naive_order[k] : k;
+}
+// What ratio_elem (newton.hip) holds an iterate to, stated once for the warm start's push and check (io.hip): the
+// slots it keeps non-negative -- lambda_g, lambda_h, lambda_y, lambda_z and, where they are Newton variables, g, h,
+// y, z: the enum's tail -- and the explicit bounds l_x < x < u_x, l_A < s < u_A it applies when neither g nor h is one.
+__host__ __device__ __forceinline__ bool nonneg_slot(int slot) { return slot >= LG; }
+__host__ __device__ __forceinline__ bool explicit_bounds(const QPDev& q) { return q.slacks || q.m == 0; }
+
 // A batch of QPs with identical (n, m, p): d = device array of B
 // descriptors (kernels index it with blockIdx.y), h = host copy of QP 0.
 struct QPBatch {
@@ -610,6 +623,18 @@ hipError_t qp_io_pack(const QPBatch& qb, const QpBlocksIn& in, hipStream_t st);
 // row z of dst (device, row stride ld >= state_len) <- QP z's state `which`
 // (IPMZ_STATE_*) in the reference's Newton order; one launch, no allocation
 hipError_t qp_gather_state(const QPBatch& qb, int which, double* dst, int64_t ld, hipStream_t st);
+// The other direction (ipmz_batch_set_state_device): the iterate of every QP z with take[z] != 0 (take == nullptr:
+// every QP) <- row z of src (device, row stride ld >= state_len, the reference's Newton order), each component of a
+// slot ratio_elem keeps non-negative raised to at least `floor` on the way.  One launch, no allocation; rows of QPs
+// not taken and columns [state_len, ld) are never read.
+hipError_t qp_scatter_state(const QPBatch& qb, const double* src, int64_t ld, const int32_t* take, double floor,
+                            hipStream_t st);
+// The check of those rows after the same push: a NaN anywhere, !(v > 0) in a non-negative slot, or, where
+// explicit_bounds holds, x outside (l_x, u_x) or s outside (l_A, u_A) of the data the solver holds.  Resets and fills
+// *verdict (device): IPMZ_IO_VALID, or the smallest z * state_len + k of a violating component k (the caller's
+// order) of QP z.  Independent of scheduling; writes nothing else.
+hipError_t qp_scatter_validate(const QPBatch& qb, const double* src, int64_t ld, const int32_t* take, double floor,
+                               unsigned long long* verdict, hipStream_t st);
 
 // grad.hip -------------------------------------------------------------------
 // QPs per chunk of the shared matrix blocks' sum over the batch: every chunk's

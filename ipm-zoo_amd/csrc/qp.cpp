@@ -7,6 +7,7 @@
 // kernels take a device array of QPDev descriptors and index it with
 // blockIdx.y, so one launch serves the whole batch.
 #include <algorithm>
+#include <cmath>
 
 #include "capi.h"
 
@@ -256,13 +257,11 @@ void drop_graph(ipmz_qp* s) {
 }
 
 // slot pointers into one contiguous Newton-order vector (the reference's
-// order; NaiveSlacks puts its duals lambda_g, lambda_h ahead of lambda_C,
-// formulations.txt)
+// order: slot_in_order, kernels.h)
 void carve(const ipmz_qp* s, double* base, double** slots) {
-  static const int naive_order[NSLOT] = {X, LG, LH, LC, P, LY, LZ, G, H, Y, Z, LA, S};
   int64_t off = 0;
   for (int k = 0; k < NSLOT; ++k) {
-    const int slot = s->naive ? naive_order[k] : k;
+    const int slot = slot_in_order(s->naive, k);
     slots[slot] = base + off;
     off += slot_len(s, slot);
   }
@@ -1625,6 +1624,49 @@ int ipmz_batch_copy_state(ipmz_qp* s, int which, double* dst, int64_t ld) {
   if (!s->loaded) return fail(IPMZ_ERR_STATE, "ipmz_batch_copy_state: load or generate the QP first");
   HIP_OK(hipSetDevice(s->ctx->device));
   HIP_OK(qp_gather_state(s->qb, which, dst, ld, s->ctx->stream));
+  return IPMZ_OK;
+}
+
+// ipmz_batch_set_state for the whole batch from device memory (io.hip): the check of the pushed rows (one kernel,
+// one synchronize for its verdict; not with IPMZ_SET_STATE_UNCHECKED), the scatter with the push, then
+// set_state_impl's evaluation of every QP.  Besides the iterate, the residuals and the scalar block's evaluated
+// entries nothing moves: the direction slots, the last step's scalars, the kept matrix K0, the restart snapshot,
+// a captured step graph and the blocking are the host call's to leave alone and this one's.
+int ipmz_batch_set_state_device(ipmz_qp* s, const double* src, int64_t ld, const int32_t* take, double floor,
+                                int flags) {
+  const std::string who = "ipmz_batch_set_state_device";
+  if (!s || !src) return fail(IPMZ_ERR_INVALID, who + ": null argument");
+  if (ld < s->state_len)
+    return fail(IPMZ_ERR_INVALID, who + ": row stride " + std::to_string(ld) + " < state_len " +
+                                      std::to_string(s->state_len));
+  if (flags & ~IPMZ_SET_STATE_UNCHECKED) return fail(IPMZ_ERR_INVALID, who + ": unknown flag bit");
+  if (!(floor >= 0.0 && floor < INFINITY))
+    return fail(IPMZ_ERR_INVALID, who + ": floor must be finite and >= 0");
+  if (floor > 0.0 && s->slacks)
+    return fail(IPMZ_ERR_INVALID, who + ": floor > 0 with InequalityHandling::Slacks (its positivity is x - l_x, "
+                                        "u_x - x, s - l_A, u_A - s, not a slot a push could raise)");
+  if (!s->loaded) return fail(IPMZ_ERR_STATE, who + ": load (and initialize) the QP first");
+  HIP_OK(hipSetDevice(s->ctx->device));
+  const bool checked = !(flags & IPMZ_SET_STATE_UNCHECKED);
+  int rc;
+  if (checked && (rc = not_capturing(s->ctx, who.c_str()))) return rc;
+  if ((rc = wait_pending_step(s))) return rc;
+  hipStream_t st = s->ctx->stream;
+  if (checked) {
+    unsigned long long verdict = IPMZ_IO_VALID;
+    HIP_OK(qp_scatter_validate(s->qb, src, ld, take, floor, s->verdict, st));
+    HIP_OK(hipMemcpyAsync(&verdict, s->verdict, sizeof verdict, hipMemcpyDeviceToHost, st));
+    HIP_OK(hipStreamSynchronize(st));
+    if (verdict != IPMZ_IO_VALID) {  // nothing was written
+      const unsigned long long L = (unsigned long long)s->state_len;
+      return fail(IPMZ_ERR_INVALID, who + ": QP " + std::to_string(verdict / L) + ": not an interior iterate at index " +
+                                        std::to_string(verdict % L) +
+                                        " (NaN, a non-positive slack or multiplier, or x / s not strictly inside its "
+                                        "bounds)");
+    }
+  }
+  HIP_OK(qp_scatter_state(s->qb, src, ld, take, floor, st));
+  HIP_OK(qp_evaluate(s->qb, st));
   return IPMZ_OK;
 }
 

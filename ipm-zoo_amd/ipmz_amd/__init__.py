@@ -31,6 +31,7 @@ SC_COUNT = 16
 PH = dict(step=0, assemble=1, factor=2, solve=3, trailing=4, eval=5)
 STEP_RESTART_IF_CONVERGED = 1
 STEP_GRAPH = 2
+SET_STATE_UNCHECKED = 1  # include/ipmz.h IPMZ_SET_STATE_UNCHECKED
 SLOTS = ["x", "lambda_A", "lambda_C", "s", "p", "lambda_g", "lambda_h", "lambda_y", "lambda_z", "g", "h", "y", "z"]
 
 EXPORTS = [
@@ -56,7 +57,7 @@ EXPORTS = [
     "ipmz_qp_newton_solve_multi", "ipmz_batch_newton_solve_multi",
     "ipmz_qp_newton_adjoint_multi", "ipmz_batch_newton_adjoint_multi",
     "ipmz_batch_load_device", "ipmz_batch_copy_state", "ipmz_batch_data_vjp", "ipmz_batch_data_jvp",
-    "ipmz_batch_data_vjp_multi",
+    "ipmz_batch_data_vjp_multi", "ipmz_batch_set_state_device",
 ]
 SOLVE_MULTI_PANEL = 256  # include/ipmz.h IPMZ_SOLVE_MULTI_PANEL: column panel of the blocked multi-rhs solve
 REDUCTION_AUGMENTED, REDUCTION_NORMAL = 0, 1
@@ -267,6 +268,7 @@ def _load():
         "ipmz_batch_data_vjp": ([_VP, _VP, _I64, ctypes.POINTER(_QPDeviceGrad)], _I),
         "ipmz_batch_data_jvp": ([_VP, _I, ctypes.POINTER(_QPDeviceTangent), _VP, _I64, _I64], _I),
         "ipmz_batch_data_vjp_multi": ([_VP, _I, _VP, _I64, _I64, ctypes.POINTER(_QPDeviceGradMulti)], _I),
+        "ipmz_batch_set_state_device": ([_VP, _VP, _I64, _VP, ctypes.c_double, _I], _I),
     }
     for name, (args, res) in sig.items():
         fn = getattr(lib, name)
@@ -692,6 +694,40 @@ class Optimizer:
         _check(lib.ipmz_batch_copy_state(self.h, which, _VP(out.data_ptr()), ld), "ipmz_batch_copy_state")
         self.ctx.sync()
         return out[:, :L]
+
+    def set_state_tensor(self, V, take=None, floor=0.0, check=True):
+        """The iterate of every QP from a float64 CUDA tensor, state_tensor(0)'s inverse -- a warm start:
+        ipmz_batch_set_state_device.  V: (batch, >= state_len) with inner stride 1 and any row stride, row q the
+        iterate of QP q in the order of vars() / state(q); columns from state_len on are not read.  take: None
+        (every QP), or a (batch,) bool or integer tensor -- QP q is set only where take[q] != 0, and the rows of
+        the others are not read.  floor >= 0: every slack and inequality multiplier of a taken row (the slots the
+        step length keeps non-negative) below floor becomes floor; a converged iterate lies on the boundary, so a
+        warm start normally wants floor > 0.  check=True: a NaN, a non-positive slack or multiplier after the
+        push, or (INEQ_SLACKS, and m == 0) x or s not strictly inside its bounds raises IpmzError naming the first
+        (QP, index), nothing written, and costs one synchronize; check=False only enqueues (and may be captured
+        into a graph on the context's stream).  On the context's stream, ordered after torch's current stream like
+        load_tensors; then every QP is evaluated, as set_state does."""
+        import torch
+        batch, L = lib.ipmz_batch_size(self.h), self.state_len
+        if not isinstance(V, torch.Tensor) or V.dtype != torch.float64 or V.dim() != 2 or V.shape[0] != batch or \
+                (V.shape[1] > 1 and V.stride(1) != 1):
+            raise ValueError(f"V: a float64 ({batch}, >= {L}) tensor with inner stride 1 is needed")
+        self._on_device(V, "V")
+        if take is not None:
+            if not isinstance(take, torch.Tensor) or take.shape != (batch,) or take.is_floating_point() or \
+                    take.is_complex():
+                raise ValueError(f"take: a bool or integer ({batch},) tensor is needed")
+            self._on_device(take, "take")
+            take = (take != 0).to(torch.int32).contiguous()
+        # (too few columns: the library refuses the row stride; the stride of a single row means nothing)
+        ld = V.shape[1] if V.shape[1] < L or batch == 1 else V.stride(0)
+        self._bump()
+        self._order_torch_stream(torch)
+        _check(lib.ipmz_batch_set_state_device(self.h, _VP(V.data_ptr()), ld, _VP(take.data_ptr()) if take is not None
+                                               else None, float(floor), 0 if check else SET_STATE_UNCHECKED),
+               "ipmz_batch_set_state_device")
+        if not self.ctx.on_stream(torch.cuda.current_stream(self.ctx.device).cuda_stream):
+            self.ctx.sync()  # (V and take may be freed or rewritten on torch's stream once this returns)
 
     def data_grad_tensors(self, W, shared=(), symmetrize=False, only=None):
         """The gradient with respect to the problem data from the cotangent with respect to the residuals:

@@ -22,8 +22,12 @@ def _even(k):
 class _SolveQP(torch.autograd.Function):
     @staticmethod
     def forward(ctx, solver, max_iter, strict, symmetrize, *blocks):
+        # (after the data blocks: the warm start, an iterate per QP and its floor -- no input of the derivative)
+        blocks, warm = blocks[:len(_NAMES)], blocks[len(_NAMES):]
         given = {k: t.detach() for k, t in zip(_NAMES, blocks) if t is not None}
         solver.load_tensors(**given)
+        if warm and warm[0] is not None:
+            solver.set_state_tensor(warm[0].detach(), floor=warm[1], check=True)
         batch = lib.ipmz_batch_size(solver.h)
         if isinstance(solver, Batch):
             its, converged = solver.solve_all(max_iter)
@@ -67,7 +71,7 @@ class _SolveQP(torch.autograd.Function):
             if g is None and k in wanted:  # a block of dimension 0
                 g = torch.zeros(ctx.shapes[k], dtype=torch.float64, device=grad_x.device)
             out.append(None if g is None else g.reshape(ctx.shapes[k]))
-        return (None, None, None, None, *out)
+        return (None, None, None, None, *out, None, None)
 
     @staticmethod
     def jvp(ctx, _solver, _max_iter, _strict, _symmetrize, *tangents):
@@ -166,7 +170,7 @@ def solution_jacobian(solver, *, shared=(), only=None):
 
 
 def solve_qp(solver, *, Q=None, c=None, l_x=None, u_x=None, A_ineq=None, l_A_ineq=None, u_A_ineq=None, A_eq=None,
-             b_eq=None, max_iter=100, strict=True, symmetrize=False):
+             b_eq=None, max_iter=100, strict=True, symmetrize=False, warm_start=None, warm_floor=0.0):
     """x* of every QP of `solver` (an Optimizer or a Batch), (batch, n), differentiable with respect to the data.
 
     The data are float64 CUDA tensors under load_tensors' names and rules: matrices (batch, rows, n) or (rows, n)
@@ -184,7 +188,19 @@ def solve_qp(solver, *, Q=None, c=None, l_x=None, u_x=None, A_ineq=None, l_A_ine
     the gradient for a caller who builds Q symmetric.  Formulations: those the adjoint solve serves (not
     EQ_SLACKED_SLACKS / EQ_NAIVE_SLACKS); INEQ_SLACKS does not converge (the reference's corrector defect).
 
+    warm_start: None (the solve starts from build_environment's iterate), or a float64 CUDA tensor (batch,
+    state_len), an iterate per QP in the order of state_tensor() -- typically the previous solve's: after
+    load_tensors it is set with set_state_tensor(warm_start, floor=warm_floor, check=True) and the solve starts
+    there.  It takes no gradient and is no differentiable input; backward and jvp read the final iterate as before.
+    A converged iterate lies on the boundary -- of every complementary pair one side is near 0, and a Newton step
+    from there is short -- so a warm start normally wants warm_floor > 0, which raises every slack and inequality
+    multiplier below it.  How many iterations a warm start saves, and with which floor, is a measurement
+    (the warm start's table), not a promise; the default warm_floor stays 0.0 until it is settled.
+
     The solver keeps the iterate the backward pass reads: one forward / backward pair is in flight per solver, and
-    backward raises IpmzError when a load, step, solve or set_vars has moved the solver since its forward."""
+    backward raises IpmzError when a load, step, solve, set_vars or set_state_tensor has moved the solver since its
+    forward."""
     given = dict(Q=Q, c=c, l_x=l_x, u_x=u_x, A_ineq=A_ineq, l_A_ineq=l_A_ineq, u_A_ineq=u_A_ineq, A_eq=A_eq, b_eq=b_eq)
-    return _SolveQP.apply(solver, max_iter, strict, symmetrize, *[given[k] for k in _NAMES])
+    if warm_start is not None:
+        warm_start = warm_start.detach()
+    return _SolveQP.apply(solver, max_iter, strict, symmetrize, *[given[k] for k in _NAMES], warm_start, warm_floor)
