@@ -488,6 +488,12 @@ int ipmz_qp_set_state(ipmz_qp* qp, const double* host_vars);
  * (lower triangle written, upper zero).  For parity tests. */
 int ipmz_qp_get_kkt(ipmz_qp* qp, double* host_K);
 int ipmz_qp_kkt_dim(ipmz_qp* qp);
+/* What the last step's factor left on the QP's storage, for parity tests
+ * (single QPs on the fp64 augmented LDL^T with nbi = 64, else IPMZ_ERR_STATE):
+ * host_L, N x N row-major (lower triangle as stored, upper zero); host_D, N;
+ * host_P, the persistent solve's prepared operators, *p_len doubles (the two
+ * blocks no solve reads are zero).  Each pointer may be null; synchronizes. */
+int ipmz_qp_get_factor(ipmz_qp* qp, double* host_L, double* host_D, double* host_P, int64_t* p_len);
 /* Solve with the KKT matrix of the QP's current iterate: assembles it (the
  * matrix ipmz_qp_get_kkt returns, order ipmz_qp_kkt_dim), factors it and
  * solves the nrhs rows of B (device, Newton order, stride ldb >= N, even) as

@@ -92,8 +92,20 @@ hipError_t solve_ws(const double* K, int64_t ld, int N, const double* D, const L
   return ldlt_solve(K, ld, N, D, w.Linv, nbi, b, w.side, st);
 }
 
+hipError_t solve_ws_tail(const double* K, int64_t ld, int N, const double* D, const LdltWs& w, double* b, int rows,
+                         hipStream_t st) {
+  return ldlt_solve_persistent_tail(K, ld, N, D, w.P, b, w.y, w.z, w.ctrl, rows, st);
+}
+
+int chain_bound_rows(int N, int nbo) {
+  int k = 0;
+  while (N - k * nbo > IPMZ_EARLY_CHAIN_MAX_N) ++k;
+  const int r = k * nbo / IPMZ_SOLVE_BLOCK * IPMZ_SOLVE_BLOCK;
+  return r >= N - IPMZ_SOLVE_BLOCK ? 0 : r;
+}
+
 int factor_impl(ipmz_ctx* ctx, int N, double* K, int64_t ld, double* D, const LdltWs& w, int nbo, TrailTimer* timer,
-                int* info2) {
+                int* info2, StepEdges* edges) {
   // one launch: info, the panel ctrl words and the persistent solve's state
   // for this factor
   HIP_OK(solve_reset(w.y, w.z, sizeof(double), N, w.ctrl, ctx->stream, w.info, w.pctrl, panel_ctrl_words(N, nbo),
@@ -103,16 +115,36 @@ int factor_impl(ipmz_ctx* ctx, int N, double* K, int64_t ld, double* D, const Ld
   auto prep = [&]() -> hipError_t {
     return ctx->nbi == 64 ? solve_prep(K, ld, N, w.Linv, w.P, ctx->stream) : hipSuccess;
   };
+  FactorHooks hooks;
+  if (edges) {
+    edges->swept = false;
+    hooks.before_b = edges->rest;
+  }
   if (npan < 3 || (debug_inject_mask() & IPMZ_DEBUG_ONE_STREAM)) {
     HIP_OK(ldlt_factor(K, ld, N, D, w.Linv, w.W, nbo, ctx->nbi, w.info, ctx->stream, timer, nullptr, nullptr, nullptr,
-                       0, w.pctrl));
+                       0, w.pctrl, nullptr, edges ? &hooks : nullptr));
     HIP_OK(prep());
     return IPMZ_OK;
   }
-  const int nev = 5 * npan + 5;  // ldlt_factor's 5 npan + 3, the fork, one spare
+  // ldlt_factor's 5 npan + 3, its hook's, the early sweep's; the fork, one spare
+  const int nev = 5 * npan + 7;
   int rc = ensure_events(ctx, (size_t)nev + 4);
   if (rc) return rc;
   hipEvent_t* ev = ctx->evpool.data();
+  // the back edge: the leading rows' operators and forward sweep on the
+  // fourth stream, which this factor leaves idle
+  hipEvent_t evSwept = ev[5 * npan + 4];
+  const int R = edges && ctx->nbi == 64 && edges->rows % IPMZ_SOLVE_BLOCK == 0 && edges->rows < N ? edges->rows : 0;
+  if (R > 0) {
+    hooks.final_rows = R;
+    hooks.final_st = ctx->sD;
+    hooks.rows_final = [&](hipStream_t s4) -> hipError_t {
+      hipError_t e = solve_prep_split(K, ld, N, w.Linv, w.P, R, true, s4);
+      if (e == hipSuccess) e = ldlt_solve_persistent_head(K, ld, N, D, w.P, edges->b, w.y, w.z, w.ctrl, R, s4);
+      if (e == hipSuccess) e = stream_record(evSwept, s4);
+      return e;
+    };
+  }
   // the fourth look-ahead stream pays for the fp32 factor only (C5 23.6 ->
   // 22.9 ms per step); the fp64 one runs faster without it (C3 14.2 -> 14.0
   // ms), profiles/r03_s5/fourth_stream_ab.log -- not forked at all here
@@ -123,7 +155,13 @@ int factor_impl(ipmz_ctx* ctx, int N, double* K, int64_t ld, double* D, const Ld
   // (a fork onto A cost the C2 step ~70 us of host enqueue before the first
   // panel, profiles/r05_s18)
   HIP_OK(ldlt_factor(K, ld, N, D, w.Linv, w.W, nbo, ctx->nbi, w.info, ctx->stream, timer, ctx->sB, ctx->sC, ev,
-                     nev - 2, w.pctrl, fourth ? ctx->sD : nullptr));
+                     nev - 2, w.pctrl, fourth ? ctx->sD : nullptr, edges ? &hooks : nullptr));
+  if (hooks.fired) {  // join the fourth stream; the operators that read rows >= R
+    HIP_OK(stream_wait(ctx->stream, evSwept));
+    HIP_OK(solve_prep_split(K, ld, N, w.Linv, w.P, R, false, ctx->stream));
+    edges->swept = true;
+    return IPMZ_OK;
+  }
   HIP_OK(prep());
   return IPMZ_OK;
 }

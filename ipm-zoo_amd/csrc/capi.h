@@ -270,9 +270,30 @@ extern const char PANEL_TIMEOUT[], SOLVE_TIMEOUT[];
 int ws_result(hipStream_t st, const int* info, const unsigned* pe, const unsigned* se, const char* what,
               const char* pe_text = PANEL_TIMEOUT, const char* se_text = SOLVE_TIMEOUT);
 int read_info(ipmz_ctx* ctx, const LdltWs& w);  // ws_result of a factor's whole workspace
+// The Newton step's work in the idle edges of a forked factor (run_step;
+// DESIGN.md §4 "The factor's idle edges").  rest: the assembly of the columns
+// >= nbo, on the trailing stream beside the first panel.  rows > 0 (nbi 64
+// only): once the leading `rows` rows of the factor are final, the fourth
+// stream prepares their solve operators and runs the forward sweep of b over
+// them; `swept` then, and the solve of b is solve_ws_tail.  A factor that does
+// not fork runs `rest` first on the step's stream and leaves swept false.
+struct StepEdges {
+  std::function<hipError_t(hipStream_t)> rest;
+  int rows = 0;
+  const double* b = nullptr;
+  bool swept = false;
+};
+// the forked factor's chain-bound stretch begins with the first panel that
+// leaves an order <= IPMZ_EARLY_CHAIN_MAX_N: the rows final by then, as a
+// multiple of the solve's block (0: no GEMM-paced stretch, or no block left
+// after it)
+int chain_bound_rows(int N, int nbo);
 // info2: a caller's own info word, reset in the same launch
 int factor_impl(ipmz_ctx* ctx, int N, double* K, int64_t ld, double* D, const LdltWs& w, int nbo, TrailTimer* timer,
-                int* info2 = nullptr);
+                int* info2 = nullptr, StepEdges* edges = nullptr);
+// the rest of a solve whose forward sweep over the leading rows ran in the factor (StepEdges::swept)
+hipError_t solve_ws_tail(const double* K, int64_t ld, int N, const double* D, const LdltWs& w, double* b, int rows,
+                         hipStream_t st);
 hipError_t solve_ws(const double* K, int64_t ld, int N, const double* D, const LdltWs& w, int nbi, double* b,
                     hipStream_t st);
 int mixed_factor_impl(ipmz_ctx* ctx, const double* K, int64_t ld, MixedWs& w, TrailTimer* timer);

@@ -4,6 +4,8 @@
 #include <stdint.h>
 #include <stdio.h>
 
+#include <functional>
+
 #define IPMZ_NBO_MAX 512
 #define IPMZ_PANEL_CTRL_WORDS 320
 // fused factor: largest N whose chain launches start beside the previous
@@ -48,6 +50,11 @@ namespace ipmz {
 // 2097152 / 4194304 = ipmz_*_newton_solve_multi's element-wise kernels take 1 / 8 rows per thread instead
 //         of IPMZ_NEWTON_MULTI_RPG; both bits = 2 (A/B, tools/newton_multi_bench.py; the same bits in every row);
 //         ipmz_*_newton_adjoint_multi's two kernels launch the same way,
+// 8388608 = the single-QP step keeps the serial order around its forked factor: the whole assembly before
+//         it, the affine right-hand side, solve_prep and the whole forward sweep after it (A/B and
+//         tests/test_gpu_step_edges.py: bitwise the overlapped order, DESIGN.md §4 "The factor's idle edges"),
+// bits 24-29 = v > 0: the early forward sweep of that step covers (v - 1) * 128 rows instead of the rows
+//         that are final when the factor turns chain-bound (tests: the split at every boundary),
 enum { IPMZ_INJECT_SOLVE = 1, IPMZ_INJECT_PANEL = 2, IPMZ_INJECT_GRAPH_FORKS = 4, IPMZ_DEBUG_CONVERT_ONLY = 16,
        IPMZ_DEBUG_ONE_STREAM = 32, IPMZ_DEBUG_TRACE = 64, IPMZ_DEBUG_F32_ENGINE = 128,
        IPMZ_DEBUG_NO_FOURTH = 256, IPMZ_DEBUG_IR_FULL = 512,
@@ -55,7 +62,8 @@ enum { IPMZ_INJECT_SOLVE = 1, IPMZ_INJECT_PANEL = 2, IPMZ_INJECT_GRAPH_FORKS = 4
        IPMZ_DEBUG_NO_K0 = 8192, IPMZ_DEBUG_NO_FUSED_SOLVES = 16384, IPMZ_DEBUG_READY_LATE = 32768,
        IPMZ_DEBUG_MULTI_BLOCKED = 65536, IPMZ_DEBUG_MULTI_W512 = 131072,
        IPMZ_DEBUG_MULTI_W128 = 262144, IPMZ_DEBUG_SOLVE_H2 = 524288, IPMZ_DEBUG_SOLVE_H4 = 1048576,
-       IPMZ_DEBUG_NEWTON_RPG1 = 2097152, IPMZ_DEBUG_NEWTON_RPG8 = 4194304 };
+       IPMZ_DEBUG_NEWTON_RPG1 = 2097152, IPMZ_DEBUG_NEWTON_RPG8 = 4194304, IPMZ_DEBUG_SERIAL_EDGES = 8388608,
+       IPMZ_DEBUG_EDGE_ROWS_SHIFT = 24, IPMZ_DEBUG_EDGE_ROWS_MASK = 63 << 24 };
 #define IPMZ_TRACE(...)                                                  \
   do {                                                                   \
     if (::ipmz::debug_inject_mask() & ::ipmz::IPMZ_DEBUG_TRACE) {        \
@@ -138,9 +146,30 @@ struct TrailTimer {  // HIP-event pairs around every dominant trailing-update la
 // (else N * nbo).  pctrl: panel_ctrl_words(N, nbo) zeroed words for the
 // panel path of panel.hip (nbi == 64); nullptr selects the diag / TRSM /
 // strip kernel chain.
+// Work of the caller's that the look-ahead factor places in its two idle
+// edges (it knows nothing about that work; the Newton step's: capi.cpp
+// factor_impl).  Needs one event more: nev >= 5 * ceil(N/nbo) + 4.
+//   before_b: enqueued on stream B after everything the caller enqueued on st
+//     and before B's first update.  It may write columns >= nbo of K (the first
+//     panel reads none of them); every other stream waits for it before its
+//     first touch of those columns.  The single-stream factor calls it on st
+//     before anything else.
+//   rows_final: called once with `final_st` made to wait until the rows
+//     < final_rows of L, D and the L^{-1} blocks are final, at the first outer
+//     panel whose completion makes them so; `fired` then.  The caller joins
+//     final_st back to st after the factor.  Not called by the single-stream
+//     factor, nor with final_rows <= 0.
+struct FactorHooks {
+  std::function<hipError_t(hipStream_t)> before_b;
+  int final_rows = 0;
+  hipStream_t final_st = nullptr;
+  std::function<hipError_t(hipStream_t)> rows_final;
+  bool fired = false;
+};
 hipError_t ldlt_factor(double* K, int64_t ld, int N, double* D, double* Linv, double* W, int nbo, int nbi,
                        int* info, hipStream_t st, TrailTimer* timer = nullptr, hipStream_t st2 = nullptr,
-                       hipStream_t st3 = nullptr, hipEvent_t* ev = nullptr, int nev = 0, unsigned* pctrl = nullptr, hipStream_t st4 = nullptr);
+                       hipStream_t st3 = nullptr, hipEvent_t* ev = nullptr, int nev = 0, unsigned* pctrl = nullptr,
+                       hipStream_t st4 = nullptr, FactorHooks* hooks = nullptr);
 // the same blocked LDL^T in fp32 (fp32 MFMA trailing update): the factor of
 // the mixed-precision solve (C5)
 hipError_t ldlt_factor(float* K, int64_t ld, int N, float* D, float* Linv, float* W, int nbo, int nbi, int* info,
@@ -255,6 +284,25 @@ hipError_t solve_prep(const double* K, int64_t ld, int N, const double* Linv, do
 hipError_t solve_prep(const float* K, int64_t ld, int N, const float* Linv, float* P, hipStream_t st);
 hipError_t ldlt_solve_persistent(const double* K, int64_t ld, int N, const double* D, const double* P, double* b,
                                  double* ybuf, double* xbuf, unsigned* ctrl, hipStream_t st);
+// The same preparation and solve in two parts around R rows (a multiple of
+// 128, 0 < R < N) that are final before the rest of the factor is:
+//   head: the operators that read only rows < R (X_J, M_J of the block rows
+//     below R and Q_J of all but the last of them), then the forward sweep
+//     over the leading R rows of b -- the leading principal block of the
+//     forward substitution, the same arithmetic;
+//   tail (after the factor and the head): the other operators; then
+//     ldlt_solve_persistent_tail: the forward sweep over the block rows from
+//     R / 128 on (their bulk sums over all earlier blocks, as ever), and the
+//     backward sweep.
+// Every element goes through the operations of the unsplit calls in the same
+// order (the parts per block are those of the whole N): bitwise alike.
+hipError_t solve_prep_split(const double* K, int64_t ld, int N, const double* Linv, double* P, int R, bool head,
+                            hipStream_t st);
+hipError_t ldlt_solve_persistent_head(const double* K, int64_t ld, int N, const double* D, const double* P,
+                                      const double* b, double* ybuf, double* xbuf, unsigned* ctrl, int R,
+                                      hipStream_t st);
+hipError_t ldlt_solve_persistent_tail(const double* K, int64_t ld, int N, const double* D, const double* P, double* b,
+                                      double* ybuf, double* xbuf, unsigned* ctrl, int R, hipStream_t st);
 // one sweep (forward: ybuf = L^{-1} b; backward: b = L^{-T} (ybuf / D)); skip
 // (device flag, may be null): return at once when set
 hipError_t ldlt_solve_persistent_sweep(const double* K, int64_t ld, int N, const double* D, const double* P,
@@ -525,6 +573,8 @@ hipError_t qp_init_iterate(const QPBatch& qb, hipStream_t st);
 // converged into scal (the head of Optimizer.cpp:127-135)
 hipError_t qp_evaluate(const QPBatch& qb, hipStream_t st);
 hipError_t qp_assemble(const QPBatch& qb, hipStream_t st);
+// ... in two launches that together write what qp_assemble writes: head = columns < c, else columns >= c
+hipError_t qp_assemble_cols(const QPBatch& qb, int c, bool head, hipStream_t st);
 // predictor / corrector pieces; which: 0 = affine direction, 1 = corrector
 hipError_t qp_rhs(const QPBatch& qb, hipStream_t st);
 hipError_t qp_backsub(const QPBatch& qb, int which, hipStream_t st);

@@ -495,11 +495,14 @@ hipError_t ldlt_factor_batched(double* K, int64_t ld, int N, double* D, double* 
 template <typename T>
 static hipError_t ldlt_factor_t(T* K, int64_t ld, int N, T* D, T* Linv, T* W, int nbo, int nbi, int* info,
                                 hipStream_t st, TrailTimer* timer, hipStream_t st2, hipStream_t st3, hipEvent_t* ev,
-                                int nev, unsigned* pctrl, hipStream_t st4) {
+                                int nev, unsigned* pctrl, hipStream_t st4, FactorHooks* hooks = nullptr) {
   if (N <= 0) return hipSuccess;
   if (nbi != 64 && nbi != 128) return hipErrorInvalidValue;
   if (nbo % nbi != 0 || nbo > IPMZ_NBO_MAX) return hipErrorInvalidValue;
   const int npan = (N + nbo - 1) / nbo;
+  // the caller's work for the idle edges (FactorHooks, kernels.h)
+  const bool hook_b = hooks && hooks->before_b;
+  if (hook_b && ev != nullptr && nev < 5 * npan + 4) return hipErrorInvalidValue;
   const bool fused = pctrl != nullptr && nbi == 64;
   const bool two = st2 != nullptr && ev != nullptr && nev >= 4 * npan + 2 && (!fused || st3 != nullptr);
   // st4 (a fourth, high-priority stream): B's look-ahead strip beside the
@@ -559,6 +562,7 @@ static hipError_t ldlt_factor_t(T* K, int64_t ld, int N, T* D, T* Linv, T* W, in
   };
   hipError_t e = hipSuccess;
   if (!two) {  // single stream: factor, then the whole trailing update
+    if (hook_b && (e = hooks->before_b(st)) != hipSuccess) return e;
     for (int k = 0; k < npan; ++k) {
       const int k0 = k * nbo, bo = pw(k), t0 = k0 + bo;
       if ((e = factor(k, false)) != hipSuccess) return e;
@@ -588,6 +592,14 @@ static hipError_t ldlt_factor_t(T* K, int64_t ld, int N, T* D, T* Linv, T* W, in
   if ((e = stream_record(evEntry, st)) != hipSuccess) return e;
   if ((e = stream_wait(st2, evEntry)) != hipSuccess) return e;
   if (fused && (e = stream_wait(sC, evEntry)) != hipSuccess) return e;
+  // the front edge: the caller's work on B beside the first panel, which
+  // factors with nothing else on the device (B's first update waits for P_0)
+  hipEvent_t evHook = hook_b ? ev[5 * npan + 3] : nullptr;
+  if (hook_b) {
+    IPMZ_TRACE("factor: the caller's work on B before its first update");
+    if ((e = hooks->before_b(st2)) != hipSuccess) return e;
+    if ((e = stream_record(evHook, st2)) != hipSuccess) return e;
+  }
   if ((e = factor(0, false)) != hipSuccess) return e;
   if (fused) {
     if ((e = stream_record(evA[0], st)) != hipSuccess) return e;
@@ -602,6 +614,15 @@ static hipError_t ldlt_factor_t(T* K, int64_t ld, int N, T* D, T* Linv, T* W, in
     if (p1 >= N) break;
     IPMZ_TRACE("factor: panel %d", k);
     if ((e = stream_record(evP[k], st)) != hipSuccess) return e;
+    // the back edge: rows < p1 are final with panel k (early: and its rows
+    // launch on C, which A no longer waits for) -- the caller's work on them
+    if (hooks && hooks->rows_final && !hooks->fired && hooks->final_rows > 0 && p1 >= hooks->final_rows) {
+      if ((e = stream_wait(hooks->final_st, evP[k])) != hipSuccess) return e;
+      if (fused && early_at(k + 1) && (e = stream_wait(hooks->final_st, evC[k])) != hipSuccess) return e;
+      IPMZ_TRACE("factor: rows < %d final with panel %d", p1, k);
+      if ((e = hooks->rows_final(hooks->final_st)) != hipSuccess) return e;
+      hooks->fired = true;
+    }
     // ---- stream B: P_{k+2} columns first, then the rest (four streams: the
     // P_{k+2} strip on st4 after B's previous trailing update, which last
     // touched those columns; B goes straight on with the rest)
@@ -613,6 +634,7 @@ static hipError_t ldlt_factor_t(T* K, int64_t ld, int N, T* D, T* Linv, T* W, in
       if ((e = stream_wait(st4, evP[k])) != hipSuccess) return e;
       if (early_at(k + 1) && (e = stream_wait(st4, evC[k])) != hipSuccess) return e;
       if (k >= 1 && (e = stream_wait(st4, evT[k - 1])) != hipSuccess) return e;
+      if (k == 0 && hook_b && (e = stream_wait(st4, evHook)) != hipSuccess) return e;
     }
     if (p2 < N) {
       if ((e = panel_update(K, ld, N, Wb(k), nbo, k0, bo, p2, p3, false, sN)) != hipSuccess) return e;
@@ -629,6 +651,11 @@ static hipError_t ldlt_factor_t(T* K, int64_t ld, int N, T* D, T* Linv, T* W, in
     }
     if (four && (e = stream_record(evT[k], st2)) != hipSuccess) return e;
     // ---- streams A (and C): update P_{k+1} with P_k, factor P_{k+1}
+    // (their first touch of columns >= nbo: after the caller's work on B)
+    if (k == 0 && hook_b) {
+      if ((e = stream_wait(st, evHook)) != hipSuccess) return e;
+      if (fused && (e = stream_wait(sC, evHook)) != hipSuccess) return e;
+    }
     if (k >= 1) {
       if (!flag_at(k + 1) && (e = stream_wait(st, evN[k - 1])) != hipSuccess) return e;
       if (fused && (e = stream_wait(sC, evN[k - 1])) != hipSuccess) return e;
@@ -675,8 +702,8 @@ static hipError_t ldlt_factor_t(T* K, int64_t ld, int N, T* D, T* Linv, T* W, in
 
 hipError_t ldlt_factor(double* K, int64_t ld, int N, double* D, double* Linv, double* W, int nbo, int nbi,
                        int* info, hipStream_t st, TrailTimer* timer, hipStream_t st2, hipStream_t st3, hipEvent_t* ev,
-                       int nev, unsigned* pctrl, hipStream_t st4) {
-  return ldlt_factor_t<double>(K, ld, N, D, Linv, W, nbo, nbi, info, st, timer, st2, st3, ev, nev, pctrl, st4);
+                       int nev, unsigned* pctrl, hipStream_t st4, FactorHooks* hooks) {
+  return ldlt_factor_t<double>(K, ld, N, D, Linv, W, nbo, nbi, info, st, timer, st2, st3, ev, nev, pctrl, st4, hooks);
 }
 hipError_t ldlt_factor(float* K, int64_t ld, int N, float* D, float* Linv, float* W, int nbo, int nbi, int* info,
                        hipStream_t st, TrailTimer* timer, hipStream_t st2, hipStream_t st3, hipEvent_t* ev, int nev,

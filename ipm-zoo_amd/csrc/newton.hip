@@ -498,43 +498,65 @@ __device__ __forceinline__ double kkt_diag(const QPDev& q, int i) {
 // end of each branch.  (Which of Q / A / C the row copies, its sign and its zeros are decided here and once more in
 // k_fused_pre's copy units: a description shared by both changed k_fused_pre's register allocation, DESIGN.md
 // "One definition per Newton-step formula and loop bound".)
-__device__ __forceinline__ void assemble_row(const QPDev& q, int i, int tid, int nth) {
+__device__ __forceinline__ void assemble_row(const QPDev& q, int i, int tid, int nth, int c0, int c1) {
+  // columns [c0, c1) of the row: the whole row with c0 = 0, c1 = N (qp_assemble_cols: the step's two parts)
   double* __restrict__ K = q.K;
   const int64_t ld = q.ldk;
   const int n = q.n, m = q.m, mk = q.mk;
   double* Kr = K + (int64_t)i * ld;
+  const int je = i < c1 ? i : c1;              // end of the off-diagonal columns written
+  const int jn = n < je ? n : je;              // ... of those copied from A / C
+  const int jz = n > c0 ? n : c0;              // start of the zeros
+  const bool dg = c0 <= i && i < c1;           // the diagonal is among them
   if (i < n) {
     const double* Qr = q.Q + (int64_t)i * q.ldn;
-    for (int j = tid; j < i; j += nth) Kr[j] = Qr[j];
+    for (int j = c0 + tid; j < je; j += nth) Kr[j] = Qr[j];
+    if (!dg) return;
     if (tid == 0) Kr[i] = kkt_diag(q, i);
   } else if (i < n + mk && q.naive) {  // | -A | -(L_g^{-1}*G) | 0 |  and  | A | 0 | -(L_h^{-1}*H) |
     const bool hrow = i >= n + m;
     const int r = hrow ? i - n - m : i - n;
     const double* Ar = q.A + (int64_t)r * q.ldn;
-    for (int j = tid; j < n; j += nth) Kr[j] = hrow ? Ar[j] : -Ar[j];
-    for (int j = n + tid; j < i; j += nth) Kr[j] = 0.0;
+    for (int j = c0 + tid; j < jn; j += nth) Kr[j] = hrow ? Ar[j] : -Ar[j];
+    for (int j = jz + tid; j < je; j += nth) Kr[j] = 0.0;
+    if (!dg) return;
     if (tid == 0) Kr[i] = kkt_diag(q, i);
   } else if (i < n + m) {
     const int r = i - n;
     const double* Ar = q.A + (int64_t)r * q.ldn;
-    for (int j = tid; j < n; j += nth) Kr[j] = Ar[j];
-    for (int j = n + tid; j < i; j += nth) Kr[j] = 0.0;
+    for (int j = c0 + tid; j < jn; j += nth) Kr[j] = Ar[j];
+    for (int j = jz + tid; j < je; j += nth) Kr[j] = 0.0;
+    if (!dg) return;
     if (tid == 0) Kr[i] = kkt_diag(q, i);
   } else {
     const int r = i - n - mk;
     const double* Cr = q.C + (int64_t)r * q.ldn;
-    for (int j = tid; j < n; j += nth) Kr[j] = Cr[j];
-    for (int j = n + tid; j < i; j += nth) Kr[j] = 0.0;
+    for (int j = c0 + tid; j < jn; j += nth) Kr[j] = Cr[j];
+    for (int j = jz + tid; j < je; j += nth) Kr[j] = 0.0;
+    if (!dg) return;
     if (tid == 0) Kr[i] = kkt_diag(q, i);
   }
 }
 
-__global__ __launch_bounds__(NT) void k_assemble(const QPDev* __restrict__ qs) {
-  assemble_row(qs[blockIdx.y], blockIdx.x, threadIdx.x, NT);
+// rows row0 .. of the lower triangle, columns [c0, c1)
+__global__ __launch_bounds__(NT) void k_assemble(const QPDev* __restrict__ qs, int row0, int c0, int c1) {
+  assemble_row(qs[blockIdx.y], row0 + blockIdx.x, threadIdx.x, NT, c0, c1);
 }
 
 hipError_t qp_assemble(const QPBatch& qb, hipStream_t st) {
-  hipLaunchKernelGGL(k_assemble, grid2(qb.h.N, qb.B), dim3(NT), 0, st, qb.d);
+  hipLaunchKernelGGL(k_assemble, grid2(qb.h.N, qb.B), dim3(NT), 0, st, qb.d, 0, 0, qb.h.N);
+  return hipGetLastError();
+}
+// the same matrix in two launches: head = columns < c of every row (with the
+// diagonal of rows < c), else columns >= c (rows >= c, with their diagonal)
+hipError_t qp_assemble_cols(const QPBatch& qb, int c, bool head, hipStream_t st) {
+  const int N = qb.h.N;
+  if (c > N) c = N;
+  if (head) {
+    if (c > 0) hipLaunchKernelGGL(k_assemble, grid2(N, qb.B), dim3(NT), 0, st, qb.d, 0, 0, c);
+  } else if (c < N) {
+    hipLaunchKernelGGL(k_assemble, grid2(N - c, qb.B), dim3(NT), 0, st, qb.d, c, c, N);
+  }
   return hipGetLastError();
 }
 

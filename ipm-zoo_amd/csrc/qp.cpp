@@ -321,7 +321,7 @@ int solve_batch(ipmz_qp* s, hipStream_t st, int which) {
 
 // info_reset: the caller already reset the batched factor's info word
 bool uses_k0(const ipmz_qp* s);
-int factor_batch(ipmz_qp* s, TrailTimer* tt, bool info_reset) {
+int factor_batch(ipmz_qp* s, TrailTimer* tt, bool info_reset, StepEdges* edges = nullptr) {
   hipStream_t st = s->ctx->stream;
   const int nbo = nbo_for(s->ctx, s->N);
   switch (path_of(s)) {
@@ -339,7 +339,7 @@ int factor_batch(ipmz_qp* s, TrailTimer* tt, bool info_reset) {
     case Path::Mixed: return mixed_factor_impl(s->ctx, s->K, s->ldk, s->mw, tt);
     case Path::Normal:
       return normal_factor_impl(s->ctx, s->n, s->m + s->p, s->K, s->ldk, s->D, normal_ws_of(s), nbo, tt);
-    case Path::Ldlt: return factor_impl(s->ctx, s->N, s->K, s->ldk, s->D, ldlt_ws_of(s), nbo, tt);
+    case Path::Ldlt: return factor_impl(s->ctx, s->N, s->K, s->ldk, s->D, ldlt_ws_of(s), nbo, tt, nullptr, edges);
     case Path::LdltBatch: break;
   }
   // (info_reset: the fused step, whose pre phase assembled into K0)
@@ -362,6 +362,27 @@ bool fused_solves(const ipmz_qp* s) {
 // factor (nbi 64) consumes it; otherwise the whole matrix is assembled into K
 bool uses_k0(const ipmz_qp* s) {
   return s->K0 && s->ctx->nbi == 64 && s->N <= IPMZ_SMALL_NMAX && !(debug_inject_mask() & IPMZ_DEBUG_NO_K0);
+}
+
+// The single-QP fp64 augmented LDL^T step whose factor forks onto the
+// look-ahead streams runs its memory-bound neighbours in the factor's two idle
+// edges (DESIGN.md §4 "The factor's idle edges"): the assembly of the columns
+// beyond the first panel beside that panel, and -- the affine right-hand side
+// moved ahead of the factor -- the solve preparation and forward sweep of the
+// rows that are final when the factor turns chain-bound beside its tail.
+// IPMZ_DEBUG_SERIAL_EDGES keeps the serial order (bitwise the same step).
+bool step_edges(const ipmz_qp* s) {
+  const int dbg = debug_inject_mask();
+  if (path_of(s) != Path::Ldlt || (dbg & (IPMZ_DEBUG_SERIAL_EDGES | IPMZ_DEBUG_ONE_STREAM))) return false;
+  const int nbo = nbo_for(s->ctx, s->N);
+  return (s->N + nbo - 1) / nbo >= 3;
+}
+// rows of the early forward sweep (0: none); debug bits 24-29 force them
+int step_edge_rows(const ipmz_qp* s) {
+  if (s->ctx->nbi != 64) return 0;
+  const int v = (debug_inject_mask() & IPMZ_DEBUG_EDGE_ROWS_MASK) >> IPMZ_DEBUG_EDGE_ROWS_SHIFT;
+  const int r = v ? (v - 1) * IPMZ_SOLVE_BLOCK : chain_bound_rows(s->N, nbo_for(s->ctx, s->N));
+  return r >= s->N - IPMZ_SOLVE_BLOCK ? 0 : r;
 }
 
 int run_step(ipmz_qp* s, int flags) {
@@ -409,13 +430,34 @@ int run_step(ipmz_qp* s, int flags) {
   } else {
     if (restart) HIP_OK(qp_restart_if_converged(qb, st));
     mark(0);
-    HIP_OK(qp_assemble(qb, st));
-    mark(1);
-    if ((rc = factor_batch(s, t ? &tt : nullptr, false))) return rc;
+    StepEdges edges;
+    const bool overlap = step_edges(s);
+    if (overlap) {
+      // the head: what the first panel reads; the rest beside it (phase
+      // accounting: inside `factor`), and the affine right-hand side -- from
+      // the residuals, which the factor does not touch -- for the early sweep
+      const int c_head = nbo_for(s->ctx, s->N);
+      HIP_OK(qp_assemble_cols(qb, c_head, true, st));
+      mark(1);
+      HIP_OK(qp_rhs(qb, st));
+      edges.rest = [&qb, c_head](hipStream_t sb) { return qp_assemble_cols(qb, c_head, false, sb); };
+      edges.rows = step_edge_rows(s);
+      edges.b = q0(s).b;
+      IPMZ_TRACE("step: edges, head columns %d, early sweep rows %d", c_head, edges.rows);
+    } else {
+      HIP_OK(qp_assemble(qb, st));
+      mark(1);
+    }
+    if ((rc = factor_batch(s, t ? &tt : nullptr, false, overlap ? &edges : nullptr))) return rc;
     mark(2);
     // predictor (affine scaling) direction
-    HIP_OK(qp_rhs(qb, st));
-    if ((rc = solve_batch(s, st, 0))) return rc;
+    if (!overlap) HIP_OK(qp_rhs(qb, st));
+    if (edges.swept) {
+      IPMZ_TRACE("step: forward sweep from row %d on", edges.rows);
+      HIP_OK(solve_ws_tail(s->K, s->ldk, s->N, s->D, ldlt_ws_of(s), q0(s).b, edges.rows, st));
+    } else if ((rc = solve_batch(s, st, 0))) {
+      return rc;
+    }
     mark(3);
     HIP_OK(qp_backsub(qb, 0, st));
     HIP_OK(qp_ratio(qb, 0, SC_ALPHA_AFF, st));
@@ -1088,6 +1130,30 @@ int ipmz_qp_kkt_dim(ipmz_qp* s) { return s ? s->N : 0; }
 int ipmz_qp_get_kkt(ipmz_qp* s, double* out) {
   if (!s || !out) return fail(IPMZ_ERR_INVALID, "bad arguments");
   return get_kkt_impl(s, 0, out);
+}
+
+int ipmz_qp_get_factor(ipmz_qp* s, double* L, double* D, double* P, int64_t* p_len) {
+  if (!s) return fail(IPMZ_ERR_INVALID, "bad arguments");
+  if (path_of(s) != Path::Ldlt || s->ctx->nbi != 64)
+    return fail(IPMZ_ERR_STATE, "ipmz_qp_get_factor: single QPs on the fp64 augmented LDL^T with nbi = 64");
+  HIP_OK(hipSetDevice(s->ctx->device));
+  hipStream_t st = s->ctx->stream;
+  const int N = s->N;
+  const int64_t q = solve_prep_elems(N) / 4;
+  if (p_len) *p_len = 4 * q;
+  const LdltWs w = ldlt_ws_of(s);
+  if (L) HIP_OK(hipMemcpy2DAsync(L, (size_t)N * 8, s->K, s->ldk * 8, (size_t)N * 8, N, hipMemcpyDeviceToHost, st));
+  if (D) HIP_OK(hipMemcpyAsync(D, s->D, (size_t)N * 8, hipMemcpyDeviceToHost, st));
+  if (P) HIP_OK(hipMemcpyAsync(P, w.P, (size_t)(4 * q) * 8, hipMemcpyDeviceToHost, st));
+  HIP_OK(hipStreamSynchronize(st));
+  if (L)
+    for (int r = 0; r < N; ++r)
+      for (int c = r + 1; c < N; ++c) L[(int64_t)r * N + c] = 0.0;
+  if (P) {  // M of the first block row and Q of the last are never built
+    const int64_t blk = (int64_t)IPMZ_SOLVE_BLOCK * IPMZ_SOLVE_BLOCK;
+    for (int64_t i = 0; i < blk; ++i) P[2 * q + i] = P[4 * q - blk + i] = 0.0;
+  }
+  return IPMZ_OK;
 }
 
 int ipmz_batch_get_kkt(ipmz_qp* s, int index, double* out) {

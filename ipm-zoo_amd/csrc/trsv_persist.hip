@@ -79,7 +79,9 @@ constexpr int RP_ROWS = 4, RP_LANES = 16;  // row phases
 constexpr int CP_ROWS = 8, CP_LANES = 32;  // column phase
 constexpr int XS_LD = SB + 4;              // LDS row stride of the staged X_J
 constexpr int TDS = 65;               // LDS row stride of the prep's 64 x 64 tiles
-enum { SC_TICKET = 2, SC_TICKET_B = 3 };  // ticket words; ctrl[SOLVE_ERR_WORD] (1) is sticky
+// ticket words; ctrl[SOLVE_ERR_WORD] (1) is sticky.  SC_TICKET_F2: the tickets of a forward sweep that starts
+// at a later block row (the tail of a split sweep), zero after solve_reset and after every backward sweep
+enum { SC_TICKET = 2, SC_TICKET_B = 3, SC_TICKET_F2 = 4 };
 
 template <typename T>
 __device__ __forceinline__ bool is_sentinel(T v);
@@ -176,14 +178,18 @@ __device__ __forceinline__ void out4(T* dst, int r0, int c0, const double4_t (&a
 // X_J from the two 64 x 64 inverses (X = [[Xa, 0], [-Xb L_ba Xa, Xb]]);
 // part 0 stores X_J and X_J^T, parts 1-2 the column halves of M_J, parts 3-4
 // those of Q_J (fp64 MFMA, stored as T).  A part's two L operands are loaded
-// with the X operands.  Rows / columns past N are zero.
+// with the X operands.  Rows / columns past N are zero.  Block rows: J =
+// jbase + blockIdx.x; X_J / M_J are built for jx0 <= J < jx1, Q_J for jq0 <=
+// J < jq1 (solve_prep_split; the whole preparation: both [0, nb)).
 template <typename T>
 __global__ __launch_bounds__(256) void solve_prep_kernel(const T* __restrict__ K, int64_t ld, int N,
                                                          const T* __restrict__ Linv, T* __restrict__ X,
                                                          T* __restrict__ XT, T* __restrict__ M, T* __restrict__ Q,
-                                                         int nb) {
+                                                         int nb, int jbase, int jx0, int jx1, int jq0,
+                                                         int jq1) {
   __shared__ double S[4][64 * TDS];  // 133 KB: Xa, Xb, X21, one L operand
-  const int J = blockIdx.x, part = blockIdx.y, J0 = J * SB;
+  const int J = jbase + blockIdx.x, part = blockIdx.y, J0 = J * SB;
+  if (part <= 2 ? (J < jx0 || J >= jx1) : (J < jq0 || J >= jq1)) return;
   if ((part == 1 || part == 2) && J == 0) return;
   if (part >= 3 && J + 1 >= nb) return;
   const int h = (part - 1) & 1;
@@ -276,7 +282,7 @@ __global__ __launch_bounds__(SNT) void trsv128_kernel(const T* __restrict__ K, i
                                                       const T* __restrict__ XT, const T* __restrict__ M,
                                                       const T* __restrict__ Q, T* b, T* ybuf, T* xbuf,
                                                       unsigned* ctrl, int nb, const unsigned* __restrict__ skip,
-                                                      int inject) {
+                                                      int inject, int nbv, int jfirst) {
   typedef typename Mfma<T>::vec2_t V2;
   constexpr int RW = SB / H;        // rows / columns a part owns
   constexpr int RPR = RP_ROWS / H;  // row phases: rows per thread
@@ -295,9 +301,10 @@ __global__ __launch_bounds__(SNT) void trsv128_kernel(const T* __restrict__ K, i
   __shared__ unsigned sh_ticket, sh_stop, sh_nr[2];
   unsigned* err = ctrl + SOLVE_ERR_WORD;
   // the parts' exchange vectors (v slices forward, u slices backward) follow
-  // the block vectors in the same ranges
-  T* const vbuf = ybuf + (int64_t)nb * SB;
-  T* const ubuf = xbuf + (int64_t)nb * SB;
+  // the block vectors in the same ranges (nbv block rows: those of the whole
+  // system, also when this sweep covers its leading nb only)
+  T* const vbuf = ybuf + (int64_t)nbv * SB;
+  T* const ubuf = xbuf + (int64_t)nbv * SB;
   const int tid = threadIdx.x;
   const int rg = tid / RP_LANES, cg = tid % RP_LANES;  // row phases
   if (tid == 0) sh_nr[0] = sh_nr[1] = 0u;
@@ -395,13 +402,18 @@ __global__ __launch_bounds__(SNT) void trsv128_kernel(const T* __restrict__ K, i
 
   for (;;) {
     lds_sync();
-    if (tid == 0) sh_ticket = atomicAdd(&ctrl[BWD ? SC_TICKET_B : SC_TICKET], 1u);
+    // (a forward sweep from block row jfirst > 0 on: its own counter, tickets
+    // from that block's first; the rows before it are complete -- stream order)
+    if (tid == 0) sh_ticket = atomicAdd(&ctrl[BWD ? SC_TICKET_B : jfirst ? SC_TICKET_F2 : SC_TICKET], 1u);
     lds_sync();
-    const int ticket = (int)sh_ticket;
+    const int ticket = (int)sh_ticket + (BWD ? 0 : jfirst * H);
     if (ticket >= nb * H) return;
     // the other sweep's ticket counter, for the next launch of that sweep
     // (the previous one has completed: stream order)
-    if (ticket == 0 && tid == 0) st_sc1(&ctrl[BWD ? SC_TICKET : SC_TICKET_B], 0u);
+    if (ticket == 0 && tid == 0) {
+      st_sc1(&ctrl[BWD ? SC_TICKET : SC_TICKET_B], 0u);
+      if (BWD) st_sc1(&ctrl[SC_TICKET_F2], 0u);
+    }
 
     if constexpr (!BWD) {
       // ============================================================ forward
@@ -678,14 +690,27 @@ int64_t solve_prep_elems(int N) {
   return 4 * nb * SB * SB;
 }
 
+// block rows [jx0, jx1) of X / M and [jq0, jq1) of Q
 template <typename T>
-static hipError_t solve_prep_t(const T* K, int64_t ld, int N, const T* Linv, T* P, hipStream_t st) {
+static hipError_t solve_prep_t(const T* K, int64_t ld, int N, const T* Linv, T* P, hipStream_t st, int jx0 = 0,
+                               int jx1 = 1 << 30, int jq0 = 0, int jq1 = 1 << 30) {
   if (N <= 0) return hipSuccess;
   const int nb = (N + SB - 1) / SB;
   const int64_t q = (int64_t)nb * SB * SB;
-  hipLaunchKernelGGL(solve_prep_kernel<T>, dim3(nb, 5), dim3(256), 0, st, K, ld, N, Linv, P, P + q, P + 2 * q,
-                     P + 3 * q, nb);
+  jx1 = jx1 < nb ? jx1 : nb;
+  jq1 = jq1 < nb ? jq1 : nb;
+  const int lo = jx0 < jq0 ? jx0 : jq0, hi = jx1 > jq1 ? jx1 : jq1;
+  if (hi <= lo) return hipSuccess;
+  hipLaunchKernelGGL(solve_prep_kernel<T>, dim3(hi - lo, 5), dim3(256), 0, st, K, ld, N, Linv, P, P + q, P + 2 * q,
+                     P + 3 * q, nb, lo, jx0, jx1, jq0, jq1);
   return hipGetLastError();
+}
+hipError_t solve_prep_split(const double* K, int64_t ld, int N, const double* Linv, double* P, int R, bool head,
+                            hipStream_t st) {
+  if (R <= 0 || R >= N || R % SB) return hipErrorInvalidValue;
+  const int j = R / SB;  // Q_{j-1} reads L_{j,j-1}: rows >= R
+  return head ? solve_prep_t<double>(K, ld, N, Linv, P, st, 0, j, 0, j - 1)
+              : solve_prep_t<double>(K, ld, N, Linv, P, st, j, 1 << 30, j - 1, 1 << 30);
 }
 hipError_t solve_stamps(unsigned long long* out) {  // DEBUG
   return hipMemcpyFromSymbol(out, HIP_SYMBOL(g_sstamp), sizeof(unsigned long long) * 2 * 256 * 6);
@@ -718,35 +743,45 @@ static int solve_parts(int N) {
   return N <= 12288 ? 4 : 2;
 }
 
+// a forward sweep's range of block rows: the leading `lead` rows only (a
+// multiple of 128, < N; 0 = all), or from block row `first` on
+struct SweepRange {
+  int lead = 0, first = 0;
+};
 // one sweep's launch.  No workgroup waits for one that has not started (the
 // tickets), so the grid is only capped by what could be resident: 256 CUs, a
 // part's LDS (mostly its RW rows of X_J) and its threads of the CU's 2048
 template <typename T, bool BWD, int H>
 static hipError_t launch_sweep(const T* K, int64_t ld, int N, const T* D, const T* P, T* b, T* ybuf, T* xbuf,
-                               unsigned* ctrl, hipStream_t st, const unsigned* skip) {
-  const int nb = (N + SB - 1) / SB;
-  const int64_t q = (int64_t)nb * SB * SB;
+                               unsigned* ctrl, hipStream_t st, const unsigned* skip, const SweepRange& sr) {
+  // (a forward sweep over the leading rows only: N and nb are those rows',
+  // the operators and the exchange vectors lie as the whole system's do)
+  const int nb = ((sr.lead ? sr.lead : N) + SB - 1) / SB, nbv = (N + SB - 1) / SB;
+  const int64_t q = (int64_t)nbv * SB * SB;
+  if (sr.lead) N = sr.lead;
   constexpr int RW = SB / H;
   constexpr int64_t lds = (int64_t)sizeof(T) * (RW * XS_LD + (SB / CP_ROWS) * RW + 3 * SB + RW) + 64;
   constexpr int by_threads = 2048 / SNT;
   constexpr int per_cu = 160 * 1024 / lds < by_threads ? (int)(160 * 1024 / lds) : by_threads;
   static_assert(per_cu >= 1, "a part's LDS fits a CU");
-  const int tickets = nb * H, cap = 256 * per_cu;
+  const int tickets = (nb - sr.first) * H, cap = 256 * per_cu;
   const int grid = tickets < cap ? tickets : cap;
   const int inject = debug_inject_mask() & IPMZ_INJECT_SOLVE;
   hipLaunchKernelGGL((trsv128_kernel<T, BWD, H>), dim3(grid), dim3(SNT), 0, st, K, ld, N, D, P, P + q, P + 2 * q,
-                     P + 3 * q, b, ybuf, xbuf, ctrl, nb, skip, inject);
+                     P + 3 * q, b, ybuf, xbuf, ctrl, nb, skip, inject, nbv, sr.first);
   return hipGetLastError();
 }
 template <typename T, bool BWD>
 static hipError_t sweep_t(const T* K, int64_t ld, int N, const T* D, const T* P, T* b, T* ybuf, T* xbuf,
-                          unsigned* ctrl, hipStream_t st, const unsigned* skip) {
+                          unsigned* ctrl, hipStream_t st, const unsigned* skip, const SweepRange& sr = SweepRange()) {
   if (N <= 0) return hipSuccess;
   if (ld % 2) return hipErrorInvalidValue;  // 2-element vector loads of the tiles
-  switch (solve_parts<T>(N)) {
-    case 4: return launch_sweep<T, BWD, 4>(K, ld, N, D, P, b, ybuf, xbuf, ctrl, st, skip);
-    case 2: return launch_sweep<T, BWD, 2>(K, ld, N, D, P, b, ybuf, xbuf, ctrl, st, skip);
-    default: return launch_sweep<T, BWD, 1>(K, ld, N, D, P, b, ybuf, xbuf, ctrl, st, skip);
+  if (BWD && (sr.lead || sr.first)) return hipErrorInvalidValue;
+  if (sr.lead % SB || sr.lead >= N || (sr.lead && sr.first) || sr.first * SB >= N) return hipErrorInvalidValue;
+  switch (solve_parts<T>(N)) {  // of the whole system, whatever the range
+    case 4: return launch_sweep<T, BWD, 4>(K, ld, N, D, P, b, ybuf, xbuf, ctrl, st, skip, sr);
+    case 2: return launch_sweep<T, BWD, 2>(K, ld, N, D, P, b, ybuf, xbuf, ctrl, st, skip, sr);
+    default: return launch_sweep<T, BWD, 1>(K, ld, N, D, P, b, ybuf, xbuf, ctrl, st, skip, sr);
   }
 }
 
@@ -762,6 +797,22 @@ static hipError_t solve_persistent_t(const T* K, int64_t ld, int N, const T* D, 
   const hipError_t e = sweep_t<T, false>(K, ld, N, D, P, b, ybuf, xbuf, ctrl, st, skip);
   if (e != hipSuccess) return e;
   return sweep_t<T, true>(K, ld, N, D, P, b, ybuf, xbuf, ctrl, st, skip);
+}
+
+hipError_t ldlt_solve_persistent_head(const double* K, int64_t ld, int N, const double* D, const double* P,
+                                      const double* b, double* ybuf, double* xbuf, unsigned* ctrl, int R,
+                                      hipStream_t st) {
+  if (R <= 0) return hipErrorInvalidValue;
+  // (the forward sweep only reads b)
+  return sweep_t<double, false>(K, ld, N, D, P, const_cast<double*>(b), ybuf, xbuf, ctrl, st, nullptr,
+                                SweepRange{R, 0});
+}
+hipError_t ldlt_solve_persistent_tail(const double* K, int64_t ld, int N, const double* D, const double* P, double* b,
+                                      double* ybuf, double* xbuf, unsigned* ctrl, int R, hipStream_t st) {
+  if (R <= 0 || R % SB) return hipErrorInvalidValue;
+  const hipError_t e = sweep_t<double, false>(K, ld, N, D, P, b, ybuf, xbuf, ctrl, st, nullptr, SweepRange{0, R / SB});
+  if (e != hipSuccess) return e;
+  return sweep_t<double, true>(K, ld, N, D, P, b, ybuf, xbuf, ctrl, st, nullptr);
 }
 
 // one sweep of the persistent solve (forward: y = L^{-1} b into ybuf;

@@ -57,7 +57,7 @@ EXPORTS = [
     "ipmz_qp_newton_solve_multi", "ipmz_batch_newton_solve_multi",
     "ipmz_qp_newton_adjoint_multi", "ipmz_batch_newton_adjoint_multi",
     "ipmz_batch_load_device", "ipmz_batch_copy_state", "ipmz_batch_data_vjp", "ipmz_batch_data_jvp",
-    "ipmz_batch_data_vjp_multi", "ipmz_batch_set_state_device",
+    "ipmz_batch_data_vjp_multi", "ipmz_batch_set_state_device", "ipmz_qp_get_factor",
 ]
 SOLVE_MULTI_PANEL = 256  # include/ipmz.h IPMZ_SOLVE_MULTI_PANEL: column panel of the blocked multi-rhs solve
 REDUCTION_AUGMENTED, REDUCTION_NORMAL = 0, 1
@@ -211,6 +211,7 @@ def _load():
         "ipmz_qp_set_state": ([_VP, _P], _I),
         "ipmz_qp_get_kkt": ([_VP, _P], _I),
         "ipmz_qp_kkt_dim": ([_VP], _I),
+        "ipmz_qp_get_factor": ([_VP, _P, _P, _P, ctypes.POINTER(_I64)], _I),
         "ipmz_qp_set_timing": ([_VP, _I], _I),
         "ipmz_qp_phase_times": ([_VP, _P, _P, ctypes.POINTER(_I64)], _I),
         "ipmz_batch_create": ([_VP, ctypes.POINTER(_QPConfig), _I, ctypes.POINTER(_VP)], _I),
@@ -467,6 +468,15 @@ def debug_inject(mask):
 
 
 INJECT_SOLVE, INJECT_PANEL, INJECT_GRAPH_FORKS = 1, 2, 4
+# csrc/kernels.h: the forked single-QP step in its serial order (no work in the factor's idle edges)
+DEBUG_SERIAL_EDGES = 8388608
+
+
+def debug_edge_rows(rows):
+    """Debug-mask bits that make the forked step's early forward sweep cover `rows` rows (a multiple
+    of 128 up to 62 * 128; 0 and anything from N - 128 on: no early sweep)."""
+    assert rows % 128 == 0 and 0 <= rows // 128 <= 62
+    return (rows // 128 + 1) << 24
 
 _default_ctx = None
 
@@ -944,6 +954,15 @@ class Optimizer:
         K = np.zeros((self.N, self.N))
         _check(lib.ipmz_qp_get_kkt(self.h, _dp(K)), "ipmz_qp_get_kkt")
         return K
+
+    def factor(self):
+        """(L, D, P) the last step's factor left: the lower triangle as stored, the pivots and the
+        persistent solve's prepared operators (ipmz_qp_get_factor; parity tests)."""
+        n = _I64(0)
+        _check(lib.ipmz_qp_get_factor(self.h, None, None, None, ctypes.byref(n)), "ipmz_qp_get_factor")
+        L, D, P = np.zeros((self.N, self.N)), np.zeros(self.N), np.zeros(n.value)
+        _check(lib.ipmz_qp_get_factor(self.h, _dp(L), _dp(D), _dp(P), ctypes.byref(n)), "ipmz_qp_get_factor")
+        return L, D, P
 
     def kkt_solve(self, B_ptr, nrhs, ldb):
         """Every row of B (device, nrhs rows in Newton order, stride ldb) <-
