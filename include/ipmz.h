@@ -48,6 +48,12 @@
  *                               <- no reference counterpart: the iterate of a whole batch
  *                                  set from such rows in device memory (a warm start),
  *                                  pushed into the interior and checked by kernels
+ *   ipmz_batch_solve_ex, ipmz_batch_can_skip_converged
+ *                               <- the loop of Optimizer::solve_quasi_definite_ for a whole
+ *                                  batch with the reference's per-QP stop (Optimizer.cpp:
+ *                                  133-135) kept on the device: a converged QP takes no part
+ *                                  in any launch of a step (IPMZ_STEP_SKIP_CONVERGED), and
+ *                                  the host looks at the device every few steps only
  *   ipmz_qp_create + ipmz_qp_load_host
  *                               <- NumericalOptimization::build_environment
  *                                  (EnvironmentBuilder.h:19-20, EnvironmentBuilder.cpp:7-76)
@@ -140,6 +146,7 @@ enum ipmz_scalar {
   IPMZ_SC_IR_ITERS_AFF, /*   refinement corrections, affine solve             */
   IPMZ_SC_IR_RATIO,     /*   the same for the corrector solve                 */
   IPMZ_SC_IR_ITERS,
+  IPMZ_SC_STEPS = 14,   /* steps with IPMZ_STEP_SKIP_CONVERGED this QP took part in */
   IPMZ_SC_COUNT = 16
 };
 
@@ -460,6 +467,34 @@ int ipmz_qp_generate(ipmz_qp* qp, uint64_t seed);
 #define IPMZ_STEP_GRAPH 2                /* capture once into a hipGraph, then replay (steps whose
                                             factor forks onto the look-ahead streams -- >= 3 outer
                                             panels -- are enqueued eagerly instead) */
+/* IPMZ_STEP_SKIP_CONVERGED: a QP of a batch whose IPMZ_SC_CONVERGED is non-zero
+ * when the step starts takes no part in it.  Its iterate, residuals, both
+ * direction blocks (IPMZ_STATE_DAFF, IPMZ_STATE_DIR), its right-hand-side slot
+ * and its whole scalar block keep their bits -- those of the step that
+ * converged it; its factor is the one of that step's matrix.  Every other QP
+ * gets bitwise the step it gets without the flag: the kernels, chosen by N,
+ * the inner block and the batch size, are the same; a skipped QP's workgroups
+ * return at the top of every launch, on the device, and the CUs they would
+ * have held go to the QPs still working.  The batched factor's info word is
+ * then the minimum over the QPs that were factored.  The step adds 1.0 to
+ * IPMZ_SC_STEPS of every QP it does not skip; no other step touches that slot,
+ * which restarts at 0 with the scalar block (a load, ipmz_batch_initialize,
+ * ipmz_qp_generate; not ipmz_batch_set_state*): after a solve it is the QP's
+ * own iteration count.
+ *   Served: batches (batch > 1) of small systems, N <= 1024, with inner block
+ *     64 -- every LDL^T formulation, whatever ipmz_batch_set_factor_kernel
+ *     selects, and IPMZ_EQ_NONE batches; with IPMZ_STEP_GRAPH, and enqueued
+ *     into a caller's capture, like any other flag set.
+ *   Refused with IPMZ_ERR_INVALID before anything is enqueued (and before the
+ *     check for a load): a solver of one QP (ipmz_qp_solve stops at
+ *     convergence already), N > 1024 and inner block 128 (their factor is not
+ *     per QP), and the flag together with IPMZ_STEP_RESTART_IF_CONVERGED.
+ *     ipmz_batch_can_skip_converged answers for the solver as configured.
+ *   Never skipping: the calls that reuse the step's assembly and factor --
+ *     ipmz_*_kkt_solve*, ipmz_*_newton_solve_multi, ipmz_*_newton_adjoint_multi
+ *     -- factor every QP, converged or not (the backward pass needs exactly
+ *     the factor of converged QPs). */
+#define IPMZ_STEP_SKIP_CONVERGED 4
 int ipmz_qp_step(ipmz_qp* qp, int flags);
 /* 1 when the last ipmz_qp_step replayed a captured hipGraph, 0 when its
  * launches were enqueued one by one (what a benchmark reports it timed). */
@@ -691,6 +726,24 @@ int ipmz_batch_copy_scalars(ipmz_qp* qp, double* dst_device);
 int ipmz_batch_summary(ipmz_qp* qp, double* dst_device);
 /* Step until every QP converged (converged QPs keep their iterate). */
 int ipmz_batch_solve(ipmz_qp* qp, int max_iter, int* iterations, int* converged_count);
+/* 1 when ipmz_qp_step serves IPMZ_STEP_SKIP_CONVERGED for this solver under
+ * the context's current blocking, else 0 (also for a null qp). */
+int ipmz_batch_can_skip_converged(ipmz_qp* qp);
+/* ipmz_batch_solve with the steps' flags and a host that looks at the device
+ * only every check_every steps.  step_flags: 0, IPMZ_STEP_SKIP_CONVERGED,
+ * IPMZ_STEP_GRAPH or both.  Between two looks the call enqueues check_every
+ * steps (>= 1), never going beyond max_iter; a look is ipmz_batch_summary's
+ * kernel and a copy of its 3 doubles, not of batch * IPMZ_SC_COUNT.
+ * iterations (host, may be NULL): the steps enqueued, at most ipmz_batch_solve's
+ * count rounded up to a multiple of check_every; with the skip flag each QP's
+ * own count is its IPMZ_SC_STEPS whatever check_every was.  converged_count:
+ * host, may be NULL.  check_every 1 and step_flags 0 give the iterates and
+ * both counts of ipmz_batch_solve.  IPMZ_ERR_INVALID: a null qp, max_iter < 0,
+ * check_every < 1, any other flag, or the skip flag where ipmz_qp_step refuses
+ * it; then IPMZ_ERR_STATE before a load, between a load and
+ * ipmz_batch_initialize, or while the context's stream is capturing. */
+int ipmz_batch_solve_ex(ipmz_qp* qp, int max_iter, int step_flags, int check_every, int* iterations,
+                        int* converged_count);
 /* Which kernel factors a batch of small systems (N <= 1024, 64-column
  * blocks, one LDL^T): IPMZ_BATCH_FACTOR_AUTO (default: the wave-specialized
  * left-looking kernel for 64 < N <= 320; above that two workgroups per QP

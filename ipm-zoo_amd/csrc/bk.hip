@@ -77,7 +77,8 @@ __device__ double block_sum(double v, double* sv) {
 
 __global__ __launch_bounds__(BKT) void k_bk_factor(double* __restrict__ Ab, int64_t ld, int n, int64_t sA,
                                                    int* __restrict__ ipivb, int64_t sP, int* __restrict__ infob,
-                                                   int fix_kp) {
+                                                   int fix_kp, SkipGate gate) {
+  if (gate.skips(blockIdx.x)) return;  // (kernels.h SkipGate)
   extern __shared__ double col[];  // the two pivot columns, unscaled: col[i], col[n + i]
   __shared__ double sv[BKW];
   __shared__ int si[BKW];
@@ -324,8 +325,9 @@ __device__ __forceinline__ void bk_solve_body(const double* __restrict__ L, int6
 template <bool TRANS>
 __global__ __launch_bounds__(BKT) void k_bk_solve(const double* __restrict__ Lb, int64_t ld, int n, int64_t sA,
                                                   const int* __restrict__ ipivb, int64_t sP, double* __restrict__ bb,
-                                                  int64_t sb, const unsigned* gate) {
+                                                  int64_t sb, const unsigned* gate, SkipGate skip) {
   if (gate && *gate == 0u) return;
+  if (skip.skips(blockIdx.x)) return;
   bk_solve_body<TRANS>(Lb + blockIdx.x * sA, ld, n, ipivb + blockIdx.x * sP, bb + blockIdx.x * sb);
 }
 
@@ -782,18 +784,18 @@ const unsigned* bk_grid_err_word(const void* ws, int n) {
 }
 
 hipError_t bk_factor(double* A, int64_t ld, int n, int* ipiv, int* info, int fix_kp, int batch, int64_t sA,
-                     int64_t sP, hipStream_t st) {
+                     int64_t sP, hipStream_t st, const SkipGate& skip) {
   if (n <= 0) return hipSuccess;
   if (n > IPMZ_BK_NMAX) return hipErrorInvalidValue;
   const size_t lds = 2 * (size_t)n * sizeof(double);  // <= 64 KB
-  hipLaunchKernelGGL(k_bk_factor, dim3(batch), dim3(BKT), lds, st, A, ld, n, sA, ipiv, sP, info, fix_kp);
+  hipLaunchKernelGGL(k_bk_factor, dim3(batch), dim3(BKT), lds, st, A, ld, n, sA, ipiv, sP, info, fix_kp, skip);
   return hipGetLastError();
 }
 
 hipError_t bk_solve(const double* F, int64_t ld, int n, const int* ipiv, double* b, int batch, int64_t sA, int64_t sP,
-                    int64_t sb, hipStream_t st) {
+                    int64_t sb, hipStream_t st, const SkipGate& skip) {
   if (n <= 0) return hipSuccess;
-  hipLaunchKernelGGL(k_bk_solve<false>, dim3(batch), dim3(BKT), 0, st, F, ld, n, sA, ipiv, sP, b, sb, nullptr);
+  hipLaunchKernelGGL(k_bk_solve<false>, dim3(batch), dim3(BKT), 0, st, F, ld, n, sA, ipiv, sP, b, sb, nullptr, skip);
   return hipGetLastError();
 }
 
@@ -1225,7 +1227,7 @@ hipError_t bk_fast_scatter(double* b, int n, void* meta, hipStream_t st) {
 }
 hipError_t bk_fast_fallback(const double* LT, int n, const int* ipiv, double* b, const void* meta, hipStream_t st) {
   hipLaunchKernelGGL(k_bk_solve<true>, dim3(1), dim3(BKT), 0, st, LT, (int64_t)n, n, 0, ipiv, 0, b, 0,
-                     bk_fast_flag(meta));
+                     bk_fast_flag(meta), SkipGate());
   return hipGetLastError();
 }
 
@@ -1259,7 +1261,7 @@ hipError_t bk_multi_dsolve(double* B, int64_t ldb, int nrhs, int n, void* meta, 
 hipError_t bk_multi_fallback(const double* LT, int n, const int* ipiv, double* B, int64_t ldb, int nrhs,
                              const void* meta, hipStream_t st) {
   hipLaunchKernelGGL(k_bk_solve<true>, dim3(nrhs), dim3(BKT), 0, st, LT, (int64_t)n, n, 0, ipiv, 0, B, ldb,
-                     bk_fast_flag(meta));
+                     bk_fast_flag(meta), SkipGate());
   return hipGetLastError();
 }
 BkFusedMeta bk_fused_meta(const void* meta, int n, const BkBatch& bb) {

@@ -98,6 +98,17 @@ struct Carver {
   }
 };
 
+// IPMZ_STEP_SKIP_CONVERGED (ipmz.h): the convergence words of a batch as the
+// per-QP kernels outside newton.hip take them -- QP 0's SC_CONVERGED and the
+// elements between two QPs' scalar blocks; conv == nullptr: nobody skips.  A
+// kernel asks skips(its QP) first of all and returns when it holds: the word
+// was written by an earlier launch, so every workgroup of a QP reads the same.
+struct SkipGate {
+  const double* conv = nullptr;
+  int64_t sScal = 0;
+  __device__ __forceinline__ bool skips(int64_t qp) const { return conv && conv[qp * sScal] != 0.0; }
+};
+
 // ldlt.hip -------------------------------------------------------------------
 // Batched factorization: element strides between consecutive QPs' K, D,
 // L^{-1} blocks and W panels.
@@ -114,6 +125,9 @@ struct BatchStrides {
   const double* K0 = nullptr;
   // small batched factor: IPMZ_BATCH_FACTOR_* (ipmz.h)
   int small_kernel = 0;
+  // small batched factor: the QPs that take no part (their K, D, L^{-1} keep
+  // their bits; info is then the minimum over the QPs that were factored)
+  SkipGate skip;
 };
 #define IPMZ_PAIR_FLAGS 32  // per QP: LW[16], DONE[16] (N <= IPMZ_SMALL_NMAX)
 // the batched factor of order N runs two workgroups per QP (given flags)
@@ -259,8 +273,10 @@ hipError_t ldlt_solve_fused(const double* K, int64_t ld, int N, const double* D,
                             double* B, int64_t ldb, int nrhs, hipStream_t st, const TrsmBatch& tb = TrsmBatch());
 
 // one workgroup per QP of a batch (small N); b: batch of rhs, stride sb
+// skip: the QPs whose b keeps its bits
 hipError_t ldlt_solve_batched(const double* K, int64_t ld, int N, const double* D, const double* Linv, int nbi,
-                              double* b, int B, int64_t sK, int64_t sD, int64_t sL, int64_t sb, hipStream_t st);
+                              double* b, int B, int64_t sK, int64_t sD, int64_t sL, int64_t sb, hipStream_t st,
+                              const SkipGate& skip = SkipGate());
 
 // trsv_persist.hip: the same solve as ONE persistent launch on 128-row
 // blocks (nbi == 64 factors).  P: solve_prep_elems(N) elements written by
@@ -368,10 +384,11 @@ hipError_t ne_check_sign(const double* D, int N, int offset, double sign, int* i
 #ifndef IPMZ_BK_NMAX  // (include/ipmz.h publishes the same limit for the batch entry points)
 #define IPMZ_BK_NMAX 4096
 #endif
+// skip: the systems of the batch that take no part (factor, pivots, info word and b keep their bits)
 hipError_t bk_factor(double* A, int64_t ld, int n, int* ipiv, int* info, int fix_kp, int batch, int64_t sA,
-                     int64_t sP, hipStream_t st);
+                     int64_t sP, hipStream_t st, const SkipGate& skip = SkipGate());
 hipError_t bk_solve(const double* F, int64_t ld, int n, const int* ipiv, double* b, int batch, int64_t sA, int64_t sP,
-                    int64_t sb, hipStream_t st);
+                    int64_t sb, hipStream_t st, const SkipGate& skip = SkipGate());
 // the whole-device factor of ONE matrix (any n; one workgroup per CU, a grid
 // barrier per step): workspace bytes, launch, and its sticky error word
 // (nonzero after a barrier spin timed out -- the factor is then invalid)
@@ -471,6 +488,7 @@ enum Scalar {
   SC_CONVERGED,
   SC_MU_NEW,
   SC_RESTARTS,
+  SC_STEPS = 14,  // IPMZ_SC_STEPS: the steps with IPMZ_STEP_SKIP_CONVERGED this QP took part in
   SC_COUNT = 16
 };
 
@@ -561,10 +579,14 @@ __host__ __device__ __forceinline__ bool explicit_bounds(const QPDev& q) { retur
 
 // A batch of QPs with identical (n, m, p): d = device array of B
 // descriptors (kernels index it with blockIdx.y), h = host copy of QP 0.
+// skip != 0 (a copy of the batch made for one step with IPMZ_STEP_SKIP_CONVERGED): in the fused per-QP phases below
+// a QP whose SC_CONVERGED is set returns at the top of the kernel -- before any barrier, LDS use or arrival counter
+// -- and keeps every bit; the pre phase counts the others' SC_STEPS
 struct QPBatch {
   const QPDev* d;
   QPDev h;
   int B;
+  int skip = 0;
 };
 
 hipError_t qp_generate(const QPBatch& qb, uint64_t seed0, hipStream_t st);  // QP b: seed0 + b

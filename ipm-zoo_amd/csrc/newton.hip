@@ -1508,12 +1508,20 @@ constexpr int FT = 512;  // 8 waves
 // the rhs (which read the iterate) in that order.
 // kmode (kernels.h KMODE_*): where the matrix goes -- K whole, or the kept
 // K0 (its off-diagonal part once per data load, its diagonal every step)
-__global__ __launch_bounds__(FT) void k_fused_pre(const QPDev* __restrict__ qs, int restart, int* info, int kmode) {
+// skip (IPMZ_STEP_SKIP_CONVERGED): a converged QP's workgroups return here,
+// after QP 0's lead has done its work for the whole batch; the lead of every
+// other QP counts the step in SC_STEPS
+__global__ __launch_bounds__(FT) void k_fused_pre(const QPDev* __restrict__ qs, int restart, int* info, int kmode,
+                                                  int skip) {
   const QPDev& q = qs[blockIdx.y];
   const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
   const bool lead = blockIdx.x == 0 && kmode != KMODE_K0_OFFDIAG;
   double* const KT = kmode == KMODE_K ? q.K : q.K0;
   if (info && lead && blockIdx.y == 0 && tid == 0) *info = 0x7f7f7f7f;  // the factor's first-failure word
+  if (skip) {
+    if (q.scal[SC_CONVERGED] != 0.0) return;
+    if (lead && tid == 0) q.scal[SC_STEPS] += 1.0;
+  }
   if (lead && restart && q.scal[SC_CONVERGED] != 0.0) {
     for (int64_t t = tid; t < q.state_len; t += FT) restart_elem(q, t);
     __syncthreads();  // every thread has read SC_CONVERGED
@@ -1587,8 +1595,9 @@ __device__ __forceinline__ void fused_mid_body(const QPDev& q, double* sh) {
   if (tid == 0) centering_store(q, c);
   for (int t = tid; t < N; t += T) rhs_elem(q, t);
 }
-__global__ __launch_bounds__(FT) void k_fused_mid(const QPDev* __restrict__ qs) {
+__global__ __launch_bounds__(FT) void k_fused_mid(const QPDev* __restrict__ qs, int skip) {
   __shared__ double sh[FT / 64];
+  if (skip && qs[blockIdx.x].scal[SC_CONVERGED] != 0.0) return;
   fused_mid_body<FT>(qs[blockIdx.x], sh);
 }
 
@@ -1610,8 +1619,9 @@ __device__ __forceinline__ void fused_post_body(const QPDev& q, int freeze, doub
     for (int t = tid; t < mx; t += T) update_elem(q, t, 0.995 * a);
   }
 }
-__global__ __launch_bounds__(FT) void k_fused_post(const QPDev* __restrict__ qs, int freeze) {
+__global__ __launch_bounds__(FT) void k_fused_post(const QPDev* __restrict__ qs, int freeze, int skip) {
   __shared__ double sh[FT / 64];
+  if (skip && qs[blockIdx.x].scal[SC_CONVERGED] != 0.0) return;
   fused_post_body<FT>(qs[blockIdx.x], freeze, sh);
 }
 
@@ -1631,13 +1641,14 @@ __global__ __launch_bounds__(64 * NW) __attribute__((amdgpu_waves_per_eu(NW == 8
                                                           int64_t ld, int N, const double* D,
                                                           const double* __restrict__ Linv, double* b,
                                                           int64_t sK, int64_t sD, int64_t sL, int64_t sb,
-                                                          int freeze) {
+                                                          int freeze, int skip) {
   // (b and D without __restrict__: the middle and post phases reach the
   // same vectors through qs[i].b / the QP's D as well)
   extern __shared__ __attribute__((aligned(16))) double sm[];
   __shared__ double sh[NW];
   const int64_t i = blockIdx.x;
   const QPDev& q = qs[i];
+  if (skip && q.scal[SC_CONVERGED] != 0.0) return;
   K += i * sK;
   D += i * sD;
   Linv += i * sL;
@@ -1655,8 +1666,13 @@ __global__ __launch_bounds__(64 * NW) __attribute__((amdgpu_waves_per_eu(NW == 8
 // then residuals, f, res, mu): gridDim.x workgroups per QP (blockIdx.y)
 // share the matvec rows and transpose columns; the last to arrive (counter
 // q.done, reset by it) runs the residual pass and the stats.
-__global__ __launch_bounds__(FT) __attribute__((amdgpu_waves_per_eu(8))) void k_fused_eval(const QPDev* __restrict__ qs) {
+// skip: a converged QP's workgroups return before they arrive at q.done (the
+// flag is this kernel's own output: written by the last workgroup to arrive,
+// after every workgroup of the QP has read it here)
+__global__ __launch_bounds__(FT) __attribute__((amdgpu_waves_per_eu(8))) void k_fused_eval(const QPDev* __restrict__ qs,
+                                                                                             int skip) {
   const QPDev& q = qs[blockIdx.y];
+  if (skip && q.scal[SC_CONVERGED] != 0.0) return;
   __shared__ double sh[FT / 64];
   __shared__ unsigned last;
   const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
@@ -1777,11 +1793,11 @@ hipError_t qp_fused_pre(const QPBatch& qb, int restart, int* info, hipStream_t s
   // the diagonal-only mode has no copy to spread: one workgroup per QP
   const int split = kmode == KMODE_K0_DIAG ? 1 : fused_split(qb.B);
   hipLaunchKernelGGL(k_fused_pre, dim3(split, qb.B), dim3(FT), 0, st, qb.d, kmode == KMODE_K0_OFFDIAG ? 0 : restart,
-                     kmode == KMODE_K0_OFFDIAG ? nullptr : info, kmode);
+                     kmode == KMODE_K0_OFFDIAG ? nullptr : info, kmode, kmode == KMODE_K0_OFFDIAG ? 0 : qb.skip);
   return hipGetLastError();
 }
 hipError_t qp_fused_mid(const QPBatch& qb, hipStream_t st) {
-  hipLaunchKernelGGL(k_fused_mid, dim3(qb.B), dim3(FT), 0, st, qb.d);
+  hipLaunchKernelGGL(k_fused_mid, dim3(qb.B), dim3(FT), 0, st, qb.d, qb.skip);
   return hipGetLastError();
 }
 hipError_t qp_fused_solves(const QPBatch& qb, const double* K, int64_t ld, int N, const double* D, const double* Linv,
@@ -1790,10 +1806,10 @@ hipError_t qp_fused_solves(const QPBatch& qb, const double* K, int64_t ld, int N
   // 16 waves when the batch leaves a CU per QP, 8 when QPs share CUs (trsv.hip)
   if (qb.B <= device_cus())
     hipLaunchKernelGGL(k_fused_solves<16>, dim3(qb.B), dim3(64 * 16), trsv_small_lds(N, 16), st, qb.d, K, ld, N, D,
-                       Linv, b, sK, sD, sL, sb, freeze);
+                       Linv, b, sK, sD, sL, sb, freeze, qb.skip);
   else
     hipLaunchKernelGGL(k_fused_solves<8>, dim3(qb.B), dim3(64 * 8), trsv_small_lds(N, 8), st, qb.d, K, ld, N, D, Linv,
-                       b, sK, sD, sL, sb, freeze);
+                       b, sK, sD, sL, sb, freeze, qb.skip);
   return hipGetLastError();
 }
 // the evaluation's workgroups per QP: enough for two row passes (4 rows per
@@ -1808,12 +1824,12 @@ static int eval_split(const QPBatch& qb) {
   return s < 1 ? 1 : (s > 8 ? 8 : s);
 }
 hipError_t qp_fused_eval(const QPBatch& qb, hipStream_t st) {
-  hipLaunchKernelGGL(k_fused_eval, dim3(eval_split(qb), qb.B), dim3(FT), 0, st, qb.d);
+  hipLaunchKernelGGL(k_fused_eval, dim3(eval_split(qb), qb.B), dim3(FT), 0, st, qb.d, qb.skip);
   return hipGetLastError();
 }
 hipError_t qp_fused_post(const QPBatch& qb, int freeze, hipStream_t st) {
-  hipLaunchKernelGGL(k_fused_post, dim3(qb.B), dim3(FT), 0, st, qb.d, freeze);
-  hipLaunchKernelGGL(k_fused_eval, dim3(eval_split(qb), qb.B), dim3(FT), 0, st, qb.d);
+  hipLaunchKernelGGL(k_fused_post, dim3(qb.B), dim3(FT), 0, st, qb.d, freeze, qb.skip);
+  hipLaunchKernelGGL(k_fused_eval, dim3(eval_split(qb), qb.B), dim3(FT), 0, st, qb.d, qb.skip);
   return hipGetLastError();
 }
 

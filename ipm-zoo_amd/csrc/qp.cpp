@@ -100,6 +100,7 @@ struct ipmz_qp {
   hipEvent_t step_in = nullptr;  // the caller's stream reached the step (the fork onto ctx->own)
   bool step_pending = false;
   int last_step_graph = 0;  // the last ipmz_qp_step replayed a captured hipGraph
+  double* summary = nullptr;  // ipmz_batch_solve_ex: the 3 doubles of its looks at the device, on first use
   int tr_cap = 0;
   double ph_ms[IPMZ_PH_COUNT] = {0};
   double tr_flops = 0.0;
@@ -286,20 +287,26 @@ Path path_of(const ipmz_qp* s) {
 LdltWs ldlt_ws_of(const ipmz_qp* s) { return ldlt_ws(s->ws, s->N, nbo_for(s->ctx, s->N), s->ctx->nbi); }
 NormalWs normal_ws_of(const ipmz_qp* s) { return normal_ws(s->nws.p, s->N, nbo_for(s->ctx, s->N), s->ctx->nbi); }
 
+// IPMZ_STEP_SKIP_CONVERGED: the batch's convergence words for the factor and solve kernels (skip false: nobody skips)
+size_t scal_pitch(const ipmz_qp* s);
+SkipGate skip_gate(const ipmz_qp* s, bool skip) {
+  return skip ? SkipGate{s->hq[0].scal + SC_CONVERGED, (int64_t)(scal_pitch(s) / 8)} : SkipGate{};
+}
 // the batch's strides as the batched LDL^T factor and the blocked solves take them
-BatchStrides batch_strides(const ipmz_qp* s, const double* K0) {
-  return BatchStrides{s->B, s->sK, s->sD, s->sL, s->sW, s->pflags, K0, s->small_kernel};
+BatchStrides batch_strides(const ipmz_qp* s, const double* K0, bool skip) {
+  return BatchStrides{s->B, s->sK, s->sD, s->sL, s->sW, s->pflags, K0, s->small_kernel, skip_gate(s, skip)};
 }
 TrsmBatch trsm_batch(const ipmz_qp* s, int64_t sB) { return TrsmBatch{s->B, s->sK, s->sD, s->sL, sB}; }
 
-int solve_batch(ipmz_qp* s, hipStream_t st, int which) {
+// skip: the step's IPMZ_STEP_SKIP_CONVERGED (the per-QP batch paths only, can_skip_converged)
+int solve_batch(ipmz_qp* s, hipStream_t st, int which, bool skip = false) {
   switch (path_of(s)) {
     case Path::BkGrid:  // overwriting_solve_bunch_kaufman, device-wide (L' in K)
       HIP_OK(bk_run(s->K, s->ldk, s->N, s->bklt, s->ipiv, bk_ws(s->bkfws, s->N), q0(s).b, st));
       break;
     case Path::BkSmall:
     case Path::BkBatch:  // overwriting_solve_bunch_kaufman
-      HIP_OK(bk_solve(s->K, s->ldk, s->N, s->ipiv, q0(s).b, s->B, s->sK, s->sP, s->sb, st));
+      HIP_OK(bk_solve(s->K, s->ldk, s->N, s->ipiv, q0(s).b, s->B, s->sK, s->sP, s->sb, st, skip_gate(s, skip)));
       break;
     case Path::Normal:
       return normal_solve_impl(s->ctx, s->n, s->m + s->p, s->K, s->ldk, s->D, normal_ws_of(s), q0(s).b);
@@ -313,15 +320,16 @@ int solve_batch(ipmz_qp* s, hipStream_t st, int which) {
       break;
     case Path::LdltBatch:
       HIP_OK(ldlt_solve_batched(s->K, s->ldk, s->N, s->D, s->bLinv, s->ctx->nbi, q0(s).b, s->B, s->sK, s->sD, s->sL,
-                                s->sb, st));
+                                s->sb, st, skip_gate(s, skip)));
       break;
   }
   return IPMZ_OK;
 }
 
-// info_reset: the caller already reset the batched factor's info word
+// info_reset: the caller already reset the batched factor's info word; skip: as solve_batch's (the callers that
+// reuse the step's factor -- the kkt, Newton-multi and adjoint solves -- never pass it: they need every QP's)
 bool uses_k0(const ipmz_qp* s);
-int factor_batch(ipmz_qp* s, TrailTimer* tt, bool info_reset, StepEdges* edges = nullptr) {
+int factor_batch(ipmz_qp* s, TrailTimer* tt, bool info_reset, StepEdges* edges = nullptr, bool skip = false) {
   hipStream_t st = s->ctx->stream;
   const int nbo = nbo_for(s->ctx, s->N);
   switch (path_of(s)) {
@@ -334,7 +342,7 @@ int factor_batch(ipmz_qp* s, TrailTimer* tt, bool info_reset, StepEdges* edges =
       return IPMZ_OK;
     case Path::BkSmall:
     case Path::BkBatch:
-      HIP_OK(bk_factor(s->K, s->ldk, s->N, s->ipiv, s->binfo, 0, s->B, s->sK, s->sP, st));
+      HIP_OK(bk_factor(s->K, s->ldk, s->N, s->ipiv, s->binfo, 0, s->B, s->sK, s->sP, st, skip_gate(s, skip)));
       return IPMZ_OK;
     case Path::Mixed: return mixed_factor_impl(s->ctx, s->K, s->ldk, s->mw, tt);
     case Path::Normal:
@@ -345,7 +353,7 @@ int factor_batch(ipmz_qp* s, TrailTimer* tt, bool info_reset, StepEdges* edges =
   // (info_reset: the fused step, whose pre phase assembled into K0)
   if (!info_reset) HIP_OK(hipMemsetAsync(s->binfo, 0x7f, sizeof(int), st));
   HIP_OK(ldlt_factor_batched(s->K, s->ldk, s->N, s->D, s->bLinv, s->bW, nbo, s->ctx->nbi, s->binfo, st,
-                             batch_strides(s, info_reset && uses_k0(s) ? s->K0 : nullptr)));
+                             batch_strides(s, info_reset && uses_k0(s) ? s->K0 : nullptr, skip)));
   return IPMZ_OK;
 }
 
@@ -362,6 +370,13 @@ bool fused_solves(const ipmz_qp* s) {
 // factor (nbi 64) consumes it; otherwise the whole matrix is assembled into K
 bool uses_k0(const ipmz_qp* s) {
   return s->K0 && s->ctx->nbi == 64 && s->N <= IPMZ_SMALL_NMAX && !(debug_inject_mask() & IPMZ_DEBUG_NO_K0);
+}
+
+// IPMZ_STEP_SKIP_CONVERGED is served where every launch of the step runs whole workgroups per QP: the fused
+// small-system step of a batch on the small batched LDL^T factor (inner block 64) or the batched Bunch-Kaufman
+bool can_skip_converged(const ipmz_qp* s) {
+  const Path path = path_of(s);
+  return fused_phases(s) && s->ctx->nbi == 64 && (path == Path::LdltBatch || path == Path::BkBatch);
 }
 
 // The single-QP fp64 augmented LDL^T step whose factor forks onto the
@@ -387,7 +402,7 @@ int step_edge_rows(const ipmz_qp* s) {
 
 int run_step(ipmz_qp* s, int flags) {
   hipStream_t st = s->ctx->stream;
-  const QPBatch& qb = s->qb;
+  QPBatch qb = s->qb;  // (a copy: this step's skip flag travels in it)
   const bool t = s->timing;
   auto mark = [&](int i) {
     IPMZ_TRACE("step: phase mark %d", i);
@@ -396,6 +411,8 @@ int run_step(ipmz_qp* s, int flags) {
   const bool restart = flags & IPMZ_STEP_RESTART_IF_CONVERGED;
   const int freeze = restart ? 0 : 1;
   const bool fused = fused_phases(s);
+  const bool skip = flags & IPMZ_STEP_SKIP_CONVERGED;  // (fused: step_impl refused every other step)
+  qb.skip = skip;  // (the fused phases' gate; the factor and the solves take theirs below)
   TrailTimer tt;
   tt.pairs = s->tr_pairs;
   tt.cap = t ? s->tr_cap : 0;
@@ -406,7 +423,7 @@ int run_step(ipmz_qp* s, int flags) {
     mark(0);
     HIP_OK(qp_fused_pre(qb, restart ? 1 : 0, s->eqnone ? nullptr : s->binfo, st, uses_k0(s) ? KMODE_K0_DIAG : KMODE_K));
     mark(1);
-    if ((rc = factor_batch(s, nullptr, true))) return rc;
+    if ((rc = factor_batch(s, nullptr, true, nullptr, skip))) return rc;
     mark(2);
     if (fused_solves(s)) {
       // both solves and the phases between them in one launch (the solve
@@ -417,11 +434,11 @@ int run_step(ipmz_qp* s, int flags) {
       mark(5);
       HIP_OK(qp_fused_eval(qb, st));
     } else {
-      if ((rc = solve_batch(s, st, 0))) return rc;
+      if ((rc = solve_batch(s, st, 0, skip))) return rc;
       mark(3);
       HIP_OK(qp_fused_mid(qb, st));
       mark(4);
-      if ((rc = solve_batch(s, st, 1))) return rc;
+      if ((rc = solve_batch(s, st, 1, skip))) return rc;
       mark(5);
       HIP_OK(qp_fused_post(qb, freeze, st));
     }
@@ -505,6 +522,8 @@ int initialize(ipmz_qp* s) {
   HIP_OK(qp_init_iterate(s->qb, st));
   if (s->K0) HIP_OK(qp_fused_pre(s->qb, 0, nullptr, st, KMODE_K0_OFFDIAG));
   HIP_OK(qp_evaluate(s->qb, st));
+  // the per-QP step count restarts with the scalar block (no step but one with IPMZ_STEP_SKIP_CONVERGED writes it)
+  HIP_OK(hipMemset2DAsync(q0(s).scal + SC_STEPS, scal_pitch(s), 0, sizeof(double), (size_t)s->B, st));
   HIP_OK(qp_save_initial(s->qb, st));
   s->loaded = true;
   HIP_OK(hipStreamSynchronize(st));
@@ -774,7 +793,26 @@ int wait_pending_step(ipmz_qp* s) {
   return IPMZ_OK;
 }
 
+// IPMZ_STEP_SKIP_CONVERGED on a step that cannot serve it, or with the restart: refused before anything is enqueued
+int refuse_skip(const ipmz_qp* s, int flags, const char* who) {
+  if (!(flags & IPMZ_STEP_SKIP_CONVERGED)) return IPMZ_OK;
+  if (flags & IPMZ_STEP_RESTART_IF_CONVERGED)
+    return fail(IPMZ_ERR_INVALID, std::string(who) + ": IPMZ_STEP_SKIP_CONVERGED with IPMZ_STEP_RESTART_IF_CONVERGED "
+                                                     "(a converged QP cannot both restart and sit out)");
+  if (can_skip_converged(s)) return IPMZ_OK;
+  const char* why = s->B == 1 ? "a solver of one QP (ipmz_qp_solve stops at convergence already)"
+                    : s->N > IPMZ_FUSED_NMAX ? "N > 1024 (the panel factor is not per QP)"
+                    : s->ctx->nbi != 64 ? "inner block 128 (its batched factor is not per QP)"
+                                        : "this factor path";
+  return fail(IPMZ_ERR_INVALID, std::string(who) + ": IPMZ_STEP_SKIP_CONVERGED is not served for " + why +
+                                    "; ask ipmz_batch_can_skip_converged");
+}
+
 int step_impl(ipmz_qp* s, int flags) {
+  if (s) {
+    const int rc = refuse_skip(s, flags, "ipmz_qp_step");
+    if (rc) return rc;
+  }
   if (!s || !s->loaded) return fail(IPMZ_ERR_STATE, "load or generate the QP first");
   HIP_OK(hipSetDevice(s->ctx->device));
   s->last_step_graph = 0;
@@ -1628,6 +1666,42 @@ int ipmz_batch_solve(ipmz_qp* s, int max_iter, int* iterations, int* converged_c
   }
   if (iterations) *iterations = it;
   if (converged_count) *converged_count = nconv;
+  return IPMZ_OK;
+}
+int ipmz_batch_can_skip_converged(ipmz_qp* s) { return s && can_skip_converged(s) ? 1 : 0; }
+// The same loop with the step's flags, looking at the device every check_every steps: a look is the batch's
+// summary (one launch) and a copy of its 3 doubles
+int ipmz_batch_solve_ex(ipmz_qp* s, int max_iter, int step_flags, int check_every, int* iterations,
+                        int* converged_count) {
+  const char* who = "ipmz_batch_solve_ex";
+  if (!s) return fail(IPMZ_ERR_INVALID, "null qp");
+  if (max_iter < 0 || check_every < 1 || (step_flags & ~(IPMZ_STEP_SKIP_CONVERGED | IPMZ_STEP_GRAPH)))
+    return fail(IPMZ_ERR_INVALID, std::string(who) + ": bad arguments (max_iter >= 0, check_every >= 1, step_flags of "
+                                                     "IPMZ_STEP_SKIP_CONVERGED and IPMZ_STEP_GRAPH only)");
+  int rc = refuse_skip(s, step_flags, who);
+  if (rc) return rc;
+  if (!s->loaded) return fail(IPMZ_ERR_STATE, "load or generate the batch first");
+  HIP_OK(hipSetDevice(s->ctx->device));
+  if ((rc = not_capturing(s->ctx, who))) return rc;
+  if (!s->summary && !(s->summary = dev_alloc<double>(s, 3, false))) {  // (every look writes all three)
+    s->alloc_failed = false;  // (create_solver's flag)
+    (void)hipGetLastError();
+    return fail(IPMZ_ERR_NOMEM, "device allocation failed");
+  }
+  hipStream_t st = s->ctx->stream;
+  double sum[3];
+  int it = 0;
+  for (;;) {
+    HIP_OK(qp_batch_summary(s->qb, s->summary, st));
+    HIP_OK(hipMemcpyAsync(sum, s->summary, sizeof(sum), hipMemcpyDeviceToHost, st));
+    HIP_OK(hipStreamSynchronize(st));
+    if ((rc = qp_status(s))) return rc;
+    if (sum[2] == 0.0 || it >= max_iter) break;
+    for (const int end = max_iter - it < check_every ? max_iter : it + check_every; it < end; ++it)
+      if ((rc = step_impl(s, step_flags))) return rc;
+  }
+  if (iterations) *iterations = it;
+  if (converged_count) *converged_count = s->B - (int)sum[2];
   return IPMZ_OK;
 }
 int ipmz_batch_set_factor_kernel(ipmz_qp* s, int kernel) {

@@ -116,10 +116,11 @@ __global__ __launch_bounds__(64 * SNW) __attribute__((amdgpu_waves_per_eu(2))) v
                                                          double* __restrict__ D, double* __restrict__ Linv,
                                                          double* __restrict__ W, int* __restrict__ info, int64_t sK,
                                                          int64_t sD, int64_t sL, int64_t sW,
-                                                         const double* __restrict__ K0) {
+                                                         const double* __restrict__ K0, SkipGate gate) {
   constexpr int SFR = Cfg<SNW>::SFR, SNN = Cfg<SNW>::SNN;
   __shared__ __attribute__((aligned(16))) double smem[2 * 64 * DS + 64];
   const int64_t qp = blockIdx.x;
+  if (gate.skips(qp)) return;  // (kernels.h SkipGate: before anything else, in all four factors)
   K += qp * sK;
   if (K0) K0 += qp * sK;  // the assembled matrix: block column 0's steps read it (first touch), L goes to K
   D += qp * sD;
@@ -250,10 +251,11 @@ __global__ __launch_bounds__(64 * SNW) __attribute__((amdgpu_waves_per_eu(2))) v
 template <int SNW, int CM, int EXP = 0>
 __global__ __launch_bounds__(64 * SNW) __attribute__((amdgpu_waves_per_eu(2))) void ldlt_small_left_kernel(
     double* __restrict__ K, int64_t ld, int N, double* __restrict__ D, double* __restrict__ Linv,
-    int* __restrict__ info, int64_t sK, int64_t sD, int64_t sL, const double* __restrict__ K0) {
+    int* __restrict__ info, int64_t sK, int64_t sD, int64_t sL, const double* __restrict__ K0, SkipGate gate) {
   constexpr int SFR = Cfg<SNW>::SFR, SNN = Cfg<SNW>::SNN, TB = 64 * DS;
   __shared__ __attribute__((aligned(16))) double smem[4 * TB + 64 + IPMZ_SMALL_NMAX];
   const int64_t qp = blockIdx.x;
+  if (gate.skips(qp)) return;
   K += qp * sK;
   D += qp * sD;
   Linv += qp * sL;
@@ -460,10 +462,11 @@ static_assert(ws_schedule_fits(2) && ws_schedule_fits(3) && ws_schedule_fits(4) 
 template <int NB, bool CLK = false>
 __global__ __launch_bounds__(512) __attribute__((amdgpu_waves_per_eu(2))) void ldlt_small_ws_kernel(
     double* __restrict__ K, int64_t ld, int N, double* __restrict__ D, double* __restrict__ Linv,
-    int* __restrict__ info, int64_t sK, int64_t sD, int64_t sL, const double* __restrict__ K0) {
+    int* __restrict__ info, int64_t sK, int64_t sD, int64_t sL, const double* __restrict__ K0, SkipGate gate) {
   constexpr int TB = 64 * DS;
   __shared__ __attribute__((aligned(16))) double smem[4 * TB + 64 + 64 * NB];
   const int64_t qp = blockIdx.x;
+  if (gate.skips(qp)) return;  // (both wave groups: nobody is left at a barrier)
   K += qp * sK;
   D += qp * sD;
   Linv += qp * sL;
@@ -851,12 +854,13 @@ __global__ __launch_bounds__(64 * SNW) void ldlt_small_pair_kernel(double* __res
                                                               double* __restrict__ W, int* __restrict__ info,
                                                               int64_t sK, int64_t sD, int64_t sL, int64_t sW,
                                                               unsigned* __restrict__ flags, unsigned* __restrict__ err,
-                                                              const double* __restrict__ K0) {
+                                                              const double* __restrict__ K0, SkipGate gate) {
   constexpr int SFR = Cfg<SNW>::SFR, SNN = Cfg<SNW>::SNN;
   __shared__ __attribute__((aligned(16))) double smem[2 * 64 * DS + 64];
   __shared__ unsigned sh_ok;
   const int64_t qp = blockIdx.x >> 1;
   const int role = blockIdx.x & 1;
+  if (gate.skips(qp)) return;  // (both roles read the same word: neither waits for the other's flags)
   K += qp * sK;
   if (K0) K0 += qp * sK;  // block column 0's steps read the assembled matrix (not written by this launch)
   D += qp * sD;
@@ -1008,21 +1012,21 @@ hipError_t ldlt_factor_small_batched(double* K, int64_t ld, int N, double* D, do
     hipError_t e = hipMemsetAsync(bs.pflags, 0, ((size_t)bs.B * IPMZ_PAIR_FLAGS + 1) * sizeof(unsigned), st);
     if (e != hipSuccess) return e;
     hipLaunchKernelGGL(ldlt_small_pair_kernel<8>, dim3(2 * bs.B), dim3(64 * 8), 0, st, K, ld, N, D, Linv, W, info,
-                       bs.sK, bs.sD, bs.sL, bs.sW, bs.pflags, bs.pflags + (size_t)bs.B * IPMZ_PAIR_FLAGS, bs.K0);
+                       bs.sK, bs.sD, bs.sL, bs.sW, bs.pflags, bs.pflags + (size_t)bs.B * IPMZ_PAIR_FLAGS, bs.K0, bs.skip);
     return hipGetLastError();
   }
   if (kern == IPMZ_BATCH_FACTOR_ONE) {
     // 8 waves (two per SIMD) also when the batch leaves a CU per QP: 16 waves
     // measured slower (N = 320, B = 128: 249 vs 190 us)
     hipLaunchKernelGGL(ldlt_small_kernel<8>, dim3(bs.B), dim3(64 * 8), 0, st, K, ld, N, D, Linv, W, info, bs.sK,
-                       bs.sD, bs.sL, bs.sW, bs.K0);
+                       bs.sD, bs.sL, bs.sW, bs.K0, bs.skip);
     return hipGetLastError();
   }
   // left-looking: wave-specialized up to N = 320 (C4: 1024 QPs 854 -> 706 us,
   // 128 QPs 195 -> 156 us against the right-looking factor), else the plain one
   const int nb = (N + 63) / 64;
   auto ws = [&](auto kern) {
-    hipLaunchKernelGGL(kern, dim3(bs.B), dim3(512), 0, st, K, ld, N, D, Linv, info, bs.sK, bs.sD, bs.sL, bs.K0);
+    hipLaunchKernelGGL(kern, dim3(bs.B), dim3(512), 0, st, K, ld, N, D, Linv, info, bs.sK, bs.sD, bs.sL, bs.K0, bs.skip);
   };
   if (nb == 5) ws(ldlt_small_ws_kernel<5>);
   else if (nb == 4) ws(ldlt_small_ws_kernel<4>);
@@ -1030,7 +1034,7 @@ hipError_t ldlt_factor_small_batched(double* K, int64_t ld, int N, double* D, do
   else if (nb == 2) ws(ldlt_small_ws_kernel<2>);
   else
     hipLaunchKernelGGL((ldlt_small_left_kernel<8, 4>), dim3(bs.B), dim3(64 * 8), 0, st, K, ld, N, D, Linv, info,
-                       bs.sK, bs.sD, bs.sL, bs.K0);
+                       bs.sK, bs.sD, bs.sL, bs.K0, bs.skip);
   return hipGetLastError();
 }
 
@@ -1040,7 +1044,7 @@ hipError_t ldlt_factor_small_variant(int snw, double* K, int64_t ld, int N, doub
                                      int* info, hipStream_t st, const BatchStrides& bs) {
   if (snw >= 100) {  // 100 + EXP: the left-looking kernel's attribution variants
     auto l = [&](auto kern) {
-      hipLaunchKernelGGL(kern, dim3(bs.B), dim3(64 * 8), 0, st, K, ld, N, D, Linv, info, bs.sK, bs.sD, bs.sL, bs.K0);
+      hipLaunchKernelGGL(kern, dim3(bs.B), dim3(64 * 8), 0, st, K, ld, N, D, Linv, info, bs.sK, bs.sD, bs.sL, bs.K0, bs.skip);
     };
     switch (snw - 100) {
       case 1: l(ldlt_small_left_kernel<8, 4, 1>); break;
@@ -1054,7 +1058,7 @@ hipError_t ldlt_factor_small_variant(int snw, double* K, int64_t ld, int N, doub
   } else if (snw == 2) {  // the wave-specialized left-looking factor (N <= 320)
     const int nb = (N + 63) / 64;
     auto l = [&](auto kern) {
-      hipLaunchKernelGGL(kern, dim3(bs.B), dim3(512), 0, st, K, ld, N, D, Linv, info, bs.sK, bs.sD, bs.sL, bs.K0);
+      hipLaunchKernelGGL(kern, dim3(bs.B), dim3(512), 0, st, K, ld, N, D, Linv, info, bs.sK, bs.sD, bs.sL, bs.K0, bs.skip);
     };
     if (nb == 5 && (debug_inject_mask() & IPMZ_DEBUG_TRACE)) {
       l(ldlt_small_ws_kernel<5, true>);
@@ -1080,13 +1084,13 @@ hipError_t ldlt_factor_small_variant(int snw, double* K, int64_t ld, int N, doub
     else return hipErrorInvalidValue;
   } else if (snw == 1)
     hipLaunchKernelGGL((ldlt_small_left_kernel<8, 4>), dim3(bs.B), dim3(64 * 8), 0, st, K, ld, N, D, Linv, info,
-                       bs.sK, bs.sD, bs.sL, bs.K0);
+                       bs.sK, bs.sD, bs.sL, bs.K0, bs.skip);
   else if (snw == 4)
     hipLaunchKernelGGL(ldlt_small_kernel<4>, dim3(bs.B), dim3(64 * 4), 0, st, K, ld, N, D, Linv, W, info, bs.sK,
-                       bs.sD, bs.sL, bs.sW, bs.K0);
+                       bs.sD, bs.sL, bs.sW, bs.K0, bs.skip);
   else
     hipLaunchKernelGGL(ldlt_small_kernel<8>, dim3(bs.B), dim3(64 * 8), 0, st, K, ld, N, D, Linv, W, info, bs.sK,
-                       bs.sD, bs.sL, bs.sW, bs.K0);
+                       bs.sD, bs.sL, bs.sW, bs.K0, bs.skip);
   return hipGetLastError();
 }
 

@@ -261,10 +261,12 @@ template <int NB>
 __global__ __launch_bounds__(TRSV_NT) void trsv_batched_kernel(const double* __restrict__ K, int64_t ld, int N,
                                                                const double* __restrict__ D,
                                                                const double* __restrict__ Linv, double* b,
-                                                               int64_t sK, int64_t sD, int64_t sL, int64_t sb) {
+                                                               int64_t sK, int64_t sD, int64_t sL, int64_t sb,
+                                                               SkipGate gate) {
   __shared__ double Ls[NB][NB + 1];
   __shared__ double vs[NB], ys[NB], part[4][NB];
   const int64_t q = blockIdx.x;
+  if (gate.skips(q)) return;
   K += q * sK;
   D += q * sD;
   Linv += q * sL;
@@ -315,14 +317,16 @@ __global__ __launch_bounds__(64 * NW) void trsv_small_kernel(const double* __res
                                                              const double* __restrict__ D,
                                                              const double* __restrict__ Linv,
                                                              double* __restrict__ b, int64_t sK, int64_t sD,
-                                                             int64_t sL, int64_t sb) {
+                                                             int64_t sL, int64_t sb, SkipGate gate) {
   extern __shared__ __attribute__((aligned(16))) double sm[];
   const int64_t q = blockIdx.x;
+  if (gate.skips(q)) return;
   trsv_small_body<NW>(K + q * sK, ld, N, D + q * sD, Linv + q * sL, b + q * sb, sm);
 }
 
 hipError_t ldlt_solve_batched(const double* K, int64_t ld, int N, const double* D, const double* Linv, int nbi,
-                              double* b, int B, int64_t sK, int64_t sD, int64_t sL, int64_t sb, hipStream_t st) {
+                              double* b, int B, int64_t sK, int64_t sD, int64_t sL, int64_t sb, hipStream_t st,
+                              const SkipGate& skip) {
   if (N <= 0 || B <= 0) return hipSuccess;
   if (nbi == 64 && N <= TRSV_SMALL_NMAX) {
     // 16 waves when the batch leaves a CU per QP, 8 when QPs share CUs
@@ -332,15 +336,16 @@ hipError_t ldlt_solve_batched(const double* K, int64_t ld, int N, const double* 
     const size_t lds = trsv_small_lds(N, NW);
     if (wide)
       hipLaunchKernelGGL((trsv_small_kernel<16>), dim3(B), dim3(64 * 16), lds, st, K, ld, N, D, Linv, b, sK, sD, sL,
-                         sb);
+                         sb, skip);
     else
       hipLaunchKernelGGL((trsv_small_kernel<8>), dim3(B), dim3(64 * 8), lds, st, K, ld, N, D, Linv, b, sK, sD, sL,
-                         sb);
+                         sb, skip);
   } else if (nbi == 64)
-    hipLaunchKernelGGL((trsv_batched_kernel<64>), dim3(B), dim3(TRSV_NT), 0, st, K, ld, N, D, Linv, b, sK, sD, sL, sb);
+    hipLaunchKernelGGL((trsv_batched_kernel<64>), dim3(B), dim3(TRSV_NT), 0, st, K, ld, N, D, Linv, b, sK, sD, sL, sb,
+                       skip);
   else if (nbi == 128)
     hipLaunchKernelGGL((trsv_batched_kernel<128>), dim3(B), dim3(TRSV_NT), 0, st, K, ld, N, D, Linv, b, sK, sD, sL,
-                       sb);
+                       sb, skip);
   else
     return hipErrorInvalidValue;
   return hipGetLastError();

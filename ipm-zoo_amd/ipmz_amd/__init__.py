@@ -26,11 +26,12 @@ IPMZ_OK = 0
 ERR = {-1: "invalid argument", -2: "HIP error", -3: "out of device memory", -4: "no gfx950 device",
        -5: "bad state"}
 SC = dict(f=0, res=1, mu=2, alpha_aff=3, mu_aff=4, sigma=5, alpha=6, converged=7, mu_new=8, restarts=9,
-          ir_ratio_aff=10, ir_iters_aff=11, ir_ratio=12, ir_iters=13)
+          ir_ratio_aff=10, ir_iters_aff=11, ir_ratio=12, ir_iters=13, steps=14)
 SC_COUNT = 16
 PH = dict(step=0, assemble=1, factor=2, solve=3, trailing=4, eval=5)
 STEP_RESTART_IF_CONVERGED = 1
 STEP_GRAPH = 2
+STEP_SKIP_CONVERGED = 4  # include/ipmz.h IPMZ_STEP_SKIP_CONVERGED: converged QPs of a batch take no part in the step
 SET_STATE_UNCHECKED = 1  # include/ipmz.h IPMZ_SET_STATE_UNCHECKED
 SLOTS = ["x", "lambda_A", "lambda_C", "s", "p", "lambda_g", "lambda_h", "lambda_y", "lambda_z", "g", "h", "y", "z"]
 
@@ -58,6 +59,7 @@ EXPORTS = [
     "ipmz_qp_newton_adjoint_multi", "ipmz_batch_newton_adjoint_multi",
     "ipmz_batch_load_device", "ipmz_batch_copy_state", "ipmz_batch_data_vjp", "ipmz_batch_data_jvp",
     "ipmz_batch_data_vjp_multi", "ipmz_batch_set_state_device", "ipmz_qp_get_factor",
+    "ipmz_batch_solve_ex", "ipmz_batch_can_skip_converged",
 ]
 SOLVE_MULTI_PANEL = 256  # include/ipmz.h IPMZ_SOLVE_MULTI_PANEL: column panel of the blocked multi-rhs solve
 REDUCTION_AUGMENTED, REDUCTION_NORMAL = 0, 1
@@ -270,6 +272,8 @@ def _load():
         "ipmz_batch_data_jvp": ([_VP, _I, ctypes.POINTER(_QPDeviceTangent), _VP, _I64, _I64], _I),
         "ipmz_batch_data_vjp_multi": ([_VP, _I, _VP, _I64, _I64, ctypes.POINTER(_QPDeviceGradMulti)], _I),
         "ipmz_batch_set_state_device": ([_VP, _VP, _I64, _VP, ctypes.c_double, _I], _I),
+        "ipmz_batch_solve_ex": ([_VP, _I, _I, _I, ctypes.POINTER(_I), ctypes.POINTER(_I)], _I),
+        "ipmz_batch_can_skip_converged": ([_VP], _I),
     }
     for name, (args, res) in sig.items():
         fn = getattr(lib, name)
@@ -893,6 +897,11 @@ class Optimizer:
         self._bump()
         _check(lib.ipmz_qp_step(self.h, flags), "ipmz_qp_step")
 
+    def can_skip_converged(self):
+        """Does step(STEP_SKIP_CONVERGED) serve this solver under the context's current blocking?  Batches
+        (batch > 1) of small systems (N <= 1024) with inner block 64; never a solver of one QP."""
+        return bool(lib.ipmz_batch_can_skip_converged(self.h))
+
     def last_step_graph(self):
         """True when the last step replayed a captured hipGraph."""
         return bool(lib.ipmz_qp_last_step_graph(self.h))
@@ -908,7 +917,9 @@ class Optimizer:
     def scalars(self):
         out = np.zeros(SC_COUNT)
         _check(lib.ipmz_qp_scalars(self.h, _dp(out)), "ipmz_qp_scalars")
-        return {k: out[i] for k, i in SC.items()}
+        # (QP 0's block without SC["steps"]: only a batch's skip steps count there -- Batch.step_counts() -- and the
+        # dict keeps the entries it always had)
+        return {k: out[i] for k, i in SC.items() if k != "steps"}
 
     def device_scalars_ptr(self):
         p = _VP()
@@ -1141,9 +1152,23 @@ class Batch(Optimizer):
         v = np.ascontiguousarray(v, dtype=np.float64)
         _check(lib.ipmz_batch_set_state(self.h, index, _dp(v)), "ipmz_batch_set_state")
 
-    def solve_all(self, max_iter=100):
+    def solve_all(self, max_iter=100, skip_converged=False, check_every=1, graph=False):
+        """Step until every QP converged or max_iter: (steps enqueued, QPs converged).  skip_converged: the steps
+        carry STEP_SKIP_CONVERGED, so a converged QP costs nothing in any launch (can_skip_converged() says
+        whether the solver serves it; the iterates are bitwise those of the plain solve, step_counts() each QP's
+        own count).  check_every: steps enqueued between two looks at the device.  graph: the steps replay a
+        captured hipGraph.  The defaults are ipmz_batch_solve; anything else is ipmz_batch_solve_ex."""
         self._bump()
         it = ctypes.c_int(0)
         nc = ctypes.c_int(0)
-        _check(lib.ipmz_batch_solve(self.h, max_iter, ctypes.byref(it), ctypes.byref(nc)), "ipmz_batch_solve")
+        if not skip_converged and check_every == 1 and not graph:
+            _check(lib.ipmz_batch_solve(self.h, max_iter, ctypes.byref(it), ctypes.byref(nc)), "ipmz_batch_solve")
+        else:
+            flags = (STEP_SKIP_CONVERGED if skip_converged else 0) | (STEP_GRAPH if graph else 0)
+            _check(lib.ipmz_batch_solve_ex(self.h, max_iter, flags, int(check_every), ctypes.byref(it),
+                                           ctypes.byref(nc)), "ipmz_batch_solve_ex")
         return it.value, nc.value
+
+    def step_counts(self):
+        """Per QP: the steps with STEP_SKIP_CONVERGED it took part in since the last load (SC["steps"])."""
+        return self.batch_scalars()[:, SC["steps"]].astype(np.int64)

@@ -22,15 +22,21 @@ def _even(k):
 class _SolveQP(torch.autograd.Function):
     @staticmethod
     def forward(ctx, solver, max_iter, strict, symmetrize, *blocks):
-        # (after the data blocks: the warm start, an iterate per QP and its floor -- no input of the derivative)
+        # (after the data blocks: the warm start, an iterate per QP and its floor, then solve_all's skip_converged
+        # and check_every -- no inputs of the derivative)
         blocks, warm = blocks[:len(_NAMES)], blocks[len(_NAMES):]
+        skip_converged, check_every = warm[2:4] if len(warm) >= 4 else (False, 1)
         given = {k: t.detach() for k, t in zip(_NAMES, blocks) if t is not None}
         solver.load_tensors(**given)
         if warm and warm[0] is not None:
             solver.set_state_tensor(warm[0].detach(), floor=warm[1], check=True)
         batch = lib.ipmz_batch_size(solver.h)
+        if skip_converged and not solver.can_skip_converged():
+            raise IpmzError("solve_qp: skip_converged=True, but this solver cannot skip converged QPs "
+                            "(can_skip_converged() is False: a batch of more than one QP with N <= 1024 and inner "
+                            "block 64 is needed)")
         if isinstance(solver, Batch):
-            its, converged = solver.solve_all(max_iter)
+            its, converged = solver.solve_all(max_iter, skip_converged=skip_converged, check_every=check_every)
         else:
             its, trace = solver.solve(max_iter)
             converged = int(solver.scalars()["converged"] == 1.0)
@@ -71,7 +77,7 @@ class _SolveQP(torch.autograd.Function):
             if g is None and k in wanted:  # a block of dimension 0
                 g = torch.zeros(ctx.shapes[k], dtype=torch.float64, device=grad_x.device)
             out.append(None if g is None else g.reshape(ctx.shapes[k]))
-        return (None, None, None, None, *out, None, None)
+        return (None, None, None, None, *out, None, None, None, None)
 
     @staticmethod
     def jvp(ctx, _solver, _max_iter, _strict, _symmetrize, *tangents):
@@ -170,7 +176,8 @@ def solution_jacobian(solver, *, shared=(), only=None):
 
 
 def solve_qp(solver, *, Q=None, c=None, l_x=None, u_x=None, A_ineq=None, l_A_ineq=None, u_A_ineq=None, A_eq=None,
-             b_eq=None, max_iter=100, strict=True, symmetrize=False, warm_start=None, warm_floor=0.0):
+             b_eq=None, max_iter=100, strict=True, symmetrize=False, warm_start=None, warm_floor=0.0,
+             skip_converged=False, check_every=1):
     """x* of every QP of `solver` (an Optimizer or a Batch), (batch, n), differentiable with respect to the data.
 
     The data are float64 CUDA tensors under load_tensors' names and rules: matrices (batch, rows, n) or (rows, n)
@@ -197,10 +204,16 @@ def solve_qp(solver, *, Q=None, c=None, l_x=None, u_x=None, A_ineq=None, l_A_ine
     multiplier below it.  How many iterations a warm start saves, and with which floor, is a measurement
     (the warm start's table), not a promise; the default warm_floor stays 0.0 until it is settled.
 
+    skip_converged, check_every: handed to Batch.solve_all -- a converged QP then takes no part in the later steps
+    and the host looks at the device every check_every steps; x* and every gradient keep their bits (backward and
+    jvp read the final iterate, and their factor covers every QP).  skip_converged=True on a solver that cannot
+    skip (can_skip_converged() is False) raises IpmzError.
+
     The solver keeps the iterate the backward pass reads: one forward / backward pair is in flight per solver, and
     backward raises IpmzError when a load, step, solve, set_vars or set_state_tensor has moved the solver since its
     forward."""
     given = dict(Q=Q, c=c, l_x=l_x, u_x=u_x, A_ineq=A_ineq, l_A_ineq=l_A_ineq, u_A_ineq=u_A_ineq, A_eq=A_eq, b_eq=b_eq)
     if warm_start is not None:
         warm_start = warm_start.detach()
-    return _SolveQP.apply(solver, max_iter, strict, symmetrize, *[given[k] for k in _NAMES], warm_start, warm_floor)
+    return _SolveQP.apply(solver, max_iter, strict, symmetrize, *[given[k] for k in _NAMES], warm_start, warm_floor,
+                          skip_converged, check_every)
