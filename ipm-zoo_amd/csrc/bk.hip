@@ -146,7 +146,7 @@ __global__ __launch_bounds__(BKT) void k_bk_factor(double* __restrict__ Ab, int6
       // ---- symmetric interchange of kk and kp in the trailing lower triangle
       const int kk = k + step - 1;
       __syncthreads();
-      if (kp != kk) {
+      if (kp != kk && kk < n) {
         for (int i = kp + 1 + tid; i < n; i += BKT) {
           const double t = a(i, kp);
           a(i, kp) = a(i, kk);
@@ -157,6 +157,11 @@ __global__ __launch_bounds__(BKT) void k_bk_factor(double* __restrict__ Ab, int6
           a(kp, j) = a(j, kk);
           a(j, kk) = t;
         }
+        // the reference swaps the diagonal after its loops (LinearSolvers.cpp:
+        // 137-150).  For kp > kk the loops never touch it; for kp < kk (a NaN
+        // pivot over a zero column: i_max = 0) the first loop's row i = kk
+        // moves a(kk, kk), so the diagonal waits for the loops.
+        __syncthreads();
         if (tid == 0) {
           double t = a(kp, kp);
           a(kp, kp) = a(kk, kk);
@@ -218,8 +223,8 @@ __global__ __launch_bounds__(BKT) void k_bk_factor(double* __restrict__ Ab, int6
       }
     }
     if (tid == 0) {
-      if (step == 1) ipiv[k] = kp;
-      else ipiv[k] = ipiv[k + 1] = -kp;
+      ipiv[k] = step == 1 ? kp : -kp;
+      if (step == 2 && k + 1 < n) ipiv[k + 1] = -kp;  // (a NaN last pivot: the reference writes past the end)
     }
     __syncthreads();
     k += step;
@@ -570,6 +575,60 @@ __device__ double block_fmax(double v, double* sv) {
   for (int w = 0; w < BKW; ++w) s = fmax(s, sv[w]);
   return s;
 }
+
+// The interchange of kk = k + step - 1 with an EARLIER row kp < kk, applied to
+// the matrix in place (LinearSolvers.cpp:137-150 in the reference's order).
+// The row search returns i_max = 0 when nothing in the column compares
+// greater than zero, and a NaN pivot then fails every test: kp = 0 < k.  The
+// swap map of pass() covers kp > kk only; this rare case takes the plain
+// route instead -- interchange, stage column k again, then the step as one
+// without interchange.  Every owner swaps a(i, kp) and a(i, kk) of its rows;
+// what moves between rows (the diagonal swap, a 2x2 pivot's a(kk, k) and
+// a(kp, k)) lies in rows kp, k, kk, whose entries in columns kp, k, kk every
+// workgroup takes from the published buffers (its own rows from the matrix),
+// runs the reference's sequence on, and writes back where it owns the row.
+__device__ __noinline__ void backward_interchange(double* __restrict__ A, int64_t ld, int k, int step, int kp,
+                                                  const double* ck0, const double* ck1, const double* prow,
+                                                  const double* pcol, int g, int G, int nq) {
+  const int tid = threadIdx.x, kk = k + step - 1;
+  const int id[3] = {kp, k, kk};
+  auto pos = [&](int x) { return x == id[0] ? 0 : x == id[1] ? 1 : 2; };
+  auto old = [&](int r, int c) -> double {
+    if (r % G == g) return A[(int64_t)r * ld + c];
+    if (r == kp) return ld_sc1(prow + c);
+    if (c == kp) return ld_sc1(pcol + r);
+    if (c == k) return ld_sc1(ck0 + r);
+    return r > k ? ld_sc1(ck1 + r) : 0.0;  // a(k, k + 1) never leaves its row
+  };
+  double M[3][3];
+  for (int a = 0; a < 3; ++a)
+    for (int b = 0; b < 3; ++b) M[a][b] = old(id[a], id[b]);
+  auto swp = [&](int a0, int b0, int a1, int b1) {
+    const double t = M[a0][b0];
+    M[a0][b0] = M[a1][b1];
+    M[a1][b1] = t;
+  };
+  const int pp = pos(kp), pk = pos(k), pq = pos(kk);
+  for (int a = 0; a < 3; ++a)
+    if (pos(id[a]) == a && id[a] > kp) swp(a, pp, a, pq);
+  swp(pp, pp, pq, pq);
+  if (step == 2) swp(pq, pk, pp, pk);
+  __syncthreads();  // every thread has read the old values
+  if (tid == 0)
+    for (int a = 0; a < 3; ++a)
+      if (pos(id[a]) == a && id[a] % G == g)
+        for (int b = 0; b < 3; ++b)
+          if (pos(id[b]) == b) A[(int64_t)id[a] * ld + id[b]] = M[a][b];
+  for (int q = tid; q < nq; q += T) {
+    const int i = g + q * G;
+    if (i > kp && i != k && i != kk) {
+      const double t = A[(int64_t)i * ld + kp];
+      A[(int64_t)i * ld + kp] = A[(int64_t)i * ld + kk];
+      A[(int64_t)i * ld + kk] = t;
+    }
+  }
+  __syncthreads();
+}
 }  // namespace bkg
 
 __global__ __launch_bounds__(bkg::T) void k_bk_grid(double* __restrict__ A, int64_t ld, int n,
@@ -612,6 +671,7 @@ __global__ __launch_bounds__(bkg::T) void k_bk_grid(double* __restrict__ A, int6
     return run(P);
   };
   int info = 0, ref_info = 0;
+  int done_step = 0, done_kp = 0;  // a step whose backward interchange is applied already
   bool ok = stage(0);
   for (int k = 0; ok && k < n;) {
     const double* ck0 = colbuf + (2 * par) * (int64_t)n;
@@ -631,7 +691,10 @@ __global__ __launch_bounds__(bkg::T) void k_bk_grid(double* __restrict__ A, int6
     const double akk = fabs(ld_sc1(ck0 + k));
     int step = 1, kp = 0;
     bool zero_col = false;
-    if (akk == 0.0 && cmax == 0.0) {
+    if (done_step) {  // chosen last time round, its backward interchange applied since
+      step = done_step;
+      kp = k + step - 1;
+    } else if (akk == 0.0 && cmax == 0.0) {
       zero_col = true;
       if (info == 0) info = k + 1;
       if (ref_info == 0) {
@@ -661,6 +724,14 @@ __global__ __launch_bounds__(bkg::T) void k_bk_grid(double* __restrict__ A, int6
           st_sc1(pcol + i, x);
           r2 = fmax(r2, fabs(x));
         }
+        // i_max = 0 <= k (nothing in the column compares greater than zero):
+        // the row loop above is empty; the pivot test reads a(i_max, i_max)
+        // and a backward interchange moves row i_max's columns k, k + 1
+        if (imax <= k && imax % G == g) {
+          st_sc1(prow + imax, A[(int64_t)imax * ld + imax]);
+          st_sc1(prow + k, A[(int64_t)imax * ld + k]);
+          if (k + 1 < n) st_sc1(prow + k + 1, A[(int64_t)imax * ld + k + 1]);
+        }
       }
       r1 = block_fmax(r1, sv);
       r2 = block_fmax(r2, sv);
@@ -686,9 +757,23 @@ __global__ __launch_bounds__(bkg::T) void k_bk_grid(double* __restrict__ A, int6
     // pivot test need no pass; if it is a 1x1 pivot without interchange too,
     // both updates run in ONE pass (each element updated by step k, then by
     // step k+1 -- the reference's order), halving the trailing traffic.
+    if (!done_step && !zero_col && kp < k + step - 1 && k + step - 1 < n) {
+      // ---- a backward interchange (bkg::backward_interchange): applied in
+      // place, columns k, k + 1 staged again, and the same k comes round once
+      // more as a pivot without interchange.  The staging pass ends on a grid
+      // barrier, so no owner meets the next step before every row is swapped.
+      backward_interchange(A, ld, k, step, kp, ck0, ck1, prow, pcol, g, G, nq);
+      ok = stage(k);
+      done_step = step;
+      done_kp = kp;
+      continue;
+    }
+    const int kp_rec = done_step ? done_kp : kp;  // what ipiv records
+    const bool was_done = done_step != 0;
+    done_step = 0;
     bool pair = false;
     double r0 = 0.0, s01 = 0.0, d1 = 0.0;
-    if (!zero_col && step == 1 && kp == k && k + 1 < n) {
+    if (!was_done && !zero_col && step == 1 && kp == k && k + 1 < n) {
       r0 = 1.0 / ld_sc1(ck0 + k);
       s01 = r0 * ld_sc1(ck0 + k + 1);
       double v = 0.0, cmax1 = 0.0;
@@ -706,8 +791,8 @@ __global__ __launch_bounds__(bkg::T) void k_bk_grid(double* __restrict__ A, int6
       pair = !(akk1 == 0.0 && cmax1 == 0.0) && akk1 >= alpha * cmax1;
     }
     if (g == 0 && tid == 0) {
-      if (step == 1) ipiv[k] = kp;
-      else ipiv[k] = ipiv[k + 1] = -kp;
+      ipiv[k] = step == 1 ? kp_rec : -kp_rec;
+      if (step == 2 && k + 1 < n) ipiv[k + 1] = -kp_rec;  // (a NaN last pivot: the reference writes past the end)
       if (pair) ipiv[k + 1] = k + 1;
     }
     if (pair) {
@@ -736,7 +821,7 @@ __global__ __launch_bounds__(bkg::T) void k_bk_grid(double* __restrict__ A, int6
     P.k = k;
     P.lo = k + step;
     P.kp = kp;
-    P.swap = kp != k + step - 1;
+    P.swap = kp != k + step - 1 && k + step - 1 < n;
     P.ck0 = ck0;
     P.ck1 = ck1;
     P.prow = prow;

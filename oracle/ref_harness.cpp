@@ -19,6 +19,11 @@
 //                                   forces interchanges and 2 x 2 pivots
 //   bk_zeros_at <dir> <N> <seed> <i,j,..> <tag>
 //                                   the same with zero rows/columns at i, j, ..
+//   bk_file <dir> <N> <tag>         the same pair on the K (N x N, row-major)
+//                                   and b read from <dir>/<tag>_K.bin and
+//                                   <tag>_b.bin (tests/bk_pivot_cases.py: tied
+//                                   maxima, threshold equalities, a NaN pivot);
+//                                   writes <tag>_F, _ipiv, _x
 //   newton <dir> <n> <m> <seed> <iters> <tag>
 //                                   SlackedSlacks (box [+ ineq]) Newton
 //                                   iterations through the reference's own
@@ -368,6 +373,30 @@ static int mode_bk_rand(const std::string& dir, size_t N, uint64_t seed, size_t 
   return 0;
 }
 
+// bk_rand without the generator: K and b come from files
+static Vec read_bin(const std::string& path, size_t count) {
+  Vec v(count);
+  std::ifstream f(path, std::ios::binary);
+  f.read(reinterpret_cast<char*>(v.data()), (std::streamsize)(count * sizeof(double)));
+  if (!f || f.peek() != std::ifstream::traits_type::eof()) throw std::runtime_error("bad size: " + path);
+  return v;
+}
+static int mode_bk_file(const std::string& dir, size_t N, const std::string& tag) {
+  const Vec flat = read_bin(dir + "/" + tag + "_K.bin", N * N);
+  const Vec b = read_bin(dir + "/" + tag + "_b.bin", N);
+  Mat K(N, Vec(N, 0.0));
+  for (size_t i = 0; i < N; ++i)
+    for (size_t j = 0; j < N; ++j) K[i][j] = flat[i * N + j];
+  auto [F, ipiv] = NO::LinearSolvers::symmetric_indefinite_factorization(K);
+  Vec x = b;
+  NO::LinearSolvers::overwriting_solve_bunch_kaufman(F, ipiv, x);
+  Vec piv(ipiv.begin(), ipiv.end());
+  write_bin(dir + "/" + tag + "_F.bin", flatten(F));
+  write_bin(dir + "/" + tag + "_ipiv.bin", piv);
+  write_bin(dir + "/" + tag + "_x.bin", x);
+  return 0;
+}
+
 // ---------------------------------------------------------------------------
 // One reference Newton iteration, restated around the reference's own private
 // methods (Optimizer.cpp:127-219), recording KKT, directions and scalars.
@@ -595,6 +624,7 @@ int main(int argc, char** argv) {
     if (mode == "bk" && argc == 6) return mode_bk(dir, std::stoul(argv[3]), std::stoull(argv[4]), argv[5]);
     if (mode == "bk_zeros_at" && argc == 7)
       return mode_bk_zeros_at(dir, std::stoul(argv[3]), std::stoull(argv[4]), argv[5], argv[6]);
+    if (mode == "bk_file" && argc == 5) return mode_bk_file(dir, std::stoul(argv[3]), argv[4]);
     if (mode == "bk_rand" && argc == 7)
       return mode_bk_rand(dir, std::stoul(argv[3]), std::stoull(argv[4]), std::stoul(argv[5]), argv[6]);
     if (mode == "newton" && argc == 8)

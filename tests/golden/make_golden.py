@@ -4,7 +4,8 @@
 Run in the build container (where /root/reference exists):
 
     make -C oracle -f Makefile.ref          # builds oracle/_ref/ref_harness
-    python tests/golden/make_golden.py
+    python tests/golden/make_golden.py            # every fixture
+    python tests/golden/make_golden.py bkp_thr21  # only the named tags (manifest entries of the others kept)
 
 The harness (oracle/ref_harness.cpp) links the reference's own objects
 (clang++ -O3 -DNDEBUG -ffp-contract=off) and calls
@@ -40,6 +41,13 @@ CASES = [
     # zero column 0 plus later zero columns: the reference's 0-based info stays
     # 0 after column 0, so column 5 takes kp = 5 and column 9 the kp = 0 defect
     ("bk_zeros_at", 16, 35, "0,5,9", "bkz0_16"),
+    # pivot choices on tied data (inputs written here from tests/bk_pivot_cases.py GOLDEN): the threshold gadgets
+    # (equalities and one-ulp misses of the three tests), integer matrices (tied maxima, exact cancellation) and a
+    # NaN pivot over a zero column (kp = 0 < k)
+    ("bk_file", 21, "bkp_thr21"),
+    ("bk_file", 17, "bkp_int17"),
+    ("bk_file", 64, "bkp_int64"),
+    ("bk_file", 8, "bkp_kplt8"),
     # C1: box-only SlackedSlacks, n=64, seed 1234, full solve trace
     ("newton", 64, 0, 1234, 100, "c1"),
     # C4-size QP: n=256, m=64 (N=320), seed 0, iterates 0-3
@@ -72,12 +80,30 @@ CASES = [
 ]
 
 
+def write_bk_file_inputs(tag, N):
+    sys.path.insert(0, os.path.join(REPO, "tests"))
+    import bk_pivot_cases
+    K = bk_pivot_cases.cases()[bk_pivot_cases.GOLDEN[tag]][1]
+    assert K.shape == (N, N)
+    K.astype("<f8").tofile(os.path.join(HERE, f"{tag}_K.bin"))
+    bk_pivot_cases.golden_rhs(N).astype("<f8").tofile(os.path.join(HERE, f"{tag}_b.bin"))
+
+
 def main():
     if not os.path.exists(HARNESS):
         sys.exit("build oracle/_ref/ref_harness first: make -C oracle -f Makefile.ref")
-    subprocess.run([HARNESS, "formulation", HERE], check=True)
+    only = set(sys.argv[1:])
+    unknown = only - {c[-1] for c in CASES}
+    if unknown:
+        sys.exit(f"unknown tags: {sorted(unknown)}")
+    if not only:
+        subprocess.run([HARNESS, "formulation", HERE], check=True)
     for case in CASES:
         mode, tag = case[0], case[-1]
+        if only and tag not in only:
+            continue
+        if mode == "bk_file":
+            write_bk_file_inputs(tag, case[1])
         if mode == "newton" and len(case) in (9, 11):
             # harness order: ... <iters> <tag> <ineq> <ineq bounds> <var bounds> [<p> <equality handling>]
             args = [HARNESS, mode, HERE] + [str(a) for a in case[1:5]] + [tag] + [str(a) for a in case[5:-1]]
@@ -92,7 +118,12 @@ def main():
         "cases": [list(map(str, c)) for c in CASES],
         "files": {},
     }
+    if only:  # the other tags' entries stay as they are
+        with open(os.path.join(HERE, "manifest.json")) as fh:
+            manifest["files"] = json.load(fh)["files"]
     for f in sorted(os.listdir(HERE)):
+        if only and not any(f.startswith(t + "_") for t in only):
+            continue
         if f.endswith(".bin") or f.endswith(".txt"):
             with open(os.path.join(HERE, f), "rb") as fh:
                 data = fh.read()
