@@ -86,6 +86,10 @@
  *                                  tangents of the data (ntan per QP, or one set shared by
  *                                  the batch) to the residual rows d r_v / d data applied to
  *                                  them, the input of ipmz_*_newton_solve_multi
+ *   ipmz_batch_center           <- no reference counterpart: Newton iterations from a solved
+ *                                  iterate onto the central path at a fixed barrier parameter
+ *                                  kappa (r(z; mu = kappa) = 0), where the derivative calls
+ *                                  above are exact at any active set
  *
  * Conventions
  *   - Plain pointers and sizes only.  "device" pointers are HIP device
@@ -1147,6 +1151,87 @@ typedef struct ipmz_qp_device_tangent {
   int64_t tQ, tA, tC, tc, tlx, tux, tlA, tuA, td;  /* tangent strides, in elements */
 } ipmz_qp_device_tangent;
 int ipmz_batch_data_jvp(ipmz_qp* qp, int ntan, const ipmz_qp_device_tangent* tan, double* R, int64_t ldr, int64_t sR);
+
+/* Centering on the central path: damped Newton iterations from the current
+ * iterate toward the point z with r(z; mu = kappa) = 0 of every QP of the
+ * solver (a solver of ipmz_qp_create is a batch of one), kappa > 0 a constant
+ * of the call.  Why: the adjoint, vjp and jvp calls above differentiate the
+ * Newton system at the current iterate with mu held constant.  At the final
+ * iterate of a solve (mu about 1e-9, a function of the data) that is the
+ * derivative of the solution map only where strict complementarity holds.  On
+ * the central path at a FIXED kappa the Jacobian J is nonsingular whatever the
+ * active set, theta -> z(theta; kappa) is smooth, and the same calls, unchanged,
+ * return its exact derivative, duals included.  The solve loop and its stop
+ * rule are not touched; call this after a solve.
+ *
+ * Per iteration, on the context's stream:
+ *   test       r_v(z; mu = kappa) of every QP by the step's own residual pass,
+ *              e_q = ||r||_inf over all ipmz_qp_state_len entries (workgroup
+ *              partials, then their maximum in index order: no atomics).  A QP
+ *              with e_q <= tol is centered and frozen from then on: its iterate
+ *              keeps its bits and it takes part in no later update.  A NaN
+ *              never passes.
+ *   direction  d = -J^{-1} r: the map of ipmz_*_newton_solve_multi for one row
+ *              per QP -- the same assembly, the formulation's own factor (fp64
+ *              LDL^T, Bunch-Kaufman for IPMZ_EQ_NONE), the same solves and
+ *              slack-first back-substitution -- and that call's step length
+ *              alpha.  Every QP is factored, centered or not.
+ *   update     z <- z + 0.995 alpha d for the QPs not centered (the step's own
+ *              update rule); the workgroups of the others return at the top of
+ *              the launch.
+ * The loop ends when every QP is centered or max_iter updates were applied; a
+ * test follows the last update.  The host looks at the device once per
+ * iteration -- two doubles of a summary launch and the factor's words -- never
+ * at batch x state_len values.  max_iter == 0 tests, evaluates and reports, and
+ * moves nothing.
+ *
+ * Afterwards every QP is evaluated as ipmz_batch_set_state does: the residual
+ * slots and the scalar block are bitwise what ipmz_batch_set_state(qp, q, z_q)
+ * leaves (IPMZ_SC_MU about kappa; IPMZ_SC_CONVERGED 0 for kappa > 1e-8), and
+ * later steps continue from there.
+ *
+ * iterations (host, batch ints, may be NULL): the updates QP q received.
+ * centered_count (host, may be NULL): the QPs that passed the test.  Returns as
+ * the Newton-solve pair does: the smallest non-zero factor info word any
+ * iteration met, else IPMZ_OK; a raised sticky error word is IPMZ_ERR_HIP.  The
+ * call synchronizes.
+ *
+ * Only stream-ordered launches, no cross-workgroup waiting, no atomics: a QP's
+ * result does not depend on the other QPs of the batch (given the same kernel
+ * selection), and equal inputs give equal bits.  The Newton formulas are not
+ * restated: the kernels are the step's residual pass and update and the
+ * Newton-solve pair's right-hand side, back-substitution and ratio test.
+ * Overwritten: the iterate, the direction slot (IPMZ_STATE_DIR), the residual
+ * slots and the scalar block's evaluated entries.  Untouched: the data, a
+ * captured step graph, the blocking, the restart snapshot, IPMZ_SC_STEPS and
+ * the scalar block's layout.  A small device buffer of the solver (a few
+ * doubles per QP and workgroup) is allocated on first use.
+ *
+ * Served: every formulation ipmz_*_newton_solve_multi serves except those
+ * below; single QPs of any N; batches on every path that call has (the
+ * one-launch blocked solve, the panel chain for N > 1024, inner block 128,
+ * IPMZ_EQ_NONE batches with N <= 4096).
+ * IPMZ_ERR_INVALID, before anything is enqueued: a null qp; kappa or tol not
+ * finite or <= 0; max_iter < 0; an enabled normal-equations reduction or mixed
+ * precision; IPMZ_EQ_SLACKED_SLACKS / IPMZ_EQ_NAIVE_SLACKS (as the Newton-solve
+ * pair); IPMZ_EQ_PENALTY / IPMZ_EQ_PENALTY_EXTRA_DUAL (their KKT block is
+ * -mu I with the environment's mu, which centering would have to own);
+ * IPMZ_INEQ_SLACKS (its solves never converge -- the reference's corrector
+ * defect -- so there is no solved iterate to center); IPMZ_EQ_NONE batches
+ * with N > 4096.  IPMZ_ERR_STATE: before a load, between a load and
+ * ipmz_batch_initialize, and while the context's stream is capturing.
+ *
+ * tol and max_iter are the caller's: 1e-10 and 30 (the Python defaults) come
+ * from a CPU prototype of this loop in numpy -- generated QPs (48,16,8),
+ * (130,40,22), (12,0,0) at kappa 1e-2 .. 1e-6 centered in 2-6 iterations from a
+ * converged iterate, a diagonal box QP with coordinates on a bound in 9-12.
+ * Measured on an MI355X (DESIGN.md "Centering on the central path",
+ * profiles/center/bench.json): 1024 QPs of n = 256, m = 48, p = 16 and one QP
+ * of n = 8192, m = 2048, p = 1024 are centered in at most 11 iterations at
+ * kappa 1e-2 .. 1e-6; an iteration costs 1.23 and 0.98 Newton steps there. */
+int ipmz_batch_center(ipmz_qp* qp, double kappa, double tol, int max_iter,
+                      int* iterations /* host, batch ints, may be NULL */,
+                      int* centered_count /* host, may be NULL */);
 
 /* Phase timing (HIP events on the context stream; eager launches only).
  * ms: host array of IPMZ_PH_COUNT floats, cumulative since enable. */

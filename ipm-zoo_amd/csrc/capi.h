@@ -210,6 +210,21 @@ inline JvpWs jvp_ws(char* base, int64_t elems) {
   return w;
 }
 
+// ipmz_batch_center's state on the device (kernels.h CenterWs): a few doubles and two ints per QP
+inline CenterWs center_ws(char* base, int batch, int nb) {
+  CenterWs w;
+  Carver c{base};
+  w.part = c.take<double>((int64_t)batch * nb);
+  w.e = c.take<double>(batch);
+  w.alpha = c.take<double>(batch);
+  w.sum = c.take<double>(2);
+  w.frozen = c.take<int>(batch);
+  w.iters = c.take<int>(batch);
+  w.nb = nb;
+  w.total = c.off;
+  return w;
+}
+
 // the workspace whose sticky error words the next ipmz_ctx_sync checks (pe:
 // a panel factor's, may be null; se: a persistent solve's)
 inline void watch(ipmz_ctx* ctx, const unsigned* pe, const unsigned* se) {

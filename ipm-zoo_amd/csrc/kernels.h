@@ -646,6 +646,26 @@ inline bool fused_solves_ok(int N, int64_t ld) { return N <= 4096 && !(ld & 1); 
 hipError_t qp_fused_solves(const QPBatch& qb, const double* K, int64_t ld, int N, const double* D, const double* Linv,
                            double* b, int64_t sK, int64_t sD, int64_t sL, int64_t sb, int freeze, hipStream_t st);
 hipError_t qp_fused_eval(const QPBatch& qb, hipStream_t st);
+// Centering on the central path (ipmz_batch_center): the solver's small device
+// buffer (capi.h center_ws carves it) and the two launch groups the loop adds
+// to the Newton-solve path.  nb = qp_center_blocks: the norm's workgroups per QP.
+struct CenterWs {
+  double* part = nullptr;   // B x nb: the workgroups' partial maxima of |r_v(z; kappa)|
+  double* e = nullptr;      // B: the QP's norm at its last test
+  double* alpha = nullptr;  // B: the step length of the QP's direction (before the 0.995)
+  double* sum = nullptr;    // the host's look: {QPs not centered, the largest e among them}
+  int* frozen = nullptr;    // B: 1 from the test the QP passed on
+  int* iters = nullptr;     // B: updates the QP received
+  int nb = 0;
+  int64_t total = 0;
+};
+int qp_center_blocks(const QPBatch& qb);
+// Q x, A x, ... of the iterate, r_v(z; mu = kappa) into the residual slots (the evaluation's own launch), the
+// infinity norm over all state_len of them per QP not yet frozen, then one launch: e, the flag raised where
+// e <= tol (a NaN never passes), and w.sum
+hipError_t qp_center_test(const QPBatch& qb, double kappa, double tol, const CenterWs& w, hipStream_t st);
+// z <- z + 0.995 alpha[QP] dir for the QPs not frozen (qp_update's kernel behind its gate), iters[QP] += 1
+hipError_t qp_center_update(const QPBatch& qb, const CenterWs& w, hipStream_t st);
 
 // io.hip, grad.hip, jvp.hip ---------------------------------------------------
 // The nine blocks of a QP's data as a caller hands them over in device memory (ipmz_qp_device_data, _grad and

@@ -438,7 +438,8 @@ static int red_blocks(int total) {
   return b < 1 ? 1 : (b > RED_BLOCKS ? RED_BLOCKS : b);
 }
 
-hipError_t qp_evaluate(const QPBatch& qb, hipStream_t st) {
+// the products of the current iterate that the residual pass reads: Q x, A x, A^T (its dual), C x, C^T lambda_C
+static void evaluate_products(const QPBatch& qb, hipStream_t st) {
   const QPDev& h = qb.h;
   hipLaunchKernelGGL((k_matvec_rows<MV_Q>), grid2((h.n + 3) / 4, qb.B), dim3(NT), 0, st, qb.d);
   if (h.m) {
@@ -449,6 +450,11 @@ hipError_t qp_evaluate(const QPBatch& qb, hipStream_t st) {
     hipLaunchKernelGGL((k_matvec_rows<MV_C>), grid2((h.p + 3) / 4, qb.B), dim3(NT), 0, st, qb.d);
     matvec_t<MV_C>(qb, st);
   }
+}
+
+hipError_t qp_evaluate(const QPBatch& qb, hipStream_t st) {
+  const QPDev& h = qb.h;
+  evaluate_products(qb, st);
   const int nb = red_blocks(residual_rows(h));
   hipLaunchKernelGGL(k_residuals, grid2(nb, qb.B), dim3(NT), 0, st, qb.d, 0.0, 1);
   hipLaunchKernelGGL(k_stats_final, grid2(1, qb.B), dim3(NT), 0, st, qb.d, nb);
@@ -1390,16 +1396,26 @@ __device__ __forceinline__ void update_elem(const QPDev& q, int t, double s) {
     if (!q.eqnone && !q.eqpen) up(P, t);
   }
 }
-__global__ void k_update(const QPDev* __restrict__ qs, int freeze) {
+// The same rule for the centering loop (qp_center_update below), when frozen is given: QP z sits out where
+// frozen[z] != 0 -- its workgroups return here, at the top of the launch -- its step length is alpha[z] (before the
+// 0.995), and count[z] counts the updates it received.
+struct UpdateGate {
+  const int* frozen = nullptr;
+  const double* alpha = nullptr;
+  int* count = nullptr;
+};
+__global__ void k_update(const QPDev* __restrict__ qs, int freeze, UpdateGate g) {
   const QPDev& q = qs[blockIdx.y];
-  if (freeze && q.scal[SC_CONVERGED] != 0.0) return;
-  update_elem(q, blockIdx.x * NT + threadIdx.x, 0.995 * q.scal[SC_ALPHA]);
+  if (g.frozen ? g.frozen[blockIdx.y] != 0 : (freeze && q.scal[SC_CONVERGED] != 0.0)) return;
+  update_elem(q, blockIdx.x * NT + threadIdx.x, 0.995 * (g.frozen ? g.alpha[blockIdx.y] : q.scal[SC_ALPHA]));
+  if (g.frozen && blockIdx.x == 0 && threadIdx.x == 0) g.count[blockIdx.y] += 1;
 }
-
-hipError_t qp_update(const QPBatch& qb, int freeze, hipStream_t st) {
-  hipLaunchKernelGGL(k_update, grid2((update_rows(qb.h) + NT - 1) / NT, qb.B), dim3(NT), 0, st, qb.d, freeze);
+static hipError_t launch_update(const QPBatch& qb, int freeze, const UpdateGate& g, hipStream_t st) {
+  hipLaunchKernelGGL(k_update, grid2((update_rows(qb.h) + NT - 1) / NT, qb.B), dim3(NT), 0, st, qb.d, freeze, g);
   return hipGetLastError();
 }
+
+hipError_t qp_update(const QPBatch& qb, int freeze, hipStream_t st) { return launch_update(qb, freeze, UpdateGate{}, st); }
 
 // Benchmark restart: a converged iterate is reset (on device, no host sync)
 // to the saved initial state, so every timed step is a real Newton step.
@@ -1831,6 +1847,89 @@ hipError_t qp_fused_post(const QPBatch& qb, int freeze, hipStream_t st) {
   hipLaunchKernelGGL(k_fused_post, dim3(qb.B), dim3(FT), 0, st, qb.d, freeze, qb.skip);
   hipLaunchKernelGGL(k_fused_eval, dim3(eval_split(qb), qb.B), dim3(FT), 0, st, qb.d, qb.skip);
   return hipGetLastError();
+}
+
+// ---------------------------------------------------------------------------
+// Centering on the central path (ipmz_batch_center; DESIGN.md "Centering on the
+// central path"): damped Newton toward r(z; mu = kappa) = 0 with kappa a constant
+// of the call.  Nothing of the Newton step is restated: the test is the step's
+// own residual pass at mu = kappa (k_residuals, the evaluation's launch without
+// its statistics) followed by the infinity norm over the residual slots, the
+// direction is ipmz_*_newton_solve_multi's map for one row per QP on the
+// solver's own slots (qp.cpp), the update is k_update behind its gate.
+//
+// The norm crosses workgroups without atomics: every workgroup of a QP writes
+// the maximum of its strided share of the state_len residuals (two per lane and
+// load: the slots are contiguous and 16-byte aligned) to its own partial, and
+// one thread per QP of the summary launch takes the maximum over the partials
+// in index order.  A NaN counts as +infinity, so it never passes e <= tol.  A
+// QP that passed is frozen: the flag is only ever raised, and the norm, the
+// summary and the update skip it.
+__global__ __launch_bounds__(NT) void k_center_norm(const QPDev* __restrict__ qs, CenterWs w) {
+  if (w.frozen[blockIdx.y]) return;
+  const QPDev& q = qs[blockIdx.y];
+  __shared__ double sh[NT / 64];
+  const double* __restrict__ r = q.r[0];
+  auto mag = [](double v) {
+    v = fabs(v);
+    return v == v ? v : INFINITY;
+  };
+  const int64_t pairs = q.state_len / 2;
+  double a = 0.0;
+  for (int64_t t = blockIdx.x * (int64_t)NT + threadIdx.x; t < pairs; t += (int64_t)gridDim.x * NT) {
+    const double2 v = reinterpret_cast<const double2*>(r)[t];
+    a = fmax(a, fmax(mag(v.x), mag(v.y)));
+  }
+  if ((q.state_len & 1) && blockIdx.x == 0 && threadIdx.x == 0) a = fmax(a, mag(r[q.state_len - 1]));
+  a = wave_max(a);
+  if ((threadIdx.x & 63) == 0) sh[threadIdx.x >> 6] = a;
+  __syncthreads();
+  if (threadIdx.x == 0) {
+    for (int k = 1; k < NT / 64; ++k) a = fmax(a, sh[k]);
+    w.part[blockIdx.y * (int64_t)w.nb + blockIdx.x] = a;
+  }
+}
+// the test of every QP not yet frozen, and the host's look: sum = {QPs not centered, the largest e among them}
+__global__ __launch_bounds__(NT) void k_center_summary(int B, double tol, CenterWs w) {
+  __shared__ double sh[2][NT];
+  double open = 0.0, worst = 0.0;
+  for (int b = threadIdx.x; b < B; b += NT) {
+    if (w.frozen[b]) continue;
+    double e = 0.0;
+    for (int k = 0; k < w.nb; ++k) e = fmax(e, w.part[b * (int64_t)w.nb + k]);
+    w.e[b] = e;
+    if (e <= tol) {
+      w.frozen[b] = 1;
+    } else {
+      open += 1.0;
+      worst = fmax(worst, e);
+    }
+  }
+  sh[0][threadIdx.x] = open;
+  sh[1][threadIdx.x] = worst;
+  __syncthreads();
+  for (int s = NT / 2; s > 0; s >>= 1) {
+    if (threadIdx.x < s) {
+      sh[0][threadIdx.x] += sh[0][threadIdx.x + s];
+      sh[1][threadIdx.x] = fmax(sh[1][threadIdx.x], sh[1][threadIdx.x + s]);
+    }
+    __syncthreads();
+  }
+  if (threadIdx.x < 2) w.sum[threadIdx.x] = sh[threadIdx.x][0];
+}
+
+int qp_center_blocks(const QPBatch& qb) { return red_blocks((int)((qb.h.state_len + 1) / 2)); }
+
+hipError_t qp_center_test(const QPBatch& qb, double kappa, double tol, const CenterWs& w, hipStream_t st) {
+  evaluate_products(qb, st);
+  hipLaunchKernelGGL(k_residuals, grid2(red_blocks(residual_rows(qb.h)), qb.B), dim3(NT), 0, st, qb.d, kappa, 0);
+  hipLaunchKernelGGL(k_center_norm, grid2(w.nb, qb.B), dim3(NT), 0, st, qb.d, w);
+  hipLaunchKernelGGL(k_center_summary, dim3(1), dim3(NT), 0, st, qb.B, tol, w);
+  return hipGetLastError();
+}
+
+hipError_t qp_center_update(const QPBatch& qb, const CenterWs& w, hipStream_t st) {
+  return launch_update(qb, 0, UpdateGate{w.frozen, w.alpha, w.iters}, st);
 }
 
 }  // namespace ipmz

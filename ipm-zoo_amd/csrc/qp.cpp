@@ -57,6 +57,8 @@ struct ipmz_qp {
   // ipmz_*_newton_solve_multi / ipmz_*_newton_adjoint_multi: the reduced right-hand sides, B x nrhs x round_up(N, 2)
   // doubles, for the largest nrhs seen
   GrowBuf nmws;
+  // ipmz_batch_center: the norm's partials, the centered flags and the update counts (center_ws), on first use
+  GrowBuf cws;
   // ipmz_batch_data_vjp(_multi): the shared matrix blocks' partial products (vjp_ws), when one is first asked for,
   // grown for the largest slab of cotangent rows seen
   GrowBuf vjpws;
@@ -1463,6 +1465,76 @@ int ipmz_batch_newton_adjoint_multi(ipmz_qp* s, int nrhs, const double* G, int64
     return rc;
   }
   return newton_multi(s, "ipmz_batch_newton_adjoint_multi", true, nrhs, G, ldg, sG, Out, ldo, sO, nullptr, info);
+}
+
+// Damped Newton toward the central-path point r(z; mu = kappa) = 0 of every QP (newton.hip "Centering on the
+// central path").  One iteration is newton_multi's map for one row per QP with the solver's own slots as its
+// block -- R the residual slots, Dir the direction slot, both contiguous in Newton order and aligned by
+// construction, so the public checks of strides and alignment are not gone through -- between the test
+// (qp_center_test) and the gated update (qp_center_update).  The host looks at the device once per iteration: the
+// summary's two doubles, copied ahead of the synchronize in which kkt_finish reads the factor's words.
+int ipmz_batch_center(ipmz_qp* s, double kappa, double tol, int max_iter, int* iterations, int* centered_count) {
+  const std::string who = "ipmz_batch_center";
+  if (!s) return fail(IPMZ_ERR_INVALID, who + ": null qp");
+  if (!(kappa > 0.0 && kappa < INFINITY)) return fail(IPMZ_ERR_INVALID, who + ": kappa must be finite and > 0");
+  if (!(tol > 0.0 && tol < INFINITY)) return fail(IPMZ_ERR_INVALID, who + ": tol must be finite and > 0");
+  if (max_iter < 0) return fail(IPMZ_ERR_INVALID, who + ": max_iter < 0");
+  if (s->normal) return fail(IPMZ_ERR_INVALID, who + ": the normal-equations reduction is enabled (augmented system only)");
+  if (s->mixed) return fail(IPMZ_ERR_INVALID, who + ": mixed precision is enabled (fp64 factors only)");
+  if (s->eqss)
+    return fail(IPMZ_ERR_INVALID, who + ": EqualityHandling::SlackedSlacks / NaiveSlacks keep a permuted, merged view of "
+                                        "the Newton order on the device; not served");
+  if (s->eqpen)
+    return fail(IPMZ_ERR_INVALID, who + ": EqualityHandling::PenaltyFunction puts the environment's mu into the KKT "
+                                        "matrix; centering would have to own that mu; not served");
+  if (s->slacks)
+    return fail(IPMZ_ERR_INVALID, who + ": InequalityHandling::Slacks never converges (the reference's corrector "
+                                        "defect): there is no solved iterate to center; not served");
+  if (path_of(s) == Path::BkBatch && (s->N > IPMZ_BK_NMAX || s->B > 65535))
+    return fail(IPMZ_ERR_INVALID, who + ": EqualityHandling::None batches: N <= 4096 and batch <= 65535");
+  if (!s->loaded) return fail(IPMZ_ERR_STATE, who + ": load (and initialize) the QP first");
+  HIP_OK(hipSetDevice(s->ctx->device));
+  int rc;
+  if ((rc = not_capturing(s->ctx, who.c_str()))) return rc;
+  if ((rc = wait_pending_step(s))) return rc;
+  if ((rc = kkt_ws_ensure(s))) return rc;
+  // (every call ends synchronized, so growing the two buffers here is safe)
+  const int64_t ldw = round_up(s->N, 2);
+  if ((rc = grow(s, s->nmws, (size_t)(ldw * s->B) * sizeof(double)))) return rc;
+  const int nb = qp_center_blocks(s->qb);
+  if ((rc = grow(s, s->cws, (size_t)center_ws(nullptr, s->B, nb).total))) return rc;
+  const CenterWs w = center_ws(s->cws.p, s->B, nb);
+  hipStream_t st = s->ctx->stream;
+  double* W = reinterpret_cast<double*>(s->nmws.p);
+  const double* R = q0(s).r[0];
+  double* Dir = q0(s).dir[0];
+  const int64_t ldv = round_up(s->state_len, 2), sV = s->B > 1 ? s->hq[1].r[0] - s->hq[0].r[0] : 0;
+  HIP_OK(hipMemsetAsync(w.frozen, 0, sizeof(int) * (size_t)s->B, st));
+  HIP_OK(hipMemsetAsync(w.iters, 0, sizeof(int) * (size_t)s->B, st));
+  double sum[2] = {0.0, 0.0};
+  HIP_OK(qp_center_test(s->qb, kappa, tol, w, st));
+  HIP_OK(hipMemcpyAsync(sum, w.sum, sizeof sum, hipMemcpyDeviceToHost, st));
+  HIP_OK(hipStreamSynchronize(st));
+  int info = IPMZ_OK;
+  for (int it = 0; it < max_iter && sum[0] != 0.0; ++it) {
+    HIP_OK(qp_rhs_multi(s->qb, R, ldv, sV, W, ldw, ldw, 1, st));
+    if ((rc = kkt_enqueue(s, W, ldw, ldw, 1))) return rc;
+    HIP_OK(qp_backsub_multi(s->qb, R, ldv, sV, W, ldw, ldw, Dir, ldv, sV, 1, st));
+    HIP_OK(qp_ratio_multi(s->qb, Dir, ldv, sV, w.alpha, 1, st));
+    HIP_OK(qp_center_update(s->qb, w, st));
+    HIP_OK(qp_center_test(s->qb, kappa, tol, w, st));
+    HIP_OK(hipMemcpyAsync(sum, w.sum, sizeof sum, hipMemcpyDeviceToHost, st));
+    rc = kkt_finish(s, who.c_str(), nullptr);  // synchronizes
+    if (rc < 0) return rc;
+    if (rc > 0 && (info == IPMZ_OK || rc < info)) info = rc;
+  }
+  // every QP evaluated as ipmz_batch_set_state does: the residual slots back at mu = 0, the scalar block's
+  // evaluated entries those of the iterate
+  HIP_OK(qp_evaluate(s->qb, st));
+  if (iterations) HIP_OK(hipMemcpyAsync(iterations, w.iters, sizeof(int) * (size_t)s->B, hipMemcpyDeviceToHost, st));
+  HIP_OK(hipStreamSynchronize(st));
+  if (centered_count) *centered_count = s->B - (int)sum[0];
+  return info;
 }
 
 // the QP's mixed-precision workspace, allocated once (a captured step keeps its addresses)

@@ -59,7 +59,7 @@ EXPORTS = [
     "ipmz_qp_newton_adjoint_multi", "ipmz_batch_newton_adjoint_multi",
     "ipmz_batch_load_device", "ipmz_batch_copy_state", "ipmz_batch_data_vjp", "ipmz_batch_data_jvp",
     "ipmz_batch_data_vjp_multi", "ipmz_batch_set_state_device", "ipmz_qp_get_factor",
-    "ipmz_batch_solve_ex", "ipmz_batch_can_skip_converged",
+    "ipmz_batch_solve_ex", "ipmz_batch_can_skip_converged", "ipmz_batch_center",
 ]
 SOLVE_MULTI_PANEL = 256  # include/ipmz.h IPMZ_SOLVE_MULTI_PANEL: column panel of the blocked multi-rhs solve
 REDUCTION_AUGMENTED, REDUCTION_NORMAL = 0, 1
@@ -274,6 +274,7 @@ def _load():
         "ipmz_batch_set_state_device": ([_VP, _VP, _I64, _VP, ctypes.c_double, _I], _I),
         "ipmz_batch_solve_ex": ([_VP, _I, _I, _I, ctypes.POINTER(_I), ctypes.POINTER(_I)], _I),
         "ipmz_batch_can_skip_converged": ([_VP], _I),
+        "ipmz_batch_center": ([_VP, ctypes.c_double, ctypes.c_double, _I, ctypes.POINTER(_I), ctypes.POINTER(_I)], _I),
     }
     for name, (args, res) in sig.items():
         fn = getattr(lib, name)
@@ -913,6 +914,24 @@ class Optimizer:
     def set_mixed_precision(self, enable=True, tol=1e-12, max_refine=10):
         """Newton directions via the fp32 factor + fp64 refinement (config C5)."""
         _check(lib.ipmz_qp_set_mixed_precision(self.h, int(enable), tol, max_refine), "ipmz_qp_set_mixed_precision")
+
+    def center(self, kappa, tol=1e-10, max_iter=30):
+        """Newton iterations from the current iterate onto the central path at the fixed barrier parameter kappa,
+        r(z; mu = kappa) = 0, for every QP of the solver: ipmz_batch_center.  Returns (iterations, centered): the
+        updates each QP received (an int ndarray, one entry per QP) and how many QPs reached
+        |r(z; kappa)|inf <= tol within max_iter updates; a centered QP is frozen.  Call it after a solve: the
+        derivative calls (newton_adjoint, data_grad_tensors, data_jvp_tensors, ipmz_amd.layer) then return the
+        exact derivative of data -> z(data; kappa), duals included, at any active set.  Afterwards every QP is
+        evaluated as set_state does (scalars()["mu"] is about kappa) and steps continue from there.  tol and
+        max_iter are parameters; their defaults come from a CPU prototype of the loop (include/ipmz.h; the device's
+        counts and the cost of an iteration: DESIGN.md "Centering on the central path")."""
+        self._bump()
+        batch = lib.ipmz_batch_size(self.h)
+        its = np.zeros(batch, dtype=np.int32)
+        nc = ctypes.c_int(0)
+        _check(lib.ipmz_batch_center(self.h, float(kappa), float(tol), int(max_iter),
+                                     its.ctypes.data_as(ctypes.POINTER(_I)), ctypes.byref(nc)), "ipmz_batch_center")
+        return its, nc.value
 
     def scalars(self):
         out = np.zeros(SC_COUNT)

@@ -23,9 +23,12 @@ class _SolveQP(torch.autograd.Function):
     @staticmethod
     def forward(ctx, solver, max_iter, strict, symmetrize, *blocks):
         # (after the data blocks: the warm start, an iterate per QP and its floor, then solve_all's skip_converged
-        # and check_every -- no inputs of the derivative)
+        # and check_every, then -- only when asked for -- the barrier parameter of the centering with its tolerance
+        # and iteration limit; no inputs of the derivative)
         blocks, warm = blocks[:len(_NAMES)], blocks[len(_NAMES):]
         skip_converged, check_every = warm[2:4] if len(warm) >= 4 else (False, 1)
+        barrier, barrier_tol, barrier_max_iter = warm[4:7] if len(warm) >= 7 else (None, 1e-10, 30)
+        ctx.extra = len(warm)
         given = {k: t.detach() for k, t in zip(_NAMES, blocks) if t is not None}
         solver.load_tensors(**given)
         if warm and warm[0] is not None:
@@ -43,6 +46,12 @@ class _SolveQP(torch.autograd.Function):
         if strict and converged != batch:
             raise IpmzError(f"solve_qp: {batch - converged} of {batch} QPs did not converge in {max_iter} iterations "
                             "(strict=True: the gradient is that of the solution map only at a converged solution)")
+        if barrier is not None:
+            its, centered = solver.center(barrier, barrier_tol, barrier_max_iter)
+            if strict and centered != batch:
+                raise IpmzError(f"solve_qp: {batch - centered} of {batch} QPs were not centered on the central path "
+                                f"at barrier={barrier} to barrier_tol={barrier_tol} in {barrier_max_iter} iterations "
+                                "(strict=True: the gradient is exact only at a centered iterate)")
         x = solver.solution_tensor().clone()
         ctx.solver, ctx.symmetrize = solver, symmetrize
         ctx.generation = solver._generation
@@ -77,7 +86,7 @@ class _SolveQP(torch.autograd.Function):
             if g is None and k in wanted:  # a block of dimension 0
                 g = torch.zeros(ctx.shapes[k], dtype=torch.float64, device=grad_x.device)
             out.append(None if g is None else g.reshape(ctx.shapes[k]))
-        return (None, None, None, None, *out, None, None, None, None)
+        return (None, None, None, None, *out, *([None] * ctx.extra))
 
     @staticmethod
     def jvp(ctx, _solver, _max_iter, _strict, _symmetrize, *tangents):
@@ -111,10 +120,14 @@ def solution_jvp(solver, **tangents):
     leading entries (x leads the Newton order in every formulation), and dz, (batch, ntan, state_len).  The
     solver's iterate and generation counter do not move.
 
-    As for solve_qp's gradient: this is the derivative of the solution map only at a converged, strictly
-    complementary solution -- the implicit-function theorem on the Newton system at the current iterate with mu
-    held constant.  At an iterate that has not converged, or where a constraint is active with a zero multiplier,
-    it is the derivative of nothing in particular."""
+    What it is the derivative of depends on the iterate.  At an iterate centered on the central path
+    (Optimizer.center(kappa), or solve_qp(barrier=kappa)) it is the exact derivative of data -> z(data; kappa), the
+    point with r(z; mu = kappa) = 0, duals included, at any active set: kappa is a constant, J is nonsingular there
+    and the map is smooth.  At the final iterate of a solve without centering the old caveat stands: it is the
+    derivative of the solution map only at a converged, strictly complementary solution -- the implicit-function
+    theorem on the Newton system at the current iterate with mu held constant -- and at an iterate that has not
+    converged, or where a constraint is active with a zero multiplier, it is the derivative of nothing in
+    particular."""
     s = solver
     batch, L = lib.ipmz_batch_size(s.h), s.state_len
     R = s.data_jvp_tensors(tangents)
@@ -140,10 +153,14 @@ def solution_vjp(solver, G, *, shared=(), only=None, symmetrize=False):
     `shared`; only, symmetrize as there -- and W, the (batch, ncot, state_len) view of the residual cotangents.
     The solver's iterate and generation counter do not move.
 
-    As for solve_qp's gradient: this is the derivative of the solution map only at a converged, strictly
-    complementary solution -- the implicit-function theorem on the Newton system at the current iterate with mu
-    held constant.  At an iterate that has not converged, or where a constraint is active with a zero multiplier,
-    it is the derivative of nothing in particular."""
+    What it is the derivative of depends on the iterate.  At an iterate centered on the central path
+    (Optimizer.center(kappa), or solve_qp(barrier=kappa)) it is the exact derivative of data -> z(data; kappa), the
+    point with r(z; mu = kappa) = 0, duals included, at any active set: kappa is a constant, J is nonsingular there
+    and the map is smooth.  At the final iterate of a solve without centering the old caveat stands: it is the
+    derivative of the solution map only at a converged, strictly complementary solution -- the implicit-function
+    theorem on the Newton system at the current iterate with mu held constant -- and at an iterate that has not
+    converged, or where a constraint is active with a zero multiplier, it is the derivative of nothing in
+    particular."""
     s = solver
     batch, L, n = lib.ipmz_batch_size(s.h), s.state_len, s.n
     if not isinstance(G, torch.Tensor) or G.dtype != torch.float64 or G.dim() != 3 or G.shape[0] != batch or \
@@ -167,8 +184,9 @@ def solution_vjp(solver, G, *, shared=(), only=None, symmetrize=False):
 def solution_jacobian(solver, *, shared=(), only=None):
     """(grads, W) of solution_vjp with G the n unit rows for every QP: grads[name][q, i] is d x_i* / d name of QP q
     (for the names in `shared`, grads[name][i] is the sum over the QPs), the whole reverse-mode Jacobian of the
-    solution from one factor.  solution_vjp's caveat holds: a converged, strictly complementary iterate, mu held
-    constant."""
+    solution from one factor.  solution_vjp's note on the iterate holds: exact for data -> z(data; kappa) at an
+    iterate centered on the central path (Optimizer.center), at any active set; otherwise only at a converged,
+    strictly complementary iterate, mu held constant."""
     s = solver
     batch, n = lib.ipmz_batch_size(s.h), s.n
     G = torch.eye(n, dtype=torch.float64, device=f"cuda:{s.ctx.device}").expand(batch, n, n)
@@ -177,7 +195,7 @@ def solution_jacobian(solver, *, shared=(), only=None):
 
 def solve_qp(solver, *, Q=None, c=None, l_x=None, u_x=None, A_ineq=None, l_A_ineq=None, u_A_ineq=None, A_eq=None,
              b_eq=None, max_iter=100, strict=True, symmetrize=False, warm_start=None, warm_floor=0.0,
-             skip_converged=False, check_every=1):
+             skip_converged=False, check_every=1, barrier=None, barrier_tol=1e-10, barrier_max_iter=30):
     """x* of every QP of `solver` (an Optimizer or a Batch), (batch, n), differentiable with respect to the data.
 
     The data are float64 CUDA tensors under load_tensors' names and rules: matrices (batch, rows, n) or (rows, n)
@@ -186,10 +204,25 @@ def solve_qp(solver, *, Q=None, c=None, l_x=None, u_x=None, A_ineq=None, l_A_ine
     the adjoint Newton solve at the final iterate, then ipmz_batch_data_vjp; an input given once for every QP
     receives the gradient summed over the batch, inputs that do not require grad are skipped.
 
-    The gradient is that of the solution map only at a converged, strictly complementary solution: it is the
-    implicit-function theorem on the Newton system at the final iterate with mu held constant, so at an iterate that
-    has not converged, or where a constraint is active with a zero multiplier, it is the derivative of nothing in
-    particular.  strict=True (default) raises IpmzError when any QP did not converge in max_iter steps.
+    barrier=None (default): the gradient is that of the solution map only at a converged, strictly complementary
+    solution: it is the implicit-function theorem on the Newton system at the final iterate with mu held constant,
+    so at an iterate that has not converged, or where a constraint is active with a zero multiplier, it is the
+    derivative of nothing in particular (a coordinate that sits on a bound gets gradient 0, a weakly active one
+    whatever the ill-conditioned Newton system returns).  strict=True (default) raises IpmzError when any QP did
+    not converge in max_iter steps.
+
+    barrier=kappa > 0: after the same solve (and the same strict check) every QP is moved onto the central path at
+    the fixed barrier parameter kappa, solver.center(kappa, barrier_tol, barrier_max_iter): x is then x(data; kappa)
+    with r(z; mu = kappa) = 0, within O(kappa) of x*, and backward, jvp, solution_jvp, solution_vjp and
+    solution_jacobian return the exact derivative of data -> z(data; kappa), duals included, at any active set --
+    kappa is a constant of the problem, J is nonsingular there and the map is smooth, so a coordinate on a bound
+    gets a gradient strictly between 0 and the unconstrained one.  strict=True also raises when a QP was not
+    centered.  barrier_tol (|r(z; kappa)|inf <= barrier_tol) and barrier_max_iter are parameters; their defaults
+    1e-10 and 30 come from a CPU prototype of the loop in numpy (2-6 iterations from a converged iterate on
+    generated QPs at kappa 1e-2 .. 1e-6, 9-12 on a diagonal box QP with coordinates on a bound; include/ipmz.h at
+    ipmz_batch_center); on the device 1024 QPs of n = 256 and one of n = 8192 needed at most 11, an iteration costing
+    about one Newton step (DESIGN.md "Centering on the central path").  Not served: EQ_PENALTY, INEQ_SLACKS and what the adjoint
+    solve refuses.  barrier=None is the path without the call, bit for bit.
 
     Q's entries are independent inputs: dL/dQ = w_x x^T, not symmetric.  symmetrize=True returns (gQ + gQ^T) / 2,
     the gradient for a caller who builds Q symmetric.  Formulations: those the adjoint solve serves (not
@@ -215,5 +248,6 @@ def solve_qp(solver, *, Q=None, c=None, l_x=None, u_x=None, A_ineq=None, l_A_ine
     given = dict(Q=Q, c=c, l_x=l_x, u_x=u_x, A_ineq=A_ineq, l_A_ineq=l_A_ineq, u_A_ineq=u_A_ineq, A_eq=A_eq, b_eq=b_eq)
     if warm_start is not None:
         warm_start = warm_start.detach()
+    extra = () if barrier is None else (float(barrier), float(barrier_tol), int(barrier_max_iter))
     return _SolveQP.apply(solver, max_iter, strict, symmetrize, *[given[k] for k in _NAMES], warm_start, warm_floor,
-                          skip_converged, check_every)
+                          skip_converged, check_every, *extra)
